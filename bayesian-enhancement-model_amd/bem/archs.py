@@ -154,15 +154,10 @@ class Decomp(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-# Stage-II: DecompDualBranchDDWavelet
+# Stage-II: the U-Net pieces every arch is built from
 # ------------------------------------------------------------------------------------------------
 class _Dec(nn.ModuleDict):
     pass
-
-
-def _decoder(dim, nb, ds, ssm_ratio, mlp_ratio, mlp_type):
-    return _Dec({"up": ConvT2x2(dim, dim // 2), "fuse": PwConv2d(dim, dim // 2, bias=False),
-                 "block": make_vss_level(dim // 2, nb, ds, ssm_ratio, mlp_ratio, mlp_type)})
 
 
 def _check_last_act(last_act):
@@ -171,47 +166,126 @@ def _check_last_act(last_act):
     return nn.Identity()
 
 
-class DecompDualBranchDDWavelet(nn.Module):
+def _first_conv(cin, n_feat):
+    fc = Conv2dK(cin, n_feat, 3, 1, 1, bias=True)
+    nn.init.kaiming_normal_(fc.weight, mode="fan_out", nonlinearity="linear")
+    nn.init.zeros_(fc.bias)
+    return fc
+
+
+def _hamilton(o1, o2, train):
+    """Hamilton(o1, o2)[1:] of two (B,4,H,W) quaternion maps -> (B,3,H,W): an autograd node in training, the kernel otherwise."""
+    if train:
+        return ag.HamiltonFn.apply(o1, o2)
+    B, _, H, W = o1.shape
+    out8 = torch.empty(B, 8, H, W, device=o1.device, dtype=o1.dtype)
+    ops.copy_channels(o1, out8, 0)
+    ops.copy_channels(o2, out8, 4)
+    return ops.hamilton(out8)
+
+
+class _Stage2(nn.Module):
+    """Construction helpers and U-Net walks shared by the Stage-II archs.  The helpers register ``first_conv<sfx>``, ``encoders<sfx>``,
+    ``down_layers<sfx>``, ``decoders<sfx>`` and ``proj<sfx>`` on the arch itself, so the state-dict keys are the reference's; each arch
+    calls them in its own registration order (which fixes parameters() order and the RNG draws of the initialisation)."""
+
+    def _setup(self, stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, decomp_model, wavelet_out):
+        """Loads the frozen decomposition; returns level(dim, i), the VSS stack of U-Net level i (i = -1: the bottleneck)."""
+        self.stage, self.num_levels = stage, len(num_blocks)
+        if isinstance(d_state, int):
+            d_state = [d_state] * self.num_levels
+        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=wavelet_out)
+        return lambda dim, i: make_vss_level(dim, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type)
+
+    def _add_encoder(self, sfx, cin, n_feat, level):
+        """first_conv<sfx> and encoders<sfx>; returns the bottleneck width."""
+        setattr(self, "first_conv" + sfx, _first_conv(cin, n_feat))
+        enc, cur = nn.ModuleList(), n_feat
+        for i in range(self.num_levels - 1):
+            enc.append(level(cur, i))
+            cur *= 2
+        setattr(self, "encoders" + sfx, enc)
+        return cur
+
+    def _add_down_layers(self, sfx, n_feat):
+        setattr(self, "down_layers" + sfx, nn.ModuleList([conv_down(n_feat * (2 ** i)) for i in range(self.num_levels - 1)]))
+
+    def _add_decoder(self, sfx, cur, n_feat, out_ch, level):
+        """decoders<sfx> from the bottleneck width ``cur`` back to n_feat, then proj<sfx> (n_feat -> out_ch)."""
+        decs = nn.ModuleList()
+        for i in range(self.num_levels - 2, -1, -1):
+            decs.append(_Dec({"up": ConvT2x2(cur, cur // 2), "fuse": PwConv2d(cur, cur // 2, bias=False), "block": level(cur // 2, i)}))
+            cur //= 2
+        setattr(self, "decoders" + sfx, decs)
+        pj = Conv2dK(n_feat, out_ch, 3, 1, 1, bias=True)
+        nn.init.zeros_(pj.bias)
+        setattr(self, "proj" + sfx, pj)
+
+    def _encode(self, sfx, x, **first_kw):
+        """first_conv, then (encoder, fork, down) per level; returns the deepest features and the skips."""
+        f = getattr(self, "first_conv" + sfx)(x, **first_kw)
+        skips = []
+        for enc, down in zip(getattr(self, "encoders" + sfx), getattr(self, "down_layers" + sfx)):
+            # two consumers (down layer, decoder skip): their gradients meet in bem_add_f32; a no-op without a graph
+            f, s = ag.fork(enc(f))
+            skips.append(s)
+            f = down(f)
+        return f, skips
+
+    def _decode(self, sfx, f, skips):
+        """(up, fuse with the skip, block) per level, then proj."""
+        for dec, skip in zip(getattr(self, "decoders" + sfx), reversed(skips)):
+            f = dec["block"](dec["fuse"](dec["up"](f), x2=skip, in_mode=2))
+        return getattr(self, "proj" + sfx)(f)
+
+
+# ------------------------------------------------------------------------------------------------
+# Stage-II: two U-Nets (Q1, Q2) around one shared bottleneck -- DecompDualBranchDDWavelet and the sibling archs
+# DecompDualBranch2DD / DecompDualBranch2 (SURVEY section 8f row 1: same blocks and kernels, different wiring of the condition)
+# ------------------------------------------------------------------------------------------------
+class _DualBranch(_Stage2):
+    """Subclasses set the decomposition's output domain and the widths of the U-Net input and of proj."""
+    _wavelet, _in_ch, _out_ch = False, 4, 4
+
     def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1,
                  mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False,
                  last_act=None, decomp_model="model1"):
         super().__init__()
-        self.stage = stage
-        self.num_levels = len(num_blocks)
-        if isinstance(d_state, int):
-            d_state = [d_state] * self.num_levels
-        if decomp_model not in ("model1", "model2", "model3", "model4"):
-            raise ValueError(f"Unknown decomp_model: {decomp_model}")
-        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=True)
-        for br in ("Q1", "Q2"):
-            fc = Conv2dK(32, n_feat, 3, 1, 1, bias=True)
-            nn.init.kaiming_normal_(fc.weight, mode="fan_out", nonlinearity="linear")
-            nn.init.zeros_(fc.bias)
-            setattr(self, f"first_conv_{br}", fc)
-            enc = nn.ModuleList()
-            cur = n_feat
-            for i in range(self.num_levels - 1):
-                enc.append(make_vss_level(cur, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                cur *= 2
-            setattr(self, f"encoders_{br}", enc)
-            setattr(self, f"down_layers_{br}", nn.ModuleList([conv_down(n_feat * (2 ** i)) for i in range(self.num_levels - 1)]))
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, decomp_model, self._wavelet)
+        for br in ("_Q1", "_Q2"):
+            cur = self._add_encoder(br, self._in_ch, n_feat, level)
+            self._add_down_layers(br, n_feat)
         self.bottleneck_fuse = PwConv2d(cur * 2, cur, bias=False)
-        self.bottleneck_block = make_vss_level(cur, num_blocks[-1], d_state[-1], ssm_ratio, mlp_ratio, mlp_type)
+        self.bottleneck_block = level(cur, -1)
         self.bottleneck_to_Q1 = PwConv2d(cur, cur, bias=False)
         self.bottleneck_to_Q2 = PwConv2d(cur, cur, bias=False)
-        for br in ("Q1", "Q2"):
-            d, decs = cur, nn.ModuleList()
-            for i in range(self.num_levels - 2, -1, -1):
-                decs.append(_decoder(d, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                d //= 2
-            setattr(self, f"decoders_{br}", decs)
-            pj = Conv2dK(n_feat, 16, 3, 1, 1, bias=True)
-            nn.init.zeros_(pj.bias)
-            setattr(self, f"proj_{br}", pj)
+        for br in ("_Q1", "_Q2"):
+            self._add_decoder(br, cur, n_feat, self._out_ch, level)
         self.last_act = _check_last_act(last_act)
         self.apply(_init_weights)
         # the registration order above differs from the reference only inside this constructor;
         # state-dict KEYS and shapes are identical (tests/test_host_contract.py)
+
+    def _dual_unet(self, qs):
+        """qs: the inputs of U-Net Q1 and Q2, taken one at a time as each branch starts.  Returns the two proj outputs."""
+        feats, skips = [], []
+        for br, q in zip(("_Q1", "_Q2"), qs):
+            f, sk = self._encode(br, q)
+            feats.append(f)
+            skips.append(sk)
+        fused = self.bottleneck_block(self.bottleneck_fuse(feats[0], x2=feats[1], in_mode=2))
+        return [self._decode(br, getattr(self, "bottleneck_to" + br)(fz), sk) for br, fz, sk in zip(("_Q1", "_Q2"), ag.fork(fused), skips)]
+
+    def _full_res(self, qs):
+        """Full-resolution tail: q1, q2 (B,Cin,H,W) -> Hamilton(Q1_out, Q2_out)[1:] (B,3,H,W).  Kernels only in inference, bem.autograd
+        nodes in train() mode with autograd on (q1, q2 come from the frozen decomposition and carry no graph)."""
+        train = grad_mode(self)
+        with torch.enable_grad() if train else torch.no_grad():
+            return _hamilton(*self._dual_unet(qs), train)
+
+
+class DecompDualBranchDDWavelet(_DualBranch):
+    _wavelet, _in_ch, _out_ch = True, 32, 16
 
     # -- pieces reused by the Monte-Carlo pipeline (decomp(img) hoisted out of the sample loop) --
     def decompose(self, x, c0):
@@ -224,35 +298,19 @@ class DecompDualBranchDDWavelet(nn.Module):
         spi = 1 if img_index is None else int(img_index)
         if d_img.shape[0] * spi != B:
             raise ValueError("forward_decomposed: image / sample batch mismatch")
-        feats, skips = {}, {}
-        for bi, br in enumerate(("Q1", "Q2")):
+
+        def branch_input(bi):
             q = torch.empty(B, 32, h, w, device=d_cond.device, dtype=d_cond.dtype)
             if spi == 1:
                 ops.copy_channels(d_img, q, 0, src_c0=16 * bi, C=16)
             else:
                 ops.copy_channels_rep(d_img, q, 0, spi, src_c0=16 * bi, C=16)
             ops.copy_channels(d_cond, q, 16, src_c0=16 * bi, C=16)
-            f = getattr(self, f"first_conv_{br}")(q)
-            sk = []
-            for i in range(self.num_levels - 1):
-                f = getattr(self, f"encoders_{br}")[i](f)
-                f, s_ = ag.fork(f)          # two consumers (down layer, decoder skip): their gradients meet in bem_add_f32
-                sk.append(s_)
-                f = getattr(self, f"down_layers_{br}")[i](f)
-            feats[br], skips[br] = f, sk
-        fused = self.bottleneck_fuse(feats["Q1"], x2=feats["Q2"], in_mode=2)
-        fused = self.bottleneck_block(fused)
-        outs = []
-        for br, fz in zip(("Q1", "Q2"), ag.fork(fused)):
-            f = getattr(self, f"bottleneck_to_{br}")(fz)
-            for j, dec in enumerate(getattr(self, f"decoders_{br}")):
-                f = dec["up"](f)
-                f = dec["fuse"](f, x2=skips[br][self.num_levels - 2 - j], in_mode=2)
-                f = dec["block"](f)
-            outs.append(getattr(self, f"proj_{br}")(f))
-        if outs[0].requires_grad or outs[1].requires_grad:
-            return ag.IwtHamiltonFn.apply(outs[0], outs[1])
-        return ops.iwt_hamilton(outs[0], outs[1])
+            return q
+        o1, o2 = self._dual_unet(branch_input(bi) for bi in range(2))
+        if o1.requires_grad or o2.requires_grad:
+            return ag.IwtHamiltonFn.apply(o1, o2)
+        return ops.iwt_hamilton(o1, o2)
 
     def forward(self, x, mask=None):
         """Inference: kernels only, nothing recorded.  ``train()`` mode with autograd enabled (image_enhancer_model.py:165-216):
@@ -269,89 +327,9 @@ class DecompDualBranchDDWavelet(nn.Module):
         return [x, out]
 
 
-# ------------------------------------------------------------------------------------------------
-# Sibling Stage-II archs: same blocks and kernels, different wiring of the condition
-# ------------------------------------------------------------------------------------------------
-class _DualBranchFullRes(nn.Module):
-    """Shared body of DecompDualBranch2DD / DecompDualBranch2: two full-resolution U-Nets over quaternion maps,
-    shared bottleneck, Hamilton product of the two 4-channel outputs (no wavelet stage)."""
-
-    def _build(self, in_branch, n_feat, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, last_act, decomp_model):
-        self.num_levels = len(num_blocks)
-        if isinstance(d_state, int):
-            d_state = [d_state] * self.num_levels
-        if decomp_model not in ("model1", "model2", "model3", "model4"):
-            raise ValueError(f"Unknown decomp_model: {decomp_model}")
-        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=False)
-        for br in ("Q1", "Q2"):
-            fc = Conv2dK(in_branch, n_feat, 3, 1, 1, bias=True)
-            nn.init.kaiming_normal_(fc.weight, mode="fan_out", nonlinearity="linear")
-            nn.init.zeros_(fc.bias)
-            setattr(self, f"first_conv_{br}", fc)
-            enc, cur = nn.ModuleList(), n_feat
-            for i in range(self.num_levels - 1):
-                enc.append(make_vss_level(cur, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                cur *= 2
-            setattr(self, f"encoders_{br}", enc)
-            setattr(self, f"down_layers_{br}", nn.ModuleList([conv_down(n_feat * (2 ** i)) for i in range(self.num_levels - 1)]))
-        self.bottleneck_fuse = PwConv2d(cur * 2, cur, bias=False)
-        self.bottleneck_block = make_vss_level(cur, num_blocks[-1], d_state[-1], ssm_ratio, mlp_ratio, mlp_type)
-        self.bottleneck_to_Q1 = PwConv2d(cur, cur, bias=False)
-        self.bottleneck_to_Q2 = PwConv2d(cur, cur, bias=False)
-        for br in ("Q1", "Q2"):
-            d, decs = cur, nn.ModuleList()
-            for i in range(self.num_levels - 2, -1, -1):
-                decs.append(_decoder(d, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                d //= 2
-            setattr(self, f"decoders_{br}", decs)
-            pj = Conv2dK(n_feat, 4, 3, 1, 1, bias=True)
-            nn.init.zeros_(pj.bias)
-            setattr(self, f"proj_{br}", pj)
-        self.last_act = _check_last_act(last_act)
-        self.apply(_init_weights)
-
-    def _dual_unet(self, q1, q2):
-        """q1, q2 (B,Cin,H,W) -> Hamilton(Q1_out, Q2_out)[1:]  (B,3,H,W): kernels only in inference, bem.autograd nodes in train() mode with
-        autograd on (q1, q2 come from the frozen decomposition and carry no graph)."""
-        train = grad_mode(self)
-        with torch.enable_grad() if train else torch.no_grad():
-            feats, skips = {}, {}
-            for br, q in (("Q1", q1), ("Q2", q2)):
-                f = getattr(self, f"first_conv_{br}")(q)
-                sk = []
-                for i in range(self.num_levels - 1):
-                    f = getattr(self, f"encoders_{br}")[i](f)
-                    f, s1 = ag.fork(f)
-                    sk.append(s1)
-                    f = getattr(self, f"down_layers_{br}")[i](f)
-                feats[br], skips[br] = f, sk
-            fused = self.bottleneck_block(self.bottleneck_fuse(feats["Q1"], x2=feats["Q2"], in_mode=2))
-            outs = []
-            for br, fz in zip(("Q1", "Q2"), ag.fork(fused)):
-                f = getattr(self, f"bottleneck_to_{br}")(fz)
-                for j, dec in enumerate(getattr(self, f"decoders_{br}")):
-                    f = dec["up"](f)
-                    f = dec["fuse"](f, x2=skips[br][self.num_levels - 2 - j], in_mode=2)
-                    f = dec["block"](f)
-                outs.append(getattr(self, f"proj_{br}")(f))
-            if train:
-                return ag.HamiltonFn.apply(outs[0], outs[1])
-            B, _, H, W = q1.shape
-            out8 = torch.empty(B, 8, H, W, device=q1.device, dtype=q1.dtype)
-            ops.copy_channels(outs[0], out8, 0)
-            ops.copy_channels(outs[1], out8, 4)
-            return ops.hamilton(out8)
-
-
-class DecompDualBranch2DD(_DualBranchFullRes):
+class DecompDualBranch2DD(_DualBranch):
     """basicsr/archs/DecompDualBranchDD_arch.py:53-302: Q = cat(Q_img, Q_cond) (8 channels per branch)."""
-
-    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1,
-                 mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False,
-                 last_act=None, decomp_model="model1"):
-        super().__init__()
-        self.stage = stage
-        self._build(8, n_feat, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, last_act, decomp_model)
+    _in_ch = 8
 
     def forward(self, x, mask=None):
         _need_cuda(x)
@@ -365,19 +343,12 @@ class DecompDualBranch2DD(_DualBranchFullRes):
                 ops.copy_channels(qi, q, 0, src_c0=4 * bi, C=4)
                 ops.copy_channels(qc, q, 4, src_c0=4 * bi, C=4)
                 qs.append(q)
-        return [x, self._dual_unet(qs[0], qs[1])]
+        return [x, self._full_res(qs)]
 
 
-class DecompDualBranch2(_DualBranchFullRes):
+class DecompDualBranch2(_DualBranch):
     """basicsr/archs/DecompDualBranch_arch.py:51-298: Q = Q_img + [cond, 0] (4 channels per branch); returns
     [x[:, 0:3], out] like the reference."""
-
-    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1,
-                 mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False,
-                 last_act=None, decomp_model="model1"):
-        super().__init__()
-        self.stage = stage
-        self._build(4, n_feat, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, last_act, decomp_model)
 
     def forward(self, x, mask=None):
         _need_cuda(x)
@@ -391,7 +362,7 @@ class DecompDualBranch2(_DualBranchFullRes):
                 ops.copy_channels(qi, q, 0, src_c0=4 * bi, C=4)
                 ops.add_channels(x, q, 0, src_c0=3, C=3)               # + [cond, 0]
                 qs.append(q)
-        return [x[:, 0:3], self._dual_unet(qs[0], qs[1])]
+        return [x[:, 0:3], self._full_res(qs)]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -457,7 +428,7 @@ class SpatialAttention(nn.Module):
         return ops.spatial_attention(x, self.conv.weight.detach(), chan_scale)
 
 
-class DecompDualBranch(nn.Module):
+class DecompDualBranch(_Stage2):
     """DecompModel_arch.py:101-366: the image's two quaternion maps (4 channels each; the condition half of the 6-channel input is not
     read, :294) through two U-Nets with their own bottlenecks.  State-dict keys follow the reference: branch 1 without suffix, branch 2
     with the suffix ``2``."""
@@ -466,33 +437,12 @@ class DecompDualBranch(nn.Module):
                  mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False,
                  last_act=None, decomp_model="model1"):
         super().__init__()
-        self.stage = stage
-        self.num_levels = len(num_blocks)
-        if isinstance(d_state, int):
-            d_state = [d_state] * self.num_levels
-        if decomp_model not in ("model1", "model2", "model3", "model4"):
-            raise ValueError(f"Unknown decomp_model: {decomp_model}")
-        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=False)
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, decomp_model, False)
         for s_ in ("", "2"):
-            fc = Conv2dK(4, n_feat, 3, 1, 1, bias=True)
-            nn.init.kaiming_normal_(fc.weight, mode="fan_out", nonlinearity="linear")
-            nn.init.zeros_(fc.bias)
-            setattr(self, "first_conv" + s_, fc)
-            enc, cur = nn.ModuleList(), n_feat
-            for i in range(self.num_levels - 1):
-                enc.append(make_vss_level(cur, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                cur *= 2
-            setattr(self, "encoders" + s_, enc)
-            setattr(self, "bottleneck" + s_, make_vss_level(cur, num_blocks[-1], d_state[-1], ssm_ratio, mlp_ratio, mlp_type))
-            d, decs = cur, nn.ModuleList()
-            for i in range(self.num_levels - 2, -1, -1):
-                decs.append(_decoder(d, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-                d //= 2
-            setattr(self, "decoders" + s_, decs)
-            pj = Conv2dK(n_feat, 4, 3, 1, 1, bias=True)
-            nn.init.zeros_(pj.bias)
-            setattr(self, "proj" + s_, pj)
-            setattr(self, "down_layers" + s_, nn.ModuleList([conv_down(n_feat * (2 ** i)) for i in range(self.num_levels - 1)]))
+            cur = self._add_encoder(s_, 4, n_feat, level)
+            setattr(self, "bottleneck" + s_, level(cur, -1))
+            self._add_decoder(s_, cur, n_feat, 4, level)
+            self._add_down_layers(s_, n_feat)
         self.last_act = _check_last_act(last_act)
         self.cross_fusion_12, self.cross_fusion_21 = CrossFusionBlock(cur), CrossFusionBlock(cur)
         self.bottleneck_se, self.bottleneck_se2 = SEBlock(cur), SEBlock(cur)
@@ -506,76 +456,39 @@ class DecompDualBranch(nn.Module):
         train = grad_mode(self)
         with torch.no_grad():
             x = x.contiguous()
-            B, _, H, W = x.shape
             qi = self.decomp(x, 0)                                      # (B,8,H,W) = [Q1 | Q2] of the image channels
         with torch.enable_grad() if train else torch.no_grad():
-            feats, skips = [], []
-            for bi, s_ in enumerate(("", "2")):
-                f = getattr(self, "first_conv" + s_)(qi, cin_slice=(4 * bi, 4))
-                sk = []
-                for i in range(self.num_levels - 1):
-                    f = getattr(self, "encoders" + s_)[i](f)
-                    f, s1 = ag.fork(f)                                  # two consumers: the down layer and the decoder's skip
-                    sk.append(s1)
-                    f = getattr(self, "down_layers" + s_)[i](f)
-                feats.append(f); skips.append(sk)
-            fa, fb = ag.fork(feats[0])                                  # branch 1's deepest features feed both cross-fusions
-            f2 = self.cross_fusion_12(fa, feats[1])                     # branch 2 takes from branch 1 first ...
+            f1, sk1 = self._encode("", qi, cin_slice=(0, 4))
+            f2, sk2 = self._encode("2", qi, cin_slice=(4, 4))
+            fa, fb = ag.fork(f1)                                        # branch 1's deepest features feed both cross-fusions
+            f2 = self.cross_fusion_12(fa, f2)                           # branch 2 takes from branch 1 first ...
             f2a, f2b = ag.fork(f2)
             f1 = self.cross_fusion_21(f2a, fb)                          # ... and branch 1 from the fused branch 2 (:311-312)
             outs = []
-            for bi, (s_, f) in enumerate((("", f1), ("2", f2b))):
+            for s_, f, sk in (("", f1, sk1), ("2", f2b, sk2)):
                 f = getattr(self, "bottleneck" + s_)(f)
                 se, sa = getattr(self, "bottleneck_se" + s_), getattr(self, "spatial_attention" + s_)
                 f = sa(se(f)) if train else sa(f, chan_scale=se.gate(f))
-                for j, dec in enumerate(getattr(self, "decoders" + s_)):
-                    f = dec["up"](f)
-                    f = dec["fuse"](f, x2=skips[bi][self.num_levels - 2 - j], in_mode=2)
-                    f = dec["block"](f)
-                outs.append(getattr(self, "proj" + s_)(f))
-            if train:
-                out = ag.HamiltonFn.apply(outs[0], outs[1])
-            else:
-                out8 = torch.empty(B, 8, H, W, device=x.device, dtype=x.dtype)
-                ops.copy_channels(outs[0], out8, 0)
-                ops.copy_channels(outs[1], out8, 4)
-                out = ops.hamilton(out8)
+                outs.append(self._decode(s_, f, sk))
+            out = _hamilton(outs[0], outs[1], train)
         return [x, out]
 
 
 # ------------------------------------------------------------------------------------------------
 # Stage-II: DecompSingleBranch (BASELINE config 1)
 # ------------------------------------------------------------------------------------------------
-class DecompSingleBranch(nn.Module):
+class DecompSingleBranch(_Stage2):
     def __init__(self, in_channels=6, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1,
                  mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False,
                  last_act=None, decomp_model="model1"):
         super().__init__()
-        self.stage = stage
-        self.num_levels = len(num_blocks)
-        if isinstance(d_state, int):
-            d_state = [d_state] * self.num_levels
-        if decomp_model not in ("model1", "model2", "model3", "model4"):
-            raise ValueError(f"Unknown decomp_model: {decomp_model}")
-        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=False)
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, decomp_model, False)
         self.conditioning_channels = 3
-        self.first_conv = Conv2dK(11, n_feat, 3, 1, 1, bias=True)
-        nn.init.kaiming_normal_(self.first_conv.weight, mode="fan_out", nonlinearity="linear")
-        nn.init.zeros_(self.first_conv.bias)
-        self.encoders = nn.ModuleList()
-        cur = n_feat
-        for i in range(self.num_levels - 1):
-            self.encoders.append(make_vss_level(cur, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-            cur *= 2
-        self.bottleneck = make_vss_level(cur, num_blocks[-1], d_state[-1], ssm_ratio, mlp_ratio, mlp_type)
-        self.decoders = nn.ModuleList()
-        for i in range(self.num_levels - 2, -1, -1):
-            self.decoders.append(_decoder(cur, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type))
-            cur //= 2
-        self.proj = Conv2dK(n_feat, 8, 3, 1, 1, bias=True)
-        nn.init.zeros_(self.proj.bias)
+        cur = self._add_encoder("", 11, n_feat, level)
+        self.bottleneck = level(cur, -1)
+        self._add_decoder("", cur, n_feat, 8, level)
         self.last_act = _check_last_act(last_act)
-        self.down_layers = nn.ModuleList([conv_down(n_feat * (2 ** i)) for i in range(self.num_levels - 1)])
+        self._add_down_layers("", n_feat)
         self.drop_path = nn.Identity()
         self.apply(_init_weights)
 
@@ -593,26 +506,11 @@ class DecompSingleBranch(nn.Module):
     def _run(self, fea):
         """The U-Net + Hamilton product on the assembled input: kernels only in inference, bem.autograd nodes in train() mode with autograd on
         (the frozen decomposition that produced ``fea`` never records)."""
-        if grad_mode(self):
-            with torch.enable_grad():
-                return ag.Hamilton8Fn.apply(self._unet(fea))
-        with torch.no_grad():
-            return ops.hamilton(self._unet(fea))
-
-    def _unet(self, fea):
-        f = self.first_conv(fea)
-        sk = []
-        for i in range(self.num_levels - 1):
-            f = self.encoders[i](f)
-            f, s1 = ag.fork(f)                                       # two consumers (down layer, decoder skip); a no-op without a graph
-            sk.append(s1)
-            f = self.down_layers[i](f)
-        f = self.bottleneck(f)
-        for j, dec in enumerate(self.decoders):
-            f = dec["up"](f)
-            f = dec["fuse"](f, x2=sk[self.num_levels - 2 - j], in_mode=2)
-            f = dec["block"](f)
-        return self.proj(f)
+        train = grad_mode(self)
+        with torch.enable_grad() if train else torch.no_grad():
+            f, sk = self._encode("", fea)
+            out = self._decode("", self.bottleneck(f), sk)
+            return ag.Hamilton8Fn.apply(out) if train else ops.hamilton(out)
 
 
 class DecompSingleBranchDD(DecompSingleBranch):
@@ -625,9 +523,7 @@ class DecompSingleBranchDD(DecompSingleBranch):
         super().__init__(in_channels, out_channels, n_feat, stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type,
                          use_pixelshuffle, drop_path, use_illu, sam, last_act, decomp_model)
         del self.conditioning_channels
-        self.first_conv = Conv2dK(16, n_feat, 3, 1, 1, bias=True)
-        nn.init.kaiming_normal_(self.first_conv.weight, mode="fan_out", nonlinearity="linear")
-        nn.init.zeros_(self.first_conv.bias)
+        self.first_conv = _first_conv(16, n_feat)       # replaces the parent's 11-channel one after its draws, like the reference
 
     def forward(self, x, mask=None):
         _need_cuda(x)
@@ -638,8 +534,6 @@ class DecompSingleBranchDD(DecompSingleBranch):
             ops.copy_channels(self.decomp(x, 0), fea, 0)
             ops.copy_channels(self.decomp(x, 3), fea, 8)
         return [x, self._run(fea)]
-
-
 # ------------------------------------------------------------------------------------------------
 # Stage-I: Network (UNet_arch.py)
 # ------------------------------------------------------------------------------------------------
