@@ -6,6 +6,7 @@ import torch
 
 import os
 
+import stage2_yardstick as Y
 from conftest import PKG, load_golden, qd_state_dict
 from oracle import bem_oracle as O
 
@@ -180,7 +181,8 @@ def test_smoke_entry():
 def test_stage2_config5_geometry_400x600():
     """BASELINE config-5 geometry: a 400x600 image is reflect-padded to 448x640 (L = 71680 at level 0: multi-chunk scan
     with the global read-modify-write path, non-square maps, 28x40 condition).  One (image, sample) pair, seeded weights,
-    deterministic Stage-I: HIP pipeline vs the CPU oracle; PSNR of the candidate must agree within 1e-3 dB."""
+    deterministic Stage-I: HIP pipeline vs the CPU oracle; PSNR of the candidate must agree within 1e-3 dB, the final image within
+    1.5e-2 max / 5e-6 mean (measured on the MI355X: max 4.2e-3, mean 1.2e-6)."""
     from bem.pipeline import BEMPipeline, build_nets, synthetic_pair
     net1, net2 = build_nets(device="cuda")
     sd1 = {k: v.detach().cpu() for k, v in net1.state_dict().items()}
@@ -200,7 +202,8 @@ def test_stage2_config5_geometry_400x600():
     close(out["raw"], ref2, 1e-4, 5e-6, "config-5 geometry Stage II")
     # end to end: the north-star criterion (PSNR of the selected candidate within 1e-3 dB) and a sanity bound on the image
     d = (out["final"][0].permute(1, 2, 0).cpu() - torch.from_numpy(ref["finals"][0])).abs()
-    assert d.mean() < 2e-4, d.mean()
+    print(f"final image: mean|d| {d.mean():.2e} max|d| {d.max():.2e}")
+    assert d.max() < 1.5e-2 and d.mean() < 5e-6, (d.max(), d.mean())
     assert abs(float(out["psnr"][0]) - ref["psnr"][0]) < 1e-3
 
 
@@ -284,45 +287,9 @@ def test_mc_pipeline_with_dualbranch_stage2_vs_oracle():
 
 
 # ----------------------------------------------------------------------------- float64 yardstick --
-def _scan64(u, delta, A, B, C, D=None, delta_bias=None, delta_softplus=True):
-    """selective_scan_ref's recurrence with nothing cast down (test-only: the reference casts to f32)."""
-    import torch.nn.functional as F
-    Bt, K, N, L = B.shape
-    Cd = u.shape[1] // K
-    dt = F.softplus(delta + delta_bias[None, :, None])
-    Bx, Cx = B.repeat_interleave(Cd, dim=1), C.repeat_interleave(Cd, dim=1)
-    dA, dBu = torch.exp(dt.unsqueeze(2) * A[None, :, :, None]), (dt * u).unsqueeze(2) * Bx
-    h = torch.zeros(Bt, u.shape[1], N, dtype=u.dtype)
-    ys = []
-    for t in range(L):
-        h = dA[..., t] * h + dBu[..., t]
-        ys.append((h * Cx[..., t]).sum(-1))
-    return torch.stack(ys, dim=2) + u * D[None, :, None]
-
-
-def _ss2d_core64(sd, pre, x, scan=None):
-    B, Cd, H, W = x.shape
-    xw, dtw = sd[pre + "x_proj_weight"], sd[pre + "dt_projs_weight"]
-    K, _, R = dtw.shape
-    N = sd[pre + "A_logs"].shape[1]
-    xs = O.cross_scan_ref(x)
-    x_dbl = torch.einsum("bkcl,kjc->bkjl", xs, xw)
-    dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
-    dts = torch.einsum("bkrl,kcr->bkcl", dts, dtw)
-    ys = _scan64(xs.reshape(B, K * Cd, H * W), dts.reshape(B, K * Cd, H * W), -torch.exp(sd[pre + "A_logs"]), Bs, Cs, sd[pre + "Ds"],
-                 sd[pre + "dt_projs_bias"].reshape(-1))
-    y = O.cross_merge_ref(ys.reshape(B, K, Cd, H, W)).reshape(B, Cd, H, W)
-    return O.layernorm2d_ref(y, sd[pre + "out_norm.weight"], sd[pre + "out_norm.bias"])
-
-
-def _iwt64(x):
-    B, C4, H, W = x.shape
-    C = C4 // 4
-    ll, hl, lh, hh = (x[:, i * C:(i + 1) * C] / 2 for i in range(4))
-    out = torch.zeros(B, C, 2 * H, 2 * W, dtype=x.dtype)
-    out[:, :, 0::2, 0::2], out[:, :, 1::2, 0::2] = ll - hl - lh + hh, ll - hl + lh - hh
-    out[:, :, 0::2, 1::2], out[:, :, 1::2, 1::2] = ll + hl - lh - hh, ll + hl + lh + hh
-    return out
+# the oracle's algorithm with nothing cast down (tests/stage2_yardstick.py; its scan is checked against the per-step loop in
+# tests/test_stage2_visibility.py)
+_ss2d_core64, _iwt64 = Y.ss2d_core64, Y.iwt64
 
 
 def test_stage2_within_f32_rounding_of_float64():
@@ -436,7 +403,8 @@ def test_archs_build_and_run_with_every_decomp_model(yml, dm):
 def test_full_width_stochastic_mc_vs_oracle():
     """The headline path at FULL WIDTH with stochastic weights: n_feat 40, blocks [2,2,2], shipped QD model4 decomposition, one 64x64 image,
     N = 4 Bayesian samples with injected weight epsilons and condition noise (eval.py:199-297, image_enhancer_model.py:165-216).  Every
-    candidate's PSNR must agree with oracle.eval_mc_ref within 1e-3 dB (the north star's bar), candidates to 5e-4, same selected index."""
+    candidate's PSNR must agree with oracle.eval_mc_ref within 1e-3 dB (the north star's bar), candidates to 3e-4 (measured on the MI355X:
+    max|d| 9.1e-5 over the four), same selected index."""
     from bem.pipeline import BEMPipeline, build_nets, synthetic_pair
     net1, net2 = build_nets(device="cuda")
     sd1 = {k: v.detach().cpu() for k, v in net1.state_dict().items()}
@@ -453,7 +421,8 @@ def test_full_width_stochastic_mc_vs_oracle():
     fin = r["final"].cpu()
     for i in range(N):
         d = float((fin[i].permute(1, 2, 0) - torch.from_numpy(ref["finals"][i])).abs().max())
-        assert d < 5e-4, (i, d)
+        print(f"candidate {i}: max|d| {d:.2e}")
+        assert d < 3e-4, (i, d)
     dps = np.abs(np.asarray(ref["psnr"]) - r["psnr"].cpu().numpy())
     assert dps.max() < 1e-3, dps                                     # dB
     s = sorted(ref["psnr"], reverse=True)
@@ -549,3 +518,95 @@ def test_sample_major_blocks_equal_unsharded_candidates():
                 rows.append(r[key][b * n:(b + 1) * n])
         got = torch.cat(rows)
         close(got, full[key], 1e-5, 1e-6, f"sample-major {key}")
+
+
+# ------------------------------------------------------------- shipped sizes, recurrence-dominated weights, float64 yardstick --
+def _yardstick(out, r32, r64, what):
+    """HIP no further from float64 than 2x the f32 oracle, mean and max (tests/test_stage2_visibility.py: every block moved by
+    1e-3 moves the output by >= 5x this bound)."""
+    (rm, rM), (hm, hM) = Y.errors(r32, r64), Y.errors(out, r64)
+    print(f"{what} vs float64: f32 oracle mean {rm:.3e} max {rM:.3e} | HIP mean {hm:.3e} max {hM:.3e} "
+          f"({hm / rm:.2f}x, {hM / rM:.2f}x) | max|out| {r64.abs().max():.3f}")
+    assert torch.isfinite(out).all()
+    assert hm <= 2 * rm and hM <= 2 * rM, (what, hm, rm, hM, rM)
+
+
+@pytest.mark.parametrize("name,batch", [(n, 1) for n in Y.SIBLINGS] + [("DecompDualBranchDDWavelet", 2)])
+def test_stage2_shipped_size_vs_float64(name, batch):
+    """Each Stage-II arch as its Options/*.yml ships it (n_feat 40, [2,2,2], its decomposition model) at 256x256 -- DDWavelet at
+    config 2's batch of 2 -- with the recurrence-dominated weights of tests/stage2_yardstick.py: level 0 runs the chunked scan with 32
+    carries, the 3x3 tap form at W = 256, the 4x4-s2 im2col kernel at Wo = 128, SE and 7x7 attention on 64x64 bottlenecks."""
+    from bem import ops
+    net = Y.build_arch(name)
+    sd = Y.recurrence_dominated({k: v.detach().clone() for k, v in net.state_dict().items()}, 7)
+    net.load_state_dict(sd, strict=True)
+    ops.bump_weight_epoch()
+    g = torch.Generator().manual_seed(11)
+    x = torch.cat([0.25 * torch.rand(batch, 3, 256, 256, generator=g), torch.rand(batch, 3, 256, 256, generator=g)], 1)
+    out = net.cuda().eval()(x.cuda())[-1].cpu()
+    _yardstick(out, Y.oracle(name, sd, x, O.selective_scan_c), Y.float64_ref(name, sd, x), f"{name} 256x256 batch {batch}")
+
+
+def _config5_nets():
+    """build_nets() with the Stage-II net moved to the recurrence-dominated operating point (before its first forward)."""
+    from bem import ops
+    from bem.pipeline import build_nets
+    net1, net2 = build_nets(device="cuda")
+    sd2 = Y.recurrence_dominated({k: v.detach().cpu().clone() for k, v in net2.state_dict().items()}, 7)
+    net2.load_state_dict(sd2, strict=True)
+    ops.bump_weight_epoch()
+    return net1, net2, {k: v.detach().cpu() for k, v in net1.state_dict().items()}, sd2
+
+
+def _stage2_input(lq, cond):
+    """The Stage-II input of eval.py for a 400x600 image: reflect-padded to 448x640, condition bilinear x16."""
+    pad = torch.from_numpy(np.ascontiguousarray(O.pad_reflect_ref(lq[0].permute(1, 2, 0).numpy(), 64))).permute(2, 0, 1)[None]
+    return torch.cat([pad, torch.nn.functional.interpolate(cond, scale_factor=16, mode="bilinear", align_corners=False)], 1)
+
+
+def test_stage2_config5_vs_float64():
+    """Config 5, Stage II in isolation at 448x640 (level 0: L = 71680, the chunked scan with 35 carries; levels 1 / 2: 112x160 / 56x80 on
+    the generic scan) with the recurrence-dominated weights, on the condition the HIP Stage I produced for a 400x600 image."""
+    from bem.pipeline import BEMPipeline, synthetic_pair
+    net1, net2, _, sd2 = _config5_nets()
+    lq, gt = synthetic_pair((1, 3, 400, 600), seed=5)
+    noise = torch.randn(1, 3, 28, 40, generator=torch.Generator().manual_seed(9))
+    r = BEMPipeline(net1, net2).enhance(lq.cuda(), gt.cuda(), 1, gt_mean=True, deterministic=True, noise=noise.cuda())
+    x = _stage2_input(lq, r["conds"].cpu())
+    out = net2(x.cuda())[-1].cpu()
+    name = "DecompDualBranchDDWavelet"
+    _yardstick(out, Y.oracle(name, sd2, x, O.selective_scan_c), Y.float64_ref(name, sd2, x), "config-5 Stage II 448x640")
+
+
+def test_config5_monte_carlo_vs_oracle():
+    """Config 5's Monte-Carlo loop: one 400x600 image, N = 4 Bayesian samples with injected weight epsilons and condition noise, Stage II
+    at the recurrence-dominated operating point.  Stage I per sample (per-sample weight sets on 28x40 .. 7x10 planes) against the oracle's
+    conditions (measured max|d| 5.7e-5); Stage II on the four HIP conditions in one batch against the float64 yardstick on each; every
+    candidate's PSNR within 1e-3 dB; the same selected index.  The noisy conditions make Stage II ill-conditioned here: where a pixel's
+    channel maximum comes close to 0, the decomposition's q1 = RGB / (max + 1e-7) is large, and the f32 oracle itself is up to 1e-2 from
+    float64 at outputs of ~1e4 -- hence the yardstick bound, not a fixed one."""
+    from bem.pipeline import BEMPipeline, synthetic_pair
+    net1, net2, sd1, sd2 = _config5_nets()
+    lq, gt = synthetic_pair((1, 3, 400, 600), seed=13)
+    N = 4
+    g = torch.Generator().manual_seed(23)
+    eps_cpu = [{(k[:-len("mu_weight")] + "weight" if k.endswith("mu_weight") else k[:-len("mu_bias")] + "bias"): torch.randn(v.shape, generator=g)
+                for k, v in sd1.items() if k.endswith(("mu_weight", "mu_bias"))} for _ in range(N)]
+    noise = torch.randn(N, 3, 28, 40, generator=g)
+    ref = O.eval_mc_ref(sd1, sd2, lq, gt, N, gt_mean=True, eps_list=eps_cpu, noise_list=[noise[i:i + 1] for i in range(N)], scan=O.selective_scan_c)
+    r = BEMPipeline(net1, net2, 16, 0.1).enhance(lq.cuda(), gt.cuda(), N, gt_mean=True, eps={k: torch.stack([e[k] for e in eps_cpu]).cuda() for k in eps_cpu[0]},
+                                                noise=noise.cuda())
+    assert r["conds"].shape == (N, 3, 28, 40) and r["raw"].shape == (N, 3, 448, 640)
+    conds = r["conds"].cpu()
+    xs = [_stage2_input(lq, conds[i:i + 1]) for i in range(N)]
+    out = net2(torch.cat(xs).cuda())[-1].cpu()                       # the N candidates in one batch
+    name = "DecompDualBranchDDWavelet"
+    for i in range(N):
+        close(conds[i:i + 1], ref["conds"][i], 0, 1e-4, f"condition {i}")
+        _yardstick(out[i:i + 1], Y.oracle(name, sd2, xs[i], O.selective_scan_c), Y.float64_ref(name, sd2, xs[i]), f"config-5 MC sample {i}")
+    dps = np.abs(np.asarray(ref["psnr"]) - r["psnr"].cpu().numpy())
+    assert dps.max() < 1e-3, dps                                     # dB
+    s = sorted(ref["psnr"], reverse=True)
+    if s[0] - s[1] > 1e-3:
+        assert int(r["best"][0]) == int(ref["best"])
+    assert float((out[0] - out[1]).abs().max()) > 1e-3                # the samples are different draws

@@ -139,6 +139,59 @@ def test_ss2d_scan_vs_oracle(ops, shape):
     close(y, ref, 2e-4, 2e-5, f"ss2d {shape}")
 
 
+def _ss2d_fused64(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
+    """bem_ss2d_scan restated in float64 (the directions as in tests/test_train_gpu.py::_ss2d_torch, the scan in the blocked closed
+    form of tests/stage2_yardstick.py): per orientation, (state term C*h, D*u) of its two directions summed."""
+    from stage2_yardstick import scan64
+    B, C, L = x0.shape
+    R = dtw.shape[2]
+    out = []
+    for o, (x, xd) in enumerate(((x0, xd0), (x1, xd1))):
+        ch = du = 0
+        for slot, k in enumerate((o, o + 2)):
+            xs, d = (x.flip(-1), xd[:, slot].flip(-1)) if slot else (x, xd[:, slot])
+            dts = torch.einsum("cr,brl->bcl", dtw[k], d[:, :R])
+            c, u = scan64(xs, dts, A[k * C:(k + 1) * C].view(C, 1), d[:, R].reshape(B, 1, 1, L), d[:, R + 1].reshape(B, 1, 1, L),
+                          Ds[k * C:(k + 1) * C], dtb[k])
+            ch, du = ch + (c.flip(-1) if slot else c), du + (u.flip(-1) if slot else u)
+        out.append((ch, du))
+    return out
+
+
+@pytest.mark.parametrize("shape", [(2, 40, 256, 256, 3),      # sibling level 0 at 256^2: chunked form, 32 chunk carries, batch strides
+                                   (1, 40, 224, 320, 3),      # config-5 level 0 (448x640): 35 chunk carries
+                                   (1, 80, 112, 160, 5),      # config-5 level 1: L % 2048 != 0, generic chunked kernel
+                                   (1, 160, 56, 80, 10),      # config-5 level 2
+                                   (1, 80, 128, 128, 5)])     # sibling level 1: chunked form with a runtime dt_rank
+def test_ss2d_scan_long_planes_vs_float64(ops, shape):
+    """bem_ss2d_scan on the long planes the shipped nets reach, at a recurrence-dominated operating point (Ds ~ 0.1 N(0,1), dt from
+    0.05 to ~1, B and C of unit size: the state term C*h is as large as D*u) against the float64 closed form.  y is held to
+    rtol 2e-5 of its largest value and the state term y - D*u on its own to 2e-5 of its largest value, so a carry that is off in one chunk,
+    or a state path that is off by 0.01 %, fails (measured on the MI355X: 1.1e-7 .. 1.8e-7 of either).  Forward only (training crops are
+    128x128)."""
+    B, C, H, W, R = shape
+    L = H * W
+    g = torch.Generator().manual_seed(L + C)
+    x = F.silu(torch.randn(B, C, H, W, generator=g))
+    xd0, xd1 = torch.randn(B, 2, R + 2, L, generator=g), torch.randn(B, 2, R + 2, L, generator=g)
+    dtw = torch.randn(4, C, R, generator=g) * (0.3 / R ** 0.5)
+    dtb = torch.log(torch.expm1(0.05 + 0.95 * torch.rand(4, C, generator=g)))
+    A = -torch.exp(0.5 * torch.randn(4 * C, generator=g))
+    Ds = 0.1 * torch.randn(4 * C, generator=g)
+    xT = x.transpose(2, 3).contiguous()
+    d64 = lambda t: t.double()
+    (c0, u0), (c1, u1) = _ss2d_fused64(d64(x).view(B, C, L), d64(xT).view(B, C, L), d64(xd0), d64(xd1), d64(dtw), d64(dtb), d64(A), d64(Ds))
+    args = [dev(t) for t in (dtw, dtb, A, Ds)]
+    y0, y1 = ops.ss2d_scan(dev(x).view(B, C, L), dev(xT).view(B, C, L), dev(xd0), dev(xd1), *args)
+    for o, h, c, u in ((0, y0, c0, u0), (1, y1, c1, u1)):
+        assert torch.isfinite(h).all()
+        e = (h.cpu().double() - u - c).abs().max().item()
+        ymax, cmax = (c + u).abs().max().item(), c.abs().max().item()
+        print(f"{shape} orientation {o}: max|y| {ymax:.3f} max|C*h| {cmax:.3f} max|D*u| {u.abs().max().item():.3f} | "
+              f"max err {e:.2e} = {e / ymax:.1e} max|y| = {e / cmax:.1e} max|C*h|")
+        assert e <= 2e-5 * ymax and e <= 2e-5 * cmax, (o, e, ymax, cmax)
+
+
 # ----------------------------------------------------------------------------- pointwise GEMM ---
 @pytest.mark.parametrize("cfg", [(2, 40, 40, 16, 12), (1, 40, 320, 8, 8), (2, 160, 40, 5, 7), (1, 32, 20, 3, 3),
                                  (3, 64, 33, 4, 130), (1, 7, 5, 2, 2), (1, 320, 160, 32, 32)])
