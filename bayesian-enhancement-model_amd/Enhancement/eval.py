@@ -4,14 +4,18 @@ line (eval.py:30-60) on the device-resident pipeline (bem.pipeline.BEMPipeline):
 
   python Enhancement/eval.py --opt Options/CG_UNet_LOLv1.yml --cond_opt Options/DecompDualBranch2DDWavelet_4.yml \
       --weights cg.pth --cond_weights stage2.pth --input_dir data/LOLv1/Test/input --target_dir data/LOLv1/Test/target \
-      --dataset LOLv1 --GT_mean --num_samples 16 [--no_ref clip] [--psnr_weight 0.5] [--Monte_Carlo] [--deterministic]
+      --dataset LOLv1 --GT_mean --num_samples 16 [--no_ref clip | --no_ref niqe --niqe_params niqe_pris_params.npz] [--psnr_weight 0.5]
+      [--Monte_Carlo] [--deterministic]
 
 What differs from the reference script, none of it in the results: all N samples of an image go through Stage I and Stage II as one
 batch (``--parallel_num`` is accepted and ignored), conditions never leave the GPU, selection metrics run on the device, and images
 are read / written with PIL (cv2, skimage, natsort, lpips, torchmetrics are not dependencies).  ``--no_ref clip`` uses the scorer
-returned by ``make_clip_scorer`` -- the deterministic stand-in of bem.scorers unless a CLIP-IQA module is importable; ``--no_ref
-niqe | uiqm_uciqe`` and ``--lpips`` need host-side metric packages that are outside this path and raise a clear error.
-Output: ``<result_dir>/<dataset>/<image>.png`` (the selected candidate) and ``result.txt`` with the reference's summary lines."""
+returned by ``make_clip_scorer`` -- the deterministic stand-in of bem.scorers unless a CLIP-IQA module is importable.  ``--no_ref niqe``
+scores every candidate with NIQE on the device (bem.ops.niqe) and keeps the first minimum; it needs ``--niqe_params``, the pristine-model
+file ``niqe_pris_params.npz`` of a BasicSR install (basicsr/metrics/), which is data and not shipped here.  ``--no_ref uiqm_uciqe`` and
+``--lpips`` need host-side metric packages that are outside this path and raise a clear error.
+Output: ``<result_dir>/<dataset>/<image>.png`` (the selected candidate) and ``result.txt`` with the reference's summary lines
+(``Best_NIQE`` after the PSNR / SSIM lines, eval.py:344-347)."""
 import argparse
 import os
 import sys
@@ -41,6 +45,7 @@ def get_parser():
     p.add_argument("--Monte_Carlo", action="store_true", help="also report the average of the random samples")
     p.add_argument("--psnr_weight", default=1.0, type=float, help="Balance between PSNR and SSIM")
     p.add_argument("--no_ref", default="", type=str, choices=["", "clip", "niqe", "uiqm_uciqe"], help="no reference image quality evaluator")
+    p.add_argument("--niqe_params", default="", type=str, help="niqe_pris_params.npz of a BasicSR install (basicsr/metrics/), for --no_ref niqe")
     p.add_argument("--uiqm_weight", default=1.0, type=float, help="Balance between UIQM and UICIQE")
     p.add_argument("--lpips", action="store_true", help="True to compute LPIPS")
     p.add_argument("--deterministic", action="store_true", help="Use deterministic mode")
@@ -73,13 +78,16 @@ def load_params(net, path):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
-    if args.no_ref in ("niqe", "uiqm_uciqe") or args.lpips:
-        raise SystemExit("--no_ref niqe / uiqm_uciqe and --lpips are host-side metric packages outside the HIP path (SURVEY.md section 2 rows 16, 1)")
+    if args.no_ref == "uiqm_uciqe" or args.lpips:
+        raise SystemExit("--no_ref uiqm_uciqe and --lpips are host-side metric packages outside the HIP path (SURVEY.md section 2 rows 16, 1)")
+    if args.no_ref == "niqe" and not args.niqe_params:
+        raise SystemExit("--no_ref niqe needs --niqe_params PATH: the NIQE pristine-model file niqe_pris_params.npz "
+                         "(basicsr/metrics/niqe_pris_params.npz in a BasicSR install)")
     from basicsr.bayesian import set_prediction_type
     from basicsr.models import build_model
     from basicsr.utils.options import parse
     from bem.pipeline import BEMPipeline
-    from bem.scorers import FullReference
+    from bem.scorers import FullReference, Niqe, NiqeParams
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N Enhancement/eval.py ...`: the driver feeds ONE image at a
     # time (eval.py:160-222), so the N Bayesian samples of that image are what gets sharded (sample-major, bem.dist); every rank holds the
     # gathered candidates, rank 0 writes the files
@@ -104,8 +112,13 @@ def main(argv=None):
     result_dir = os.path.join(args.result_dir, args.dataset)
     os.makedirs(result_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.input_dir) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
-    scorer = make_clip_scorer(args.clip_prompts) if args.no_ref == "clip" else (FullReference(args.psnr_weight) if args.target_dir else None)
-    psnr, ssim, mc_psnr, mc_ssim = [], [], [], []
+    if args.no_ref == "clip":
+        scorer = make_clip_scorer(args.clip_prompts)
+    elif args.no_ref == "niqe":
+        scorer = Niqe(NiqeParams.load(args.niqe_params))
+    else:
+        scorer = FullReference(args.psnr_weight) if args.target_dir else None
+    psnr, ssim, mc_psnr, mc_ssim, niqe = [], [], [], [], []
     t0 = time.perf_counter()
     with torch.inference_mode():
         for i, name in enumerate(names):
@@ -116,6 +129,8 @@ def main(argv=None):
             r = pipe.enhance(img, tgt, args.num_samples, gt_mean=args.GT_mean, deterministic=args.deterministic, scorer=scorer,
                              monte_carlo=args.Monte_Carlo, seed=args.seed + i, shard=(rank, world) if world > 1 else None)
             best = r["best_images"]
+            if args.no_ref == "niqe":
+                niqe.append(float(r["scores"][r["best"][0]]))          # the chosen sample's score (eval.py:273-275)
             if tgt is not None:
                 from bem import ops
                 _, p = ops.candidate_finalize(best.contiguous(), tgt.contiguous(), 1, best.shape[2], best.shape[3], False)
@@ -130,7 +145,7 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
-        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, result_dir=result_dir)
+        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, result_dir=result_dir)
     print(f"running time: {time.perf_counter() - t0:.4f} sec")
     with open(os.path.join(result_dir, "result.txt"), "w") as f:
         if args.target_dir:
@@ -141,7 +156,10 @@ def main(argv=None):
                 for label, vals, unit in (("MC_PSNR", mc_psnr, " dB"), ("MC_SSIM", mc_ssim, "")):
                     line = f"{label}: {np.mean(vals):.4f}{unit}"
                     print(line); f.write(line + " \n")
-    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, result_dir=result_dir)
+        if args.no_ref == "niqe":
+            line = f"Best_NIQE: {np.mean(niqe):.4f}"
+            print(line); f.write(line + " \n")
+    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, result_dir=result_dir)
 
 
 if __name__ == "__main__":

@@ -1022,6 +1022,97 @@ def mc_mean(raw, target, samples_per_image, h, w, gt_mean):
     return out
 
 
+# NIQE (basicsr/metrics/niqe.py as Enhancement/eval.py:248-254 calls it).  Derived tables, built on the host once and kept on the device:
+# the AGGD shape grid of estimate_aggd_param (niqe.py:24-26) with its closed-form gamma ratios, and per input length the weights and
+# symmetric-padded source indices of MATLAB's antialiased bicubic x0.5 resize (matlab_functions.py:16-81).
+NIQE_BLOCK = 96
+_niqe_cache = {}
+
+
+def niqe_gamma_table():
+    """(4, 9801) f64: gam = arange(0.2, 10.001, 0.001), r_gam = G(2/a)^2 / (G(1/a) G(3/a)), sqrt(G(1/a) / G(3/a)), G(2/a) / G(1/a)."""
+    import math
+    import numpy as np
+    gam = np.arange(0.2, 10.001, 0.001)
+    rec = np.reciprocal(gam)
+    tab = np.empty((4, gam.size))
+    tab[0] = gam
+    for i, (a, r) in enumerate(zip(gam.tolist(), rec.tolist())):
+        tab[1, i] = math.gamma(r * 2) ** 2 / (math.gamma(r) * math.gamma(r * 3))
+        tab[2, i] = math.sqrt(math.gamma(1 / a) / math.gamma(3 / a))
+        tab[3, i] = math.gamma(2 / a) / math.gamma(1 / a)
+    return tab
+
+
+def niqe_resize_table(n, scale=0.5):
+    """MATLAB imresize (bicubic, antialiased) along one axis of length n, in float32 like the reference: weights (out, K) f32 and the
+    0-based source index of every tap (out, K) int32 with the symmetric padding folded in; all-zero end columns trimmed."""
+    import math
+    import numpy as np
+    f32 = np.float32
+    out = math.ceil(n * scale)
+    width = 4.0 / scale if scale < 1 else 4.0
+    x = np.arange(1, out + 1, dtype=f32)
+    u = x / f32(scale) + f32(0.5 * (1 - 1 / scale))
+    left = np.floor(u - f32(width / 2))
+    taps = math.ceil(width) + 2
+    idx = left[:, None] + np.arange(taps, dtype=f32)[None, :]
+    d = np.abs((u[:, None] - idx) * f32(scale) if scale < 1 else u[:, None] - idx)
+    d2, d3 = d ** 2, d ** 3
+    cub = (f32(1.5) * d3 - f32(2.5) * d2 + f32(1)) * (d <= 1) + (f32(-0.5) * d3 + f32(2.5) * d2 - f32(4) * d + f32(2)) * ((d > 1) & (d <= 2))
+    wt = (f32(scale) * cub if scale < 1 else cub).astype(f32)
+    wt = wt / wt.sum(axis=1, keepdims=True)
+    keep = np.ones(taps, bool)
+    keep[0] = not (wt[:, 0] == 0).any()
+    keep[-1] = not (wt[:, -1] == 0).any()
+    wt, idx = wt[:, keep], idx[:, keep].astype(np.int64) - 1
+    idx = np.where(idx < 0, -idx - 1, idx)
+    idx = np.where(idx >= n, 2 * n - 1 - idx, idx)
+    return np.ascontiguousarray(wt, dtype=f32), np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def _niqe_tables(device, Hc, Wc):
+    key = (str(device), "gamma")
+    if key not in _niqe_cache:
+        _niqe_cache[key] = torch.from_numpy(niqe_gamma_table()).to(device)
+    rs = []
+    for n in (Hc, Wc):
+        k = (str(device), "resize", n)
+        if k not in _niqe_cache:
+            wt, ix = niqe_resize_table(n)
+            _niqe_cache[k] = (torch.from_numpy(wt).to(device), torch.from_numpy(ix).to(device))
+        rs.append(_niqe_cache[k])
+    return _niqe_cache[key], rs[0], rs[1]
+
+
+def niqe(final, params):
+    """NIQE per candidate: final (Bn,3,h,w) f32 in [0,1] (RGB, clipped, GT-mean rescaled: BEMPipeline's ``final``), params a
+    bem.scorers.NiqeParams (mu (36,), cov (36,36), window (7,7), f64 on the device) -> (Bn) f64 on the device, lower is better.
+    A candidate with fewer than 2 NaN-free block rows (a flat image) scores NaN."""
+    _chk(final, "final")
+    _chk(params.mu, "mu_pris", torch.float64); _chk(params.cov, "cov_pris", torch.float64); _chk(params.window, "window", torch.float64)
+    if final.dim() != 4 or final.shape[1] != 3:
+        raise ValueError("niqe: final must be (Bn,3,h,w)")
+    Bn, _, h, w = final.shape
+    if h < NIQE_BLOCK or w < NIQE_BLOCK:
+        raise ValueError(f"niqe: images must be at least {NIQE_BLOCK} x {NIQE_BLOCK}, got {h} x {w}")
+    if params.mu.numel() != 36 or tuple(params.cov.shape) != (36, 36) or tuple(params.window.shape) != (7, 7):
+        raise ValueError("niqe: pristine parameters must be mu (36), cov (36,36), window (7,7)")
+    dev = final.device
+    tab, (wh, ih), (ww, iw) = _niqe_tables(dev, h // NIQE_BLOCK * NIQE_BLOCK, w // NIQE_BLOCK * NIQE_BLOCK)
+    out = torch.empty(Bn, device=dev, dtype=torch.float64)
+    if Bn == 0:
+        return out
+    nbytes = int(lib().bem_niqe_ws_bytes(Bn, h, w))
+    key = (str(dev), "ws", torch.cuda.current_stream(dev).cuda_stream)
+    ws = _niqe_cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _niqe_cache[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(lib().bem_niqe_f32(_p(final), _p(params.mu), _p(params.cov), _p(params.window), _p(tab), tab.shape[1], _p(wh), _p(ih), wh.shape[1],
+                             _p(ww), _p(iw), ww.shape[1], _p(out), _p(ws), ws.numel(), Bn, h, w, _stream()), "niqe")
+    return out
+
+
 # --------------------------------------------------------------------------- training step ----
 # Backward kernels + optimizer (SURVEY.md section 8a row A10).  Parameter-gradient outputs (dw, dbias, dgamma, ...) are
 # ACCUMULATED INTO: they are views of the parameters' .grad buffers.

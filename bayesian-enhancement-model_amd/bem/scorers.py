@@ -11,6 +11,8 @@ A scorer maps the finished candidates of a batch -- ``final`` (B*N,3,h,w) in [0,
                                fetched here.  It follows eval.py:229-243's post-processing (prompt scores
                                'brightness' x 0.7, 'noisiness' x 1, 'quality', averaged) on closed-form per-image statistics;
                                its VALUES are parity-unpinned, the ordering logic applied to them is the reference's.
+  Niqe(params)                 NIQE (basicsr/metrics/niqe.py, eval.py:253), rule ``index(min)``; ops.niqe on the device with the
+                               pristine-model statistics of a NiqeParams (niqe_pris_params.npz from a BasicSR install).
 All scores stay on the device; ``select`` runs bem_select_scores_f32 (first index on ties, float64 comparisons)."""
 from __future__ import annotations
 
@@ -83,3 +85,31 @@ class ClipStandIn(NoReference):
         if unknown:
             raise ValueError(f"ClipStandIn: unknown prompts {unknown}")
         return torch.stack([vals[p] for p in self.prompts]).mean(dim=0).reshape(Bn)
+
+
+class NiqeParams:
+    """NIQE's pristine multivariate-Gaussian model and smoothing window (basicsr/metrics/niqe_pris_params.npz), f64 on the device."""
+
+    def __init__(self, mu, cov, window, device="cuda"):
+        t = lambda a: torch.as_tensor(a, dtype=torch.float64).to(device).contiguous()
+        self.mu, self.cov, self.window = t(mu).reshape(-1), t(cov), t(window)
+        if self.mu.numel() != 36 or tuple(self.cov.shape) != (36, 36) or tuple(self.window.shape) != (7, 7):
+            raise ValueError("NiqeParams: expected mu_pris_param (36), cov_pris_param (36,36), gaussian_window (7,7)")
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        import numpy as np
+        with np.load(path) as z:
+            missing = [k for k in ("mu_pris_param", "cov_pris_param", "gaussian_window") if k not in z]
+            if missing:
+                raise ValueError(f"{path}: missing {missing} (expected BasicSR's niqe_pris_params.npz)")
+            return cls(z["mu_pris_param"], z["cov_pris_param"], z["gaussian_window"], device)
+
+
+class Niqe(NoReference):
+    """eval.py:253,272-274: NIQE of every candidate, the first minimum wins (bem_select_scores_f32 rule 2).  The selection compares the
+    scores as float32, like every scorer here; ``ops.niqe`` gives the float64 values."""
+
+    def __init__(self, params: NiqeParams):
+        self.params = params
+        super().__init__(lambda final: ops.niqe(final.contiguous(), params), "min")

@@ -337,6 +337,23 @@ int bem_ssim_f32(const float* pred, const float* target, float* ssim, double* ws
 int bem_select_scores_f32(const float* cand, const float* s1, const float* s2, float weight, int rule, int* best, float* best_s1,
                           float* best_s2, float* best_img, int B, int N, int64_t chw, void* stream);
 
+/* NIQE of Enhancement/eval.py:248-254 (calculate_niqe(pred * 255, crop_border=0), basicsr/metrics/niqe.py) per candidate, the
+ * no-reference score that eval.py:272-274 minimises.  final (Bn,3,h,w) f32 in [0,1], RGB as BEMPipeline.candidates returns it; h, w >= 96
+ * (the reference silently yields NaN below one 96 x 96 block).  Steps, with the reference's dtypes:
+ *   Y of metric_util.py:32-45 / color_util.py:38-70 on the stored order (its BGR weights: 24.966 multiplies R), rounded half to even,
+ *   cropped to floor(h/96)*96 x floor(w/96)*96 (top-left); MSCN with the 7x7 `window` (scipy.ndimage.convolve, 'nearest', f64 sums,
+ *   f32 result); per 96 x 96 block the AGGD fits of compute_feature (niqe.py:13-62); imresize(img/255, 0.5, antialiasing=True) * 255
+ *   (matlab_functions.py:16-175, two passes); MSCN and 48 x 48 block fits again; mu_d = nanmean, cov_d = np.cov over NaN-free rows;
+ *   score = sqrt(d^T ((cov_pris + cov_d)/2)^-1 d), d = mu_pris - mu_d (niqe.py:65-143), by a Cholesky solve in f64.
+ * mu_pris (36), cov_pris (36x36), window (7x7): niqe_pris_params.npz, f64 on the device.  gam_tab (4 x ntab f64): gam = arange(0.2,
+ * 10.001, 0.001), r_gam = G(2/a)^2 / (G(1/a) G(3/a)), sqrt(G(1/a) / G(3/a)), G(2/a) / G(1/a).  rs_wh / rs_ih (h'/2 x kh): resize weights
+ * and symmetric-padded source rows of the H pass, rs_ww / rs_iw (w'/2 x kw) of the W pass (h', w' = cropped size).  scores (Bn) f64 out;
+ * a candidate with fewer than 2 NaN-free block rows scores NaN (the reference raises there).  ws: bem_niqe_ws_bytes(Bn, h, w) bytes. */
+int bem_niqe_f32(const float* final, const double* mu_pris, const double* cov_pris, const double* window, const double* gam_tab, int ntab,
+                 const float* rs_wh, const int* rs_ih, int kh, const float* rs_ww, const int* rs_iw, int kw, double* scores, void* ws,
+                 int64_t ws_bytes, int Bn, int h, int w, void* stream);
+int64_t bem_niqe_ws_bytes(int Bn, int h, int w);   /* 0 for h or w < 96 */
+
 /* Monte-Carlo mean of eval.py:224-225,308-314: out (B,3,h,w) = clamp(mean_n clamp(pred[b*N+n][:, :h, :w], 0, 1), 0, 1), with gt_mean scaled
  * by mean(gray(target)) / mean(gray(out)) (cv2 BGR2GRAY weights on the stored channel order) and clipped.  pred (B*N,3,Hp,Wp);
  * ws: 2 B doubles (zeroed by the call) when gt_mean. */
