@@ -278,10 +278,16 @@ class VSSBlockFn(Function):
         cw, cb = op.conv2d.dw_weights(B)
         xc = ops.dwconv3x3(t, cw, cb, mode=1)
         wall, dtw, dtb, A, Ds = op._scan_params()
-        xd = ops.pw_gemm(xc, wall, 4 * (R + 2))
-        xd1 = ops.transpose_plane_slice(xd, 2 * (R + 2), 2 * (R + 2))
+        N = op.d_state
+        M = R + 2 * N                                    # x_dbl rows per direction
+        xd = ops.pw_gemm(xc, wall, 4 * M)
+        xd1 = ops.transpose_plane_slice(xd, 2 * M, 2 * M)
         xcT = None
-        if ops.ss2d_scan_rm_supported(H, W, R):
+        if N > 1:
+            xcT = ops.transpose_planes(xc)
+            y0, y1T = ops.ss2d_scan_n(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L), dtw, dtb, A, Ds)
+            y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1T.view(B, Ci, W, H))
+        elif ops.ss2d_scan_rm_supported(H, W, R):
             y0, y1 = ops.ss2d_scan_rm(xc, xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L), dtw, dtb, A, Ds)
         else:
             xcT = ops.transpose_planes(xc)
@@ -332,17 +338,19 @@ class VSSBlockFn(Function):
         ops.pw_wgrad_(dx2, nys, grad_of(oww), dbias=None if owb is None else grad_of(owb))
         del nys
         wall, dtw, dtb, A, Ds = op._scan_params()
+        M = R + 2 * op.d_state                           # x_dbl rows per direction
         dysT = ops.transpose_planes(dys)
         xcT = ops.transpose_planes(xc)
-        dx0, dx1T, dxd0, dxd1 = ops.ss2d_scan_bwd(
-            xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L), dys.view(B, Ci, L), dysT.view(B, Ci, L),
+        scan_bwd = ops.ss2d_scan_n_bwd if op.d_state > 1 else ops.ss2d_scan_bwd
+        dx0, dx1T, dxd0, dxd1 = scan_bwd(
+            xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L), dys.view(B, Ci, L), dysT.view(B, Ci, L),
             dtw, dtb, A, Ds, grad_of(op.A_logs), grad_of(op.Ds), grad_of(op.dt_projs_weight), grad_of(op.dt_projs_bias))
         del dysT, xcT, dys
         # x_dbl gradient back in the stacked row order of the forward GEMM: [dir 0 | dir 2 | dir 1 | dir 3], row-major pixels
-        dxd = torch.empty(B, 4 * (R + 2), H, W, device=x.device, dtype=x.dtype)
-        ops.copy_channels(dxd0.view(B, 2 * (R + 2), H, W), dxd, 0)
-        _transpose_into(dxd1.view(B, 2 * (R + 2), W, H), dxd, 2 * (R + 2))
-        ops.pw_wgrad_(dxd, xc, grad_of(op.x_proj_weight), blk_rows=R + 2, perm=(0, 2, 1, 3))
+        dxd = torch.empty(B, 4 * M, H, W, device=x.device, dtype=x.dtype)
+        ops.copy_channels(dxd0.view(B, 2 * M, H, W), dxd, 0)
+        _transpose_into(dxd1.view(B, 2 * M, W, H), dxd, 2 * M)
+        ops.pw_wgrad_(dxd, xc, grad_of(op.x_proj_weight), blk_rows=M, perm=(0, 2, 1, 3))
         xw = op.x_proj_weight
         wallT = _pack(op, "wallT", [xw], lambda: torch.cat([xw.detach()[0], xw.detach()[2], xw.detach()[1], xw.detach()[3]], 0).t())
         dxc = ops.pw_gemm(dxd, wallT, Ci, res=dx0.view(B, Ci, H, W))

@@ -669,6 +669,9 @@ class gdMlp(nn.Module):
         return ops.pw_gemm(g, Wp, _out_features(self.project_out), bias=b, res=x)
 
 
+SS2D_MAX_D_STATE = 16       # bem_ss2d_scan_n_f32 / bem_ss2d_scan_n_bwd_f32
+
+
 class SS2D(nn.Module):
     """forward_type 'v05_noz' only (the one every arch on this path selects, UNet_arch.py:219)."""
 
@@ -678,15 +681,16 @@ class SS2D(nn.Module):
         super().__init__()
         if forward_type != "v05_noz" or not channel_first or d_conv != 3 or initialize != "v0":
             raise NotImplementedError("SS2D: only forward_type='v05_noz', channel_first, d_conv=3, init v0 are on the BEM path")
-        if int(d_state) != 1:
-            raise NotImplementedError("SS2D: the fused HIP scan is specialised for d_state = 1 (every shipped option file)")
+        N = int(d_state)
+        if not 1 <= N <= SS2D_MAX_D_STATE:
+            raise NotImplementedError(f"SS2D: d_state = {N}: the fused HIP scans take 1 <= d_state <= {SS2D_MAX_D_STATE}")
         d_inner = int(ssm_ratio * d_model)
         R = math.ceil(d_model / 16) if dt_rank == "auto" else dt_rank
-        self.d_inner, self.dt_rank, self.d_state = d_inner, R, 1
+        self.d_inner, self.dt_rank, self.d_state = d_inner, R, N
         self.in_proj = Linear2d(d_model, d_inner, bias=bias)
         self.act = act_layer()
         self.conv2d = DwConv2d(d_inner, bias=conv_bias)
-        K, N = 4, 1
+        K = 4
         self.x_proj_weight = nn.Parameter(torch.stack([nn.Linear(d_inner, R + 2 * N, bias=False).weight.detach() for _ in range(K)], 0))
         self.out_proj = Linear2d(d_inner, d_model, bias=bias)
         # mamba_init.init_dt_A_D (vmamba.py:222-289)
@@ -708,16 +712,19 @@ class SS2D(nn.Module):
         R = self.dt_rank
 
         def prep():
-            xw = self.x_proj_weight.detach()                                # (4, R+2, C)
+            xw = self.x_proj_weight.detach()                                # (4, R+2N, C)
             # one x_proj GEMM over the row-major planes for all four directions: rows [dir 0 | dir 2 | dir 1 | dir 3]
             wall = ops.pack_pw_weight(torch.cat([xw[0], xw[2], xw[1], xw[3]], 0).contiguous())
-            A = (-torch.exp(self.A_logs.detach().float())).reshape(-1).contiguous()
+            A = -torch.exp(self.A_logs.detach().float())                    # (4C, N): flat (4C) for the d_state = 1 kernels
+            A = (A.reshape(-1) if self.d_state == 1 else A).contiguous()
             return (wall, self.dt_projs_weight.detach().contiguous(), self.dt_projs_bias.detach().contiguous(), A,
                     self.Ds.detach().float().contiguous())
         return self._cache.get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
 
     def forward_fused(self, x, norm: LayerNorm2d):
         """x + out_proj(out_norm(merge(scan(SiLU(dw(in_proj(LN(x))))))))  (vmamba.py:700-716 + 547-698)."""
+        if self.d_state > 1:
+            return self._forward_fused_n(x, norm)
         B, C, H, W = x.shape
         Ci, R, L = self.d_inner, self.dt_rank, H * W
         wall, dtw, dtb, A, Ds = self._scan_params()
@@ -751,6 +758,33 @@ class SS2D(nn.Module):
         y0, y1 = ops.ss2d_scan(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L),
                                dtw, dtb, A, Ds)
         y1r = ops.transpose_planes(y1.view(B, Ci, W, H))
+        return ops.pw_gemm(y0.view(B, Ci, H, W), Wp, _out_features(self.out_proj), x2=y1r, in_mode=1,
+                           ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
+
+    def _forward_fused_n(self, x, norm: LayerNorm2d):
+        """forward_fused for d_state N > 1: x_dbl has R + 2N rows per direction and the scan is bem_ss2d_scan_n_f32."""
+        B, C, H, W = x.shape
+        Ci, L, M = self.d_inner, H * W, self.dt_rank + 2 * self.d_state
+        wall, dtw, dtb, A, Ds = self._scan_params()
+        front = ops.ss2d_front_supported(C, 4 * M) and Ci == C and type(self.in_proj) is Linear2d and type(self.conv2d) is DwConv2d \
+            and ops.USE_X6
+        if front:
+            Wpi, bi = self.in_proj.gemm_weights(B)
+            w, bw = self.conv2d.dw_weights(B)
+            xc, xd = ops.ss2d_front(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wpi, bi, w, bw, wall, 4 * M)
+        else:
+            Wp, b = self.in_proj.gemm_weights(B)
+            t = ops.pw_gemm(x, Wp, Ci, ln=(norm.weight.detach(), norm.bias.detach()), ln_eps=norm.eps, bias=b)
+            w, b = self.conv2d.dw_weights(B)
+            xc = ops.dwconv3x3(t, w, b, mode=1)
+            xd = ops.pw_gemm(xc, wall, 4 * M)                                     # (B, 4M, H, W): [dir 0 | dir 2 | dir 1 | dir 3]
+        xcT = ops.transpose_planes(xc)
+        xd1 = ops.transpose_plane_slice(xd, 2 * M, 2 * M)                         # (B, 2M, W, H)
+        y0, y1 = ops.ss2d_scan_n(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L),
+                                 dtw, dtb, A, Ds)
+        y1r = ops.transpose_planes(y1.view(B, Ci, W, H))
+        Wp, b = self.out_proj.gemm_weights(B)
+        on = self.out_norm
         return ops.pw_gemm(y0.view(B, Ci, H, W), Wp, _out_features(self.out_proj), x2=y1r, in_mode=1,
                            ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
 

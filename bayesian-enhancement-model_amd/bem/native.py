@@ -143,13 +143,18 @@ SIGNATURES = {
     "bem_pw_wgrad_x6_ws_elems": [I, I, I, I],
     "bem_conv_wgrad_f32": [P, P, I64, P, P, I, I, I, I, I, I, I, I, I, P],
     "bem_ss2d_scan_bwd_f32": [P] * 18 + [I, I, I, I, I64, I64, P],
+    "bem_ss2d_scan_n_supported": [I],
+    "bem_ss2d_scan_n_f32": [P] * 10 + [I, I, I, I, I, I64, I64, P],
+    "bem_ss2d_scan_n_bwd_ws_elems": [I, I, I, I],
+    "bem_ss2d_scan_n_bwd_f32": [P] * 19 + [I64, I, I, I, I, I, I64, I64, P],
     "bem_grad_sumsq_f32": [P, I64, P, P],
     "bem_adamw_step_f32": [P, P, P, P, I64, F, F, F, F, F, I, F, P, P, P, P],
     "bem_last_error": [],
     "bem_abi_version": [],
 }
 _RESTYPE = {"bem_last_error": ctypes.c_char_p, "bem_pw_packed_elems": c_int64, "bem_pw_x6_packed_elems": c_int64, "bem_selective_scan_bwd_ws_elems": c_int64,
-            "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64}
+            "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64,
+            "bem_ss2d_scan_n_bwd_ws_elems": c_int64}
 
 _lib = None
 

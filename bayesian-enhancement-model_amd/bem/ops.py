@@ -125,6 +125,45 @@ def ss2d_scan(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
     return y0, y1
 
 
+def ss2d_scan_n_supported(N):
+    return bool(lib().bem_ss2d_scan_n_supported(int(N)))
+
+
+def _xd_bstrides(name, xd0, xd1, B, rows, L):
+    bs = []
+    for n, t in (("xd0", xd0), ("xd1", xd1)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
+        if t.stride()[1:] != (rows * L, L, 1) or (B > 1 and (t.stride(0) < 2 * rows * L or (L % 4 == 0 and t.stride(0) % 4))):
+            raise ValueError(f"{name}: {n}: only the batch stride may differ from a contiguous (B,2,R+2N,L) tensor")
+        bs.append(t.stride(0) if B > 1 else 0)
+    return bs
+
+
+def ss2d_scan_n(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
+    """d_state N form of ss2d_scan (bem_ss2d_scan_n_f32): xd0 / xd1 (B,2,R+2N,L) with rows [dt | B_0..B_{N-1} | C_0..C_{N-1}]
+    (contiguous or batch-strided channel slices), A (4C, N) = -exp(A_logs)."""
+    for n, t in (("x0", x0), ("x1", x1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
+        _chk(t, n)
+    B, C, L = x0.shape
+    R = dtw.shape[2]
+    if A.dim() != 2 or A.shape[0] != 4 * C:
+        raise ValueError(f"ss2d_scan_n: A {tuple(A.shape)} is not (4C, N)")
+    N = A.shape[1]
+    if not ss2d_scan_n_supported(N):
+        raise NotImplementedError(f"ss2d_scan_n: d_state {N} outside 1..16")
+    if x1.shape != x0.shape or xd0.shape != (B, 2, R + 2 * N, L) or xd1.shape != xd0.shape:
+        raise ValueError(f"ss2d_scan_n shapes: x {tuple(x0.shape)}/{tuple(x1.shape)} xd {tuple(xd0.shape)}/{tuple(xd1.shape)} R={R} N={N}")
+    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or Ds.numel() != 4 * C:
+        raise ValueError("ss2d_scan_n parameter shapes")
+    bs = _xd_bstrides("ss2d_scan_n", xd0, xd1, B, R + 2 * N, L)
+    y0 = torch.empty_like(x0)
+    y1 = torch.empty_like(x0)
+    check(lib().bem_ss2d_scan_n_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1),
+                                    B, C, L, R, N, bs[0], bs[1], _stream()), "ss2d_scan_n")
+    return y0, y1
+
+
 def ss2d_scan_rm_supported(H, W, R):
     return bool(lib().bem_ss2d_scan_rm_supported(H, W, R))
 
@@ -1307,6 +1346,36 @@ def ss2d_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw,
     check(lib().bem_ss2d_scan_bwd_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dy0), _p(dy1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(dx0), _p(dx1),
                                       _p(dxd0), _p(dxd1), _p(dAlog), _p(dDs), _p(ddtw), _p(ddtb), B, C, L, R, bs[0], bs[1], _stream()),
           "ss2d_scan_bwd")
+    return dx0, dx1, dxd0, dxd1
+
+
+def ss2d_scan_n_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw, ddtb):
+    """Backward of ss2d_scan_n: returns (dx0, dx1, dxd0, dxd1), dxd* (B,2,R+2N,L); parameter gradients accumulated into dAlog (4C, N),
+    dDs (4C), ddtw (4,C,R), ddtb (4,C)."""
+    for n, t in (("x0", x0), ("x1", x1), ("dy0", dy0), ("dy1", dy1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds), ("dAlog", dAlog),
+                 ("dDs", dDs), ("ddtw", ddtw), ("ddtb", ddtb)):
+        _chk(t, n)
+    B, C, L = x0.shape
+    R = dtw.shape[2]
+    if A.dim() != 2 or A.shape[0] != 4 * C:
+        raise ValueError(f"ss2d_scan_n_bwd: A {tuple(A.shape)} is not (4C, N)")
+    N = A.shape[1]
+    if not ss2d_scan_n_supported(N):
+        raise NotImplementedError(f"ss2d_scan_n_bwd: d_state {N} outside 1..16")
+    if x1.shape != x0.shape or dy0.shape != x0.shape or dy1.shape != x0.shape or xd0.shape != (B, 2, R + 2 * N, L) or xd1.shape != xd0.shape:
+        raise ValueError("ss2d_scan_n_bwd: activation shapes")
+    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or Ds.numel() != 4 * C or dAlog.numel() != 4 * C * N or dDs.numel() != 4 * C \
+            or ddtw.numel() != 4 * C * R or ddtb.numel() != 4 * C:
+        raise ValueError("ss2d_scan_n_bwd: parameter shapes")
+    bs = _xd_bstrides("ss2d_scan_n_bwd", xd0, xd1, B, R + 2 * N, L)
+    dx0, dx1 = torch.empty_like(x0), torch.empty_like(x0)
+    dxd0 = torch.empty(B, 2, R + 2 * N, L, device=x0.device, dtype=x0.dtype)
+    dxd1 = torch.empty(B, 2, R + 2 * N, L, device=x0.device, dtype=x0.dtype)
+    nws = int(lib().bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N))
+    ws = torch.empty(max(nws, 1), device=x0.device, dtype=torch.float32)
+    check(lib().bem_ss2d_scan_n_bwd_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dy0), _p(dy1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(dx0), _p(dx1),
+                                        _p(dxd0), _p(dxd1), _p(dAlog), _p(dDs), _p(ddtw), _p(ddtb), _p(ws), ws.numel(), B, C, L, R, N,
+                                        bs[0], bs[1], _stream()), "ss2d_scan_n_bwd")
     return dx0, dx1, dxd0, dxd1
 
 

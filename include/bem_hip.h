@@ -103,6 +103,18 @@ int bem_ss2d_scan_rm_f32(const float* x, const float* xd0, const float* xd1, con
                          const float* A, const float* Ds, float* y0, float* y1, int B, int C, int H, int W, int R,
                          int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
 
+/* Fused SS2D core for d_state = N > 1 (SS2D with ssm_d_state from the option file, vmamba.py:251-253,345-346,442,518-519: x_proj emits
+ * R + 2N rows per direction, A_logs is (4C, N), forward_corev2 splits [R, N, N] at :660-671).  The operands of bem_ss2d_scan_strided_f32
+ * except:
+ *   xd0, xd1 (B,2,R+2N,L)  rows [dt_0..dt_{R-1}, B_0..B_{N-1}, C_0..C_{N-1}] per direction; batch strides as above (0 = contiguous)
+ *   A (4C, N) = -exp(A_logs)
+ * Per direction y = sum_n C_n h_n + D x with h_n = exp(dl A_n) h_n + dl B_n x, dl = softplus(dt + dtb) (threshold 20).
+ * 1 <= N <= 16 (bem_ss2d_scan_n_supported), 1 <= R <= 16.  The d_state = 1 path keeps the kernels above. */
+int bem_ss2d_scan_n_supported(int N);
+int bem_ss2d_scan_n_f32(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dtw, const float* dtb,
+                        const float* A, const float* Ds, float* y0, float* y1, int B, int C, int L, int R, int N,
+                        int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pointwise (1x1) channel-mix GEMM with fused prologue / epilogue (argument block of bem_pw_gemm_x6_f32).  Replaces
  * Linear2d / nn.Conv2d(k=1) / LayerNorm2d+Linear2d chains (vmamba.py:42-63,123-133,702,715,1326-1334).
@@ -458,6 +470,14 @@ int bem_ss2d_scan_bwd_f32(const float* x0, const float* x1, const float* xd0, co
                           const float* dtw, const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0,
                           float* dxd1, float* dAlog, float* dDs, float* ddtw, float* ddtb, int B, int C, int L, int R,
                           int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
+/* Backward of bem_ss2d_scan_n_f32 (what autograd runs through forward_corev2 with d_state N, vmamba.py:657-684; SelectiveScanCuda.backward
+ * csms6s.py:95-113).  Outputs as bem_ss2d_scan_bwd_f32 with dxd0 / dxd1 (B,2,R+2N,L) contiguous, zeroed by the call, and dAlog (4C, N).
+ * ws: scratch of at least bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N) floats (the forward states entering every 256-position tile). */
+int64_t bem_ss2d_scan_n_bwd_ws_elems(int B, int C, int L, int N);
+int bem_ss2d_scan_n_bwd_f32(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dy0, const float* dy1,
+                            const float* dtw, const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0,
+                            float* dxd1, float* dAlog, float* dDs, float* ddtw, float* ddtb, float* ws, int64_t ws_elems, int B, int C,
+                            int L, int R, int N, int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
 
 /* clip_grad_norm_ + torch.optim.AdamW on one flat parameter buffer.  bem_grad_sumsq_f32: acc[0] = sum g^2 (f64, zeroed by the
  * call).  bem_adamw_step_f32: g *= min(1, max_norm / (sqrt(sumsq) + 1e-6)) when max_norm > 0 (read on the device), then the AdamW
