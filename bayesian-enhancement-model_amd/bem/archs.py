@@ -4,6 +4,10 @@
   DecompDualBranchDDWavelet   basicsr/archs/DecompDualBranchDDWavelet_arch.py:146-369
   DecompSingleBranch          basicsr/archs/DecompSingleBranch_arch.py:53-237
   Decomp (model1 / model4)    basicsr/QD/model1.py, model4.py:167-262 (+ the wavelet-domain MyDecomp :71-132)
+  VMUNet                      basicsr/archs/VMUnet_arch.py:68-240
+  NaiveVMUNetTwoBranch        basicsr/archs/TwoBranchNaive_arch.py:68-271
+  TunedModel                  basicsr/archs/TunedModel_arch.py:162-406
+  FusedTunedModel             basicsr/archs/FusedModel_arch.py:101-332
 
 forward(x, mask=None) -> [x, out] like the reference.  All compute goes through bem.ops (HIP).
 """
@@ -190,11 +194,13 @@ class _Stage2(nn.Module):
     calls them in its own registration order (which fixes parameters() order and the RNG draws of the initialisation)."""
 
     def _setup(self, stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, decomp_model, wavelet_out):
-        """Loads the frozen decomposition; returns level(dim, i), the VSS stack of U-Net level i (i = -1: the bottleneck)."""
+        """Loads the frozen decomposition (none for decomp_model=None); returns level(dim, i), the VSS stack of U-Net level i (i = -1: the
+        bottleneck)."""
         self.stage, self.num_levels = stage, len(num_blocks)
         if isinstance(d_state, int):
             d_state = [d_state] * self.num_levels
-        self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=wavelet_out)
+        if decomp_model is not None:
+            self.decomp = Decomp.from_shipped(decomp_model, wavelet_out=wavelet_out)
         return lambda dim, i: make_vss_level(dim, num_blocks[i], d_state[i], ssm_ratio, mlp_ratio, mlp_type)
 
     def _add_encoder(self, sfx, cin, n_feat, level):
@@ -237,6 +243,20 @@ class _Stage2(nn.Module):
         for dec, skip in zip(getattr(self, "decoders" + sfx), reversed(skips)):
             f = dec["block"](dec["fuse"](dec["up"](f), x2=skip, in_mode=2))
         return getattr(self, "proj" + sfx)(f)
+
+    def _cross_fuse(self, f1, f2):
+        """The one cross-fusion at the deepest encoder level of DecompDualBranch / FusedTunedModel: branch 2 takes from branch 1 first, then
+        branch 1 from the fused branch 2 (DecompModel_arch.py:311-312, FusedModel_arch.py:299-300)."""
+        fa, fb = ag.fork(f1)                                            # branch 1's deepest features feed both cross-fusions
+        f2 = self.cross_fusion_12(fa, f2)
+        f2a, f2b = ag.fork(f2)
+        return self.cross_fusion_21(f2a, fb), f2b
+
+    def _attn_bottleneck(self, sfx, f, train):
+        """bottleneck<sfx>, then SE and spatial attention: the SE gate is applied inside the attention kernel in inference."""
+        f = getattr(self, "bottleneck" + sfx)(f)
+        se, sa = getattr(self, "bottleneck_se" + sfx), getattr(self, "spatial_attention" + sfx)
+        return sa(se(f)) if train else sa(f, chan_scale=se.gate(f))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -460,16 +480,8 @@ class DecompDualBranch(_Stage2):
         with torch.enable_grad() if train else torch.no_grad():
             f1, sk1 = self._encode("", qi, cin_slice=(0, 4))
             f2, sk2 = self._encode("2", qi, cin_slice=(4, 4))
-            fa, fb = ag.fork(f1)                                        # branch 1's deepest features feed both cross-fusions
-            f2 = self.cross_fusion_12(fa, f2)                           # branch 2 takes from branch 1 first ...
-            f2a, f2b = ag.fork(f2)
-            f1 = self.cross_fusion_21(f2a, fb)                          # ... and branch 1 from the fused branch 2 (:311-312)
-            outs = []
-            for s_, f, sk in (("", f1, sk1), ("2", f2b, sk2)):
-                f = getattr(self, "bottleneck" + s_)(f)
-                se, sa = getattr(self, "bottleneck_se" + s_), getattr(self, "spatial_attention" + s_)
-                f = sa(se(f)) if train else sa(f, chan_scale=se.gate(f))
-                outs.append(self._decode(s_, f, sk))
+            f1, f2 = self._cross_fuse(f1, f2)
+            outs = [self._decode(s_, self._attn_bottleneck(s_, f, train), sk) for s_, f, sk in (("", f1, sk1), ("2", f2, sk2))]
             out = _hamilton(outs[0], outs[1], train)
         return [x, out]
 
@@ -534,6 +546,141 @@ class DecompSingleBranchDD(DecompSingleBranch):
             ops.copy_channels(self.decomp(x, 0), fea, 0)
             ops.copy_channels(self.decomp(x, 3), fea, 8)
         return [x, self._run(fea)]
+# ------------------------------------------------------------------------------------------------
+# Stage-II without a decomposition: U-Nets on the 6-channel cat(image, upsampled condition) -- VMUNet and its two-branch kin
+# ------------------------------------------------------------------------------------------------
+def _check_head_width(arch, out_channels):
+    """Before any parameter is drawn: the head kernel takes two 3-channel branch outputs only (C_out 3, C_in 6)."""
+    if out_channels != 3:
+        raise NotImplementedError(f"{arch}: out_channels={out_channels}; only out_channels 3 is supported by the two-branch head kernel")
+
+
+class FusionHead(nn.Sequential):
+    """fusion = Sequential(Conv2d(2C, C, 3, p=1), ReLU, Conv2d(C, C, 3, p=1)) on cat(out_1, out_2) (TunedModel_arch.py:315-319,406,
+    FusedModel_arch.py:234-238,330), evaluated by one kernel from the two branch outputs (the concatenation is never formed).  C = 3
+    only: the width of every option file."""
+
+    def __init__(self, out_channels):
+        if out_channels != 3:
+            raise NotImplementedError(f"fusion head: out_channels={out_channels}; only out_channels 3 (Conv2d(6,3) -> ReLU -> Conv2d(3,3)) "
+                                      "is supported")
+        super().__init__(nn.Conv2d(6, 3, 3, 1, 1, bias=True), nn.ReLU(inplace=True), nn.Conv2d(3, 3, 3, 1, 1, bias=True))
+
+    def forward(self, o1, o2):
+        _need_cuda(o1)
+        c1, c2 = self[0], self[2]
+        if grad_mode(self):
+            return ag.FusionHeadFn.apply(o1, o2, c1.weight, c1.bias, c2.weight, c2.bias)
+        return ops.fusion_head(o1, o2, c1.weight.detach(), c1.bias.detach(), c2.weight.detach(), c2.bias.detach())
+
+
+class _ImageDomain(_Stage2):
+    """The reference builds these archs branch by branch (first_conv, encoders, bottleneck, decoders, proj, last_act, down_layers; branch 2
+    with the suffix ``2``), then their extra blocks; each subclass registers in its reference's order, so parameters() order, state-dict
+    keys and the RNG draws of the initialisation are the reference's."""
+
+    def _add_unet(self, sfx, cin, n_feat, out_ch, level, last_act):
+        cur = self._add_encoder(sfx, cin, n_feat, level)
+        setattr(self, "bottleneck" + sfx, level(cur, -1))
+        self._add_decoder(sfx, cur, n_feat, out_ch, level)
+        setattr(self, "last_act" + sfx, _check_last_act(last_act))
+        self._add_down_layers(sfx, n_feat)
+        return cur
+
+    def forward(self, x, mask=None):
+        """Inference: kernels only, nothing recorded.  ``train()`` mode with autograd enabled (image_enhancer_model.py:165-216): every block
+        records its bem.autograd node."""
+        _need_cuda(x)
+        train = grad_mode(self)
+        x = x.contiguous()
+        with torch.enable_grad() if train else torch.no_grad():
+            out = self._body(x, train)
+        return [x, out]
+
+
+class VMUNet(_ImageDomain):
+    """VMUnet_arch.py:68-240: one U-Net."""
+
+    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1, mlp_ratio=4,
+                 mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False, last_act=None):
+        super().__init__()
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, None, False)
+        self._add_unet("", in_channels, n_feat, out_channels, level, last_act)
+        self.drop_path = nn.Identity()
+        self.apply(_init_weights)
+
+    def _body(self, x, train):
+        f, sk = self._encode("", x)
+        return self._decode("", self.bottleneck(f), sk)
+
+
+class NaiveVMUNetTwoBranch(_ImageDomain):
+    """TwoBranchNaive_arch.py:68-271: two U-Nets on the same input, outputs averaged."""
+
+    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1, mlp_ratio=4,
+                 mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False, last_act=None):
+        super().__init__()
+        _check_head_width("NaiveVMUNetTwoBranch", out_channels)
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, None, False)
+        for s_ in ("", "2"):
+            self._add_unet(s_, in_channels, n_feat, out_channels, level, last_act)
+        self.drop_path = nn.Identity()
+        self.apply(_init_weights)
+
+    def _body(self, x, train):
+        o1, o2 = [self._decode(s_, getattr(self, "bottleneck" + s_)(f), sk) for s_, (f, sk) in (("", self._encode("", x)), ("2", self._encode("2", x)))]
+        return ag.BranchMeanFn.apply(o1, o2) if train else ops.fusion_head(o1, o2, mean=True)
+
+
+class TunedModel(_ImageDomain):
+    """TunedModel_arch.py:162-406: two U-Nets with SE + spatial attention after each bottleneck, outputs fused by the 3x3 head."""
+
+    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1, mlp_ratio=4,
+                 mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False, last_act=None):
+        super().__init__()
+        _check_head_width("TunedModel", out_channels)
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, None, False)
+        for s_ in ("", "2"):
+            cur = self._add_unet(s_, in_channels, n_feat, out_channels, level, last_act)
+        self.drop_path = nn.Identity()
+        self.spatial_attention, self.spatial_attention2 = SpatialAttention(), SpatialAttention()
+        self.fusion = FusionHead(out_channels)
+        self.bottleneck_se, self.bottleneck_se2 = SEBlock(cur), SEBlock(cur)
+        self.apply(_init_weights)
+
+    def _body(self, x, train):
+        outs = []
+        for s_ in ("", "2"):
+            f, sk = self._encode(s_, x)
+            outs.append(self._decode(s_, self._attn_bottleneck(s_, f, train), sk))
+        return self.fusion(*outs)
+
+
+class FusedTunedModel(_ImageDomain):
+    """FusedModel_arch.py:101-332: TunedModel with one cross-fusion at the deepest encoder level, the sequence of DecompDualBranch."""
+
+    def __init__(self, in_channels=3, out_channels=3, n_feat=40, stage=1, num_blocks=[2, 2, 2], d_state=1, ssm_ratio=1, mlp_ratio=4,
+                 mlp_type="gdmlp", use_pixelshuffle=False, drop_path=0.0, use_illu=False, sam=False, last_act=None):
+        super().__init__()
+        _check_head_width("FusedTunedModel", out_channels)
+        level = self._setup(stage, num_blocks, d_state, ssm_ratio, mlp_ratio, mlp_type, None, False)
+        for s_ in ("", "2"):
+            cur = self._add_unet(s_, in_channels, n_feat, out_channels, level, last_act)
+        self.drop_path = nn.Identity()
+        self.cross_fusion_12, self.cross_fusion_21 = CrossFusionBlock(cur), CrossFusionBlock(cur)
+        self.bottleneck_se, self.bottleneck_se2 = SEBlock(cur), SEBlock(cur)
+        self.spatial_attention, self.spatial_attention2 = SpatialAttention(), SpatialAttention()
+        self.fusion = FusionHead(out_channels)
+        self.apply(_init_weights)
+
+    def _body(self, x, train):
+        f1, sk1 = self._encode("", x)
+        f2, sk2 = self._encode("2", x)
+        f1, f2 = self._cross_fuse(f1, f2)
+        outs = [self._decode(s_, self._attn_bottleneck(s_, f, train), sk) for s_, f, sk in (("", f1, sk1), ("2", f2, sk2))]
+        return self.fusion(*outs)
+
+
 # ------------------------------------------------------------------------------------------------
 # Stage-I: Network (UNet_arch.py)
 # ------------------------------------------------------------------------------------------------

@@ -656,3 +656,38 @@ class Hamilton8Fn(Function):
     def backward(ctx, dout):
         (q8,) = ctx.saved_tensors
         return ops.hamilton_bwd(q8, dout.contiguous())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Output heads of the two-branch archs without a decomposition (TunedModel_arch.py:315-319,406, TwoBranchNaive_arch.py:268)
+# ------------------------------------------------------------------------------------------------------------------
+class FusionHeadFn(Function):
+    """fusion(cat(o1, o2)) = Conv2d(6,3,3) -> ReLU -> Conv2d(3,3,3) as one kernel.  Only the two inputs are saved: the backward
+    recomputes the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, o1, o2, w1, b1, w2, b2):
+        o1, o2 = o1.contiguous(), o2.contiguous()
+        ctx.save_for_backward(o1, o2)
+        ctx.w = (w1, b1, w2, b2)
+        return ops.fusion_head(o1, o2, w1.detach(), b1.detach(), w2.detach(), b2.detach())
+
+    @staticmethod
+    def backward(ctx, dout):
+        o1, o2 = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.w
+        do1, do2 = ops.fusion_head_bwd_(o1, o2, dout.contiguous(), w1.detach(), b1.detach(), w2.detach(), grad_of(w1), grad_of(b1),
+                                        grad_of(w2), grad_of(b2))
+        return do1, do2, None, None, None, None
+
+
+class BranchMeanFn(Function):
+    """(o1 + o2) / 2; both input gradients are dout / 2."""
+
+    @staticmethod
+    def forward(ctx, o1, o2):
+        return ops.fusion_head(o1.contiguous(), o2.contiguous(), mean=True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.fusion_head_bwd_(None, None, dout.contiguous(), mean=True)

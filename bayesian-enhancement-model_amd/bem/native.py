@@ -147,6 +147,9 @@ SIGNATURES = {
     "bem_ss2d_scan_n_f32": [P] * 10 + [I, I, I, I, I, I64, I64, P],
     "bem_ss2d_scan_n_bwd_ws_elems": [I, I, I, I],
     "bem_ss2d_scan_n_bwd_f32": [P] * 19 + [I64, I, I, I, I, I, I64, I64, P],
+    "bem_fusion_head_f32": [P, I64, P, I64, P, P, P, P, P, I, I, I, I, I, I, P],
+    "bem_fusion_head_bwd_ws_elems": [I, I, I],
+    "bem_fusion_head_bwd_f32": [P, I64, P, I64] + [P] * 11 + [I64, I, I, I, I, I, I, P],
     "bem_grad_sumsq_f32": [P, I64, P, P],
     "bem_adamw_step_f32": [P, P, P, P, I64, F, F, F, F, F, I, F, P, P, P, P],
     "bem_last_error": [],
@@ -154,7 +157,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"bem_last_error": ctypes.c_char_p, "bem_pw_packed_elems": c_int64, "bem_pw_x6_packed_elems": c_int64, "bem_selective_scan_bwd_ws_elems": c_int64,
             "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64,
-            "bem_ss2d_scan_n_bwd_ws_elems": c_int64}
+            "bem_ss2d_scan_n_bwd_ws_elems": c_int64, "bem_fusion_head_bwd_ws_elems": c_int64}
 
 _lib = None
 

@@ -1320,6 +1320,71 @@ def conv_wgrad_(dy, x, dw, dbias=None, stride=1, pad=1, cin_slice=None):
     return dw
 
 
+def _head_operand(t, name, shape):
+    """A (B,3,H,W) branch output whose planes are contiguous; the batch stride is free (a channel slice of a wider tensor is fine)."""
+    if t is None:
+        raise ValueError(f"{name} is required")
+    if not t.is_cuda:
+        raise native.BemNativeError(f"{name} must be a CUDA/HIP tensor: the BEM hot path has no CPU implementation")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    if t.dim() != 4 or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError(f"fusion_head: {name} must be {shape or '(B,3,H,W)'}, got {tuple(t.shape)}")
+    B, C, H, W = t.shape
+    if C != 3:
+        raise ValueError(f"fusion_head: {name} has {C} channels; only out_channels 3 is supported")
+    if t.stride()[1:] != (H * W, W, 1) and B * H * W > 0:
+        raise ValueError(f"fusion_head: {name} planes must be contiguous (strides {t.stride()})")
+    return t.stride(0)
+
+
+def _head_weights(w1, b1, w2, b2):
+    for n, t, shp in (("w1", w1, (3, 6, 3, 3)), ("b1", b1, (3,)), ("w2", w2, (3, 3, 3, 3)), ("b2", b2, (3,))):
+        if t is None:
+            continue
+        _chk(t, n)
+        if tuple(t.shape) != shp:
+            raise ValueError(f"fusion_head: {n} must be {shp} (Conv2d(6,3,3) then Conv2d(3,3,3)), got {tuple(t.shape)}")
+
+
+def fusion_head(o1, o2, w1=None, b1=None, w2=None, b2=None, mean=False):
+    """The output head of the two-branch archs on two (B,3,H,W) branch outputs, without forming their concatenation:
+    conv2(relu(conv1(cat(o1, o2)) + b1)) + b2 (w1 (3,6,3,3), w2 (3,3,3,3)), or (o1 + o2) / 2 with ``mean=True``."""
+    bs1 = _head_operand(o1, "o1", None)
+    B, _, H, W = o1.shape
+    bs2 = _head_operand(o2, "o2", (B, 3, H, W))
+    if not mean:
+        if w1 is None or b1 is None or w2 is None or b2 is None:
+            raise ValueError("fusion_head: w1, b1, w2, b2 are required")
+        _head_weights(w1, b1, w2, b2)
+    out = torch.empty(B, 3, H, W, device=o1.device, dtype=o1.dtype)
+    check(lib().bem_fusion_head_f32(_p(o1), bs1, _p(o2), bs2, _p(w1), _p(b1), _p(w2), _p(b2), _p(out), B, 6, 3, H, W, int(bool(mean)),
+                                    _stream()), "fusion_head")
+    return out
+
+
+def fusion_head_bwd_(o1, o2, dout, w1=None, b1=None, w2=None, dw1=None, db1=None, dw2=None, db2=None, mean=False):
+    """Backward of fusion_head: returns (do1, do2) (B,3,H,W); dw1, db1, dw2, db2 += the weight gradients (``mean=False``)."""
+    _chk(dout, "dout")
+    if dout.dim() != 4 or dout.shape[1] != 3:
+        raise ValueError(f"fusion_head_bwd: dout must be (B,3,H,W), got {tuple(dout.shape)}")
+    B, _, H, W = dout.shape
+    bs1 = bs2 = 0
+    ws = None
+    if not mean:
+        bs1, bs2 = _head_operand(o1, "o1", (B, 3, H, W)), _head_operand(o2, "o2", (B, 3, H, W))
+        if any(t is None for t in (w1, b1, w2, dw1, db1, dw2, db2)):
+            raise ValueError("fusion_head_bwd: w1, b1, w2 and the gradient buffers dw1, db1, dw2, db2 are required")
+        _head_weights(w1, b1, w2, None)
+        _head_weights(dw1, db1, dw2, db2)
+        ws = torch.empty(int(lib().bem_fusion_head_bwd_ws_elems(B, H, W)), device=dout.device, dtype=torch.float32)
+    do1, do2 = torch.empty_like(dout), torch.empty_like(dout)
+    check(lib().bem_fusion_head_bwd_f32(_p(o1), bs1, _p(o2), bs2, _p(dout), _p(w1), _p(b1), _p(w2), _p(do1), _p(do2), _p(dw1), _p(db1),
+                                        _p(dw2), _p(db2), _p(ws), 0 if ws is None else ws.numel(), B, 6, 3, H, W, int(bool(mean)), _stream()),
+          "fusion_head_bwd")
+    return do1, do2
+
+
 def ss2d_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw, ddtb):
     """Backward of ss2d_scan: returns (dx0, dx1, dxd0, dxd1); parameter gradients accumulated into dAlog (4C), dDs (4C),
     ddtw (4,C,R), ddtb (4,C)."""

@@ -167,12 +167,17 @@ def synthetic_pair(shape, seed=287128, device="cpu"):
 
 def build_nets(n_feat=40, num_blocks=(2, 2, 2), seed=100, device="cuda", stage2="DecompDualBranchDDWavelet", decomp="model4"):
     """Seeded random-init Stage-I (Bayesian) and Stage-II nets through the registry, like eval.py:84-85."""
+    import inspect
     from basicsr.archs import build_network
     from basicsr.bayesian import convert2bnn_selective
+    from basicsr.utils.registry import ARCH_REGISTRY
     torch.manual_seed(seed)
     common = dict(n_feat=n_feat, d_state=[1, 1, 1], ssm_ratio=1, mlp_ratio=4, mlp_type="gdmlp", use_pixelshuffle=True,
                   drop_path=0.0, sam=False, stage=1, num_blocks=list(num_blocks))
     net1 = build_network(dict(type="Network", in_channels=3, out_channels=3, **common))
     convert2bnn_selective(net1, {"sigma_init": 0.05, "decay": 0.998, "pretrain": False})
-    net2 = build_network(dict(type=stage2, in_channels=6, out_channels=3, decomp_model=decomp, **common))
+    opt2 = dict(type=stage2, in_channels=6, out_channels=3, **common)
+    if "decomp_model" in inspect.signature(ARCH_REGISTRY.get(stage2)).parameters:      # the image-domain archs take no decomposition
+        opt2["decomp_model"] = decomp
+    net2 = build_network(opt2)
     return net1.to(device).eval(), net2.to(device).eval()

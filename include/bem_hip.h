@@ -479,6 +479,25 @@ int bem_ss2d_scan_n_bwd_f32(const float* x0, const float* x1, const float* xd0, 
                             float* dxd1, float* dAlog, float* dDs, float* ddtw, float* ddtb, float* ws, int64_t ws_elems, int B, int C,
                             int L, int R, int N, int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
 
+/* Output head of the two-branch Stage-II archs (replaces TunedModel_arch.py:315-319,406 and FusedModel_arch.py:234-238,330:
+ * fusion = Sequential(Conv2d(6,3,3,p=1), ReLU, Conv2d(3,3,3,p=1)) applied to cat(out_1, out_2); and TwoBranchNaive_arch.py:268).
+ *   mode 0: out = conv2(relu(conv1(cat(o1, o2)) + b1)) + b2, h zero-padded at the image border like nn.Conv2d.
+ *           w1 (3,6,3,3), b1 (3), w2 (3,3,3,3), b2 (3), read on the device.
+ *   mode 1: out = (o1 + o2) / 2 (weights unused, may be NULL).
+ * o1 / o2 (B,3,H,W) planes contiguous, batch strides o*_bstride elements (0 = 3*H*W); out (B,3,H,W) contiguous.  Only C_out = 3 and
+ * C_in = 6 (two 3-channel branch outputs) are supported; other values are refused. */
+int bem_fusion_head_f32(const float* o1, int64_t o1_bstride, const float* o2, int64_t o2_bstride, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* out, int B, int Cin, int Cout, int H, int W, int mode, void* stream);
+/* Backward of bem_fusion_head_f32.  The pre-activation is recomputed from o1 / o2 (nothing is saved by the forward); the ReLU passes
+ * the gradient where pre > 0 only (threshold_backward).  do1 / do2 (B,3,H,W) contiguous are written.  mode 0: dw1, db1, dw2, db2
+ * += the weight gradients, summed from per-workgroup partials in ws (at least bem_fusion_head_bwd_ws_elems(B, H, W) floats) in f64
+ * in a fixed order by a second launch -- bitwise reproducible, no float atomics.  mode 1: do1 = do2 = dout / 2 (o1, o2, weights,
+ * ws unused). */
+int64_t bem_fusion_head_bwd_ws_elems(int B, int H, int W);
+int bem_fusion_head_bwd_f32(const float* o1, int64_t o1_bstride, const float* o2, int64_t o2_bstride, const float* dout, const float* w1,
+                            const float* b1, const float* w2, float* do1, float* do2, float* dw1, float* db1, float* dw2, float* db2,
+                            float* ws, int64_t ws_elems, int B, int Cin, int Cout, int H, int W, int mode, void* stream);
+
 /* clip_grad_norm_ + torch.optim.AdamW on one flat parameter buffer.  bem_grad_sumsq_f32: acc[0] = sum g^2 (f64, zeroed by the
  * call).  bem_adamw_step_f32: g *= min(1, max_norm / (sqrt(sumsq) + 1e-6)) when max_norm > 0 (read on the device), then the AdamW
  * update with bias corrections of `step` (>= 1); norm_out (or NULL) receives the unclipped total norm.  hyper (NULL or three floats
