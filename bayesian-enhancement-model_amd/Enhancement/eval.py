@@ -4,18 +4,21 @@ line (eval.py:30-60) on the device-resident pipeline (bem.pipeline.BEMPipeline):
 
   python Enhancement/eval.py --opt Options/CG_UNet_LOLv1.yml --cond_opt Options/DecompDualBranch2DDWavelet_4.yml \
       --weights cg.pth --cond_weights stage2.pth --input_dir data/LOLv1/Test/input --target_dir data/LOLv1/Test/target \
-      --dataset LOLv1 --GT_mean --num_samples 16 [--no_ref clip | --no_ref niqe --niqe_params niqe_pris_params.npz] [--psnr_weight 0.5]
-      [--Monte_Carlo] [--deterministic]
+      --dataset LOLv1 --GT_mean --num_samples 16 [--no_ref clip | --no_ref niqe --niqe_params niqe_pris_params.npz |
+      --no_ref uiqm_uciqe [--uiqm_weight 0.5]] [--psnr_weight 0.5] [--Monte_Carlo] [--deterministic]
 
 What differs from the reference script, none of it in the results: all N samples of an image go through Stage I and Stage II as one
 batch (``--parallel_num`` is accepted and ignored), conditions never leave the GPU, selection metrics run on the device, and images
 are read / written with PIL (cv2, skimage, natsort, lpips, torchmetrics are not dependencies).  ``--no_ref clip`` uses the scorer
 returned by ``make_clip_scorer`` -- the deterministic stand-in of bem.scorers unless a CLIP-IQA module is importable.  ``--no_ref niqe``
 scores every candidate with NIQE on the device (bem.ops.niqe) and keeps the first minimum; it needs ``--niqe_params``, the pristine-model
-file ``niqe_pris_params.npz`` of a BasicSR install (basicsr/metrics/), which is data and not shipped here.  ``--no_ref uiqm_uciqe`` and
-``--lpips`` need host-side metric packages that are outside this path and raise a clear error.
+file ``niqe_pris_params.npz`` of a BasicSR install (basicsr/metrics/), which is data and not shipped here.  ``--no_ref uiqm_uciqe``
+scores every candidate with UIQM and UCIQE on the device (bem.ops.uiqm_uciqe) and keeps the first maximum of ``w * uiqm / max(uiqm) +
+(1 - w) * uciqe / max(uciqe)``, w = ``--uiqm_weight`` (eval.py:277-278); images must resize to at least 10 rows at width 256.  ``--lpips``
+needs a network whose weights are outside this path and raises a clear error.  Scoring happens after the candidates are gathered, so
+every mode works on the sample-sharded ``torchrun`` path.
 Output: ``<result_dir>/<dataset>/<image>.png`` (the selected candidate) and ``result.txt`` with the reference's summary lines
-(``Best_NIQE`` after the PSNR / SSIM lines, eval.py:344-347)."""
+(``Best_NIQE``, then ``Best_UIQM`` and ``Best_UCIQE``, after the PSNR / SSIM lines, eval.py:344-355)."""
 import argparse
 import os
 import sys
@@ -78,8 +81,14 @@ def load_params(net, path):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
-    if args.no_ref == "uiqm_uciqe" or args.lpips:
-        raise SystemExit("--no_ref uiqm_uciqe and --lpips are host-side metric packages outside the HIP path (SURVEY.md section 2 rows 16, 1)")
+    if args.lpips:
+        raise SystemExit("--lpips is a host-side metric package outside the HIP path (SURVEY.md section 2 row 1)")
+    if args.no_ref == "uiqm_uciqe":
+        # checked before any model or device work
+        if not os.path.isdir(args.input_dir):
+            raise SystemExit(f"--no_ref uiqm_uciqe: --input_dir {args.input_dir!r} is not a directory")
+        if not np.isfinite(args.uiqm_weight):
+            raise SystemExit(f"--no_ref uiqm_uciqe: --uiqm_weight must be finite, got {args.uiqm_weight}")
     if args.no_ref == "niqe" and not args.niqe_params:
         raise SystemExit("--no_ref niqe needs --niqe_params PATH: the NIQE pristine-model file niqe_pris_params.npz "
                          "(basicsr/metrics/niqe_pris_params.npz in a BasicSR install)")
@@ -87,7 +96,7 @@ def main(argv=None):
     from basicsr.models import build_model
     from basicsr.utils.options import parse
     from bem.pipeline import BEMPipeline
-    from bem.scorers import FullReference, Niqe, NiqeParams
+    from bem.scorers import FullReference, Niqe, NiqeParams, UiqmUciqe
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N Enhancement/eval.py ...`: the driver feeds ONE image at a
     # time (eval.py:160-222), so the N Bayesian samples of that image are what gets sharded (sample-major, bem.dist); every rank holds the
     # gathered candidates, rank 0 writes the files
@@ -116,9 +125,11 @@ def main(argv=None):
         scorer = make_clip_scorer(args.clip_prompts)
     elif args.no_ref == "niqe":
         scorer = Niqe(NiqeParams.load(args.niqe_params))
+    elif args.no_ref == "uiqm_uciqe":
+        scorer = UiqmUciqe(args.uiqm_weight)
     else:
         scorer = FullReference(args.psnr_weight) if args.target_dir else None
-    psnr, ssim, mc_psnr, mc_ssim, niqe = [], [], [], [], []
+    psnr, ssim, mc_psnr, mc_ssim, niqe, uiqm, uciqe = [], [], [], [], [], [], []
     t0 = time.perf_counter()
     with torch.inference_mode():
         for i, name in enumerate(names):
@@ -131,6 +142,9 @@ def main(argv=None):
             best = r["best_images"]
             if args.no_ref == "niqe":
                 niqe.append(float(r["scores"][r["best"][0]]))          # the chosen sample's score (eval.py:273-275)
+            elif args.no_ref == "uiqm_uciqe":
+                k = int(r["best"][0])                                     # the chosen sample's pair (eval.py:279-280)
+                uiqm.append(float(r["scores"][k])); uciqe.append(float(r["scores2"][k]))
             if tgt is not None:
                 from bem import ops
                 _, p = ops.candidate_finalize(best.contiguous(), tgt.contiguous(), 1, best.shape[2], best.shape[3], False)
@@ -145,7 +159,7 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
-        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, result_dir=result_dir)
+        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, result_dir=result_dir)
     print(f"running time: {time.perf_counter() - t0:.4f} sec")
     with open(os.path.join(result_dir, "result.txt"), "w") as f:
         if args.target_dir:
@@ -159,7 +173,11 @@ def main(argv=None):
         if args.no_ref == "niqe":
             line = f"Best_NIQE: {np.mean(niqe):.4f}"
             print(line); f.write(line + " \n")
-    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, result_dir=result_dir)
+        if args.no_ref == "uiqm_uciqe":
+            for label, vals in (("Best_UIQM", uiqm), ("Best_UCIQE", uciqe)):
+                line = f"{label}: {np.mean(vals):.4f}"
+                print(line); f.write(line + " \n")
+    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, result_dir=result_dir)
 
 
 if __name__ == "__main__":

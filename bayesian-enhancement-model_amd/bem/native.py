@@ -123,6 +123,8 @@ SIGNATURES = {
     "bem_select_scores_f32": [P, P, P, F, I, P, P, P, P, I, I, I64, P],
     "bem_niqe_f32": [P, P, P, P, P, I, P, P, I, P, P, I, P, P, I64, I, I, I, P],
     "bem_niqe_ws_bytes": [I, I, I],
+    "bem_uiqm_uciqe_f32": [P, P, P, P, I, P, P, I, P, P, P, I64, I, I, I, I, P],
+    "bem_uiqm_ws_bytes": [I, I, I, I],
     "bem_mc_mean_f32": [P, P, P, P, I, I, I, I, I, I, I, P],
     "bem_pad_reflect_f32": [P, P, I, I, I, I, I, P],
     "bem_resize_down_f32": [P, P, I, I, I, I, P],
@@ -156,7 +158,7 @@ SIGNATURES = {
     "bem_abi_version": [],
 }
 _RESTYPE = {"bem_last_error": ctypes.c_char_p, "bem_pw_packed_elems": c_int64, "bem_pw_x6_packed_elems": c_int64, "bem_selective_scan_bwd_ws_elems": c_int64,
-            "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64,
+            "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64, "bem_uiqm_ws_bytes": c_int64,
             "bem_ss2d_scan_n_bwd_ws_elems": c_int64, "bem_fusion_head_bwd_ws_elems": c_int64}
 
 _lib = None

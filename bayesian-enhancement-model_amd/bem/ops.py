@@ -1152,6 +1152,124 @@ def niqe(final, params):
     return out
 
 
+# UIQM / UCIQE (basicsr/metrics/uciqe_uiqm.py as Enhancement/eval.py:255-260 calls them).  Host-built tables, kept on the device: per
+# (source length, target length) Pillow's fixed-point BICUBIC coefficients (Resample.c), and OpenCV 4.x's 8-bit RGB -> Lab tables
+# (color_lab.cpp, RGB2Lab_b).
+UIQM_WIDTH = 256
+UIQM_WINDOW = 10
+_uiqm_cache = {}
+
+
+def _pil_bicubic(x):
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_resize_table(n_in, n_out):
+    """Pillow's BICUBIC resample of one axis, n_in -> n_out, in its 8-bit form (precompute_coeffs + normalize_coeffs_8bpc):
+    bounds (n_out, 2) int32 = first source index and tap count, weights (n_out, K) int32 with 22 fractional bits, zero past the taps."""
+    import math
+    import numpy as np
+    scale = n_in / n_out
+    fscale = max(scale, 1.0)
+    support = 2.0 * fscale
+    K = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((n_out, 2), np.int32)
+    kk = np.zeros((n_out, K), np.int32)
+    for o in range(n_out):
+        center = (o + 0.5) * scale
+        x0 = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), n_in) - x0
+        ss = 1.0 / fscale
+        ws = [_pil_bicubic((x + x0 - center + 0.5) * ss) for x in range(n)]
+        tot = 0.0
+        for v in ws:
+            tot += v
+        for x, v in enumerate(ws):
+            v = v / tot if tot != 0.0 else v
+            kk[o, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
+        bounds[o] = (x0, n)
+    return bounds, kk
+
+
+def lab_tables():
+    """OpenCV 4.x RGB2Lab_b tables as one int32 vector: sRGB gamma x 255 x 8 (256 entries), 2^15 (x < 0.008856 ? 7.787 x + 16/116 : cbrt x)
+    at x = i / (255 x 8) (3072), and the fixed-point matrix cvRound(4096 sRGB2XYZ_D65[i][j] / D65white[i]) (9, row-major, R G B order)."""
+    import numpy as np
+    x = np.arange(256) / 255.0
+    gamma = np.rint(np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4) * 255.0 * 8)
+    t = np.arange(3072) / (255.0 * 8)
+    cbrt = np.rint((1 << 15) * np.where(t < 0.008856, t * 7.787 + 16.0 / 116.0, np.cbrt(t)))
+    m = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
+    coef = np.rint(4096 * m / np.array([0.950456, 1.0, 1.088754])[:, None])
+    return np.concatenate([gamma, cbrt, coef.ravel()]).astype(np.int32)
+
+
+def uiqm_resized_rows(h, w):
+    """eval.py:257: the resized image is (int(256 / w * h), 256)."""
+    return int(UIQM_WIDTH / w * h)
+
+
+def _uiqm_tables(device, h, w, Hr):
+    dev = str(device)
+    if (dev, "lab") not in _uiqm_cache:
+        _uiqm_cache[(dev, "lab")] = torch.from_numpy(lab_tables()).to(device)
+    rs = []
+    for n_in, n_out in ((w, UIQM_WIDTH), (h, Hr)):
+        k = (dev, "resize", n_in, n_out)
+        if k not in _uiqm_cache:
+            b, kk = pil_resize_table(n_in, n_out)
+            _uiqm_cache[k] = (torch.from_numpy(b).to(device), torch.from_numpy(kk).to(device))
+        rs.append(_uiqm_cache[k])
+    return _uiqm_cache[(dev, "lab")], rs[0], rs[1]
+
+
+def uiqm_uciqe(final, debug=False):
+    """UIQM and UCIQE per candidate: final (Bn,3,h,w) f32 in [0,1] (RGB, clipped, GT-mean rescaled: BEMPipeline's ``final``) ->
+    (uiqm (Bn) f64, uciqe (Bn) f64) on the device, higher is better.  UIQM is computed on the image resized to width 256 and needs
+    int(256 / w * h) >= 10 rows; a candidate with a channel without Sobel edges (a flat plane) has NaN UIQM.
+    debug=True also returns a dict of device views into the workspace, valid until the next call on this stream: ``parts`` (Bn, 8) f64
+    (uicm, uism, uiconm, uiqm, var_chr, con_lum, aver_sat, uciqe), ``resized`` (Bn,3,Hr,256) u8 and ``lab`` (Bn,3,h,w) u8."""
+    _chk(final, "final")
+    if final.dim() != 4 or final.shape[1] != 3:
+        raise ValueError("uiqm_uciqe: final must be (Bn,3,h,w)")
+    Bn, _, h, w = final.shape
+    if h < 1 or w < 1:
+        raise ValueError("uiqm_uciqe: empty images")
+    Hr = uiqm_resized_rows(h, w)
+    if Hr < UIQM_WINDOW:
+        raise ValueError(f"uiqm_uciqe: a {h} x {w} image resizes to {Hr} x {UIQM_WIDTH} (int(256 * h / w) rows); UIQM needs at least "
+                         f"{UIQM_WINDOW} rows, i.e. h / w >= {UIQM_WINDOW / UIQM_WIDTH:.4f}")
+    dev = final.device
+    u1 = torch.empty(Bn, device=dev, dtype=torch.float64)
+    u2 = torch.empty(Bn, device=dev, dtype=torch.float64)
+    if Bn == 0:
+        return (u1, u2, None) if debug else (u1, u2)
+    tab, (bh, kh), (bv, kv) = _uiqm_tables(dev, h, w, Hr)
+    nbytes = int(lib().bem_uiqm_ws_bytes(Bn, h, w, Hr))
+    key = (str(dev), "ws", torch.cuda.current_stream(dev).cuda_stream)
+    ws = _uiqm_cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _uiqm_cache[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(lib().bem_uiqm_uciqe_f32(_p(final), _p(tab), _p(bh), _p(kh), kh.shape[1], _p(bv), _p(kv), kv.shape[1], _p(u1), _p(u2), _p(ws),
+                                   ws.numel(), Bn, h, w, Hr, _stream()), "uiqm_uciqe")
+    if not debug:
+        return u1, u2
+    up = lambda n: (n + 255) // 256 * 256
+    o_rs = up(Bn * 64)
+    o_lab = o_rs + up(Bn * 3 * Hr * UIQM_WIDTH)
+    views = dict(parts=ws[:Bn * 64].view(torch.float64).reshape(Bn, 8),
+                 resized=ws[o_rs:o_rs + Bn * 3 * Hr * UIQM_WIDTH].reshape(Bn, 3, Hr, UIQM_WIDTH),
+                 lab=ws[o_lab:o_lab + Bn * 3 * h * w].reshape(Bn, 3, h, w))
+    return u1, u2, views
+
+
 # --------------------------------------------------------------------------- training step ----
 # Backward kernels + optimizer (SURVEY.md section 8a row A10).  Parameter-gradient outputs (dw, dbias, dgamma, ...) are
 # ACCUMULATED INTO: they are views of the parameters' .grad buffers.

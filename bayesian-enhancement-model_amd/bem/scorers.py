@@ -13,6 +13,8 @@ A scorer maps the finished candidates of a batch -- ``final`` (B*N,3,h,w) in [0,
                                its VALUES are parity-unpinned, the ordering logic applied to them is the reference's.
   Niqe(params)                 NIQE (basicsr/metrics/niqe.py, eval.py:253), rule ``index(min)``; ops.niqe on the device with the
                                pristine-model statistics of a NiqeParams (niqe_pris_params.npz from a BasicSR install).
+  UiqmUciqe(uiqm_weight)       UIQM and UCIQE (basicsr/metrics/uciqe_uiqm.py, eval.py:255-260), rule ``index(max(w * uiqm / max(uiqm)
+                               + (1 - w) * uciqe / max(uciqe)))`` (eval.py:277-278); ops.uiqm_uciqe on the device.
 All scores stay on the device; ``select`` runs bem_select_scores_f32 (first index on ties, float64 comparisons)."""
 from __future__ import annotations
 
@@ -113,3 +115,21 @@ class Niqe(NoReference):
     def __init__(self, params: NiqeParams):
         self.params = params
         super().__init__(lambda final: ops.niqe(final.contiguous(), params), "min")
+
+
+class UiqmUciqe(Scorer):
+    """eval.py:255-260,276-280: UIQM (s1) and UCIQE (s2) of every candidate, the first maximum of w * s1 / max(s1) + (1 - w) * s2 / max(s2)
+    wins (bem_select_scores_f32 rule 0).  Both are always computed: the driver reports the chosen sample's pair.  The selection compares
+    the scores as float32, like every scorer here; ``ops.uiqm_uciqe`` gives the float64 values.
+    NaN (UIQM of a candidate with a flat channel): max() skips NaN scores and a NaN weighted score never wins, so such a candidate is
+    chosen only when every candidate's score is NaN (then the first).  The reference's Python max() differs when the FIRST candidate is
+    NaN: it then keeps index 0."""
+
+    rule = "weighted"
+
+    def __init__(self, uiqm_weight: float = 1.0):
+        self.weight = float(uiqm_weight)
+
+    def scores(self, final, targets, samples_per_image, psnr=None):
+        u1, u2 = ops.uiqm_uciqe(final.contiguous())
+        return u1.float().contiguous(), u2.float().contiguous()

@@ -366,6 +366,22 @@ int bem_niqe_f32(const float* final, const double* mu_pris, const double* cov_pr
                  int64_t ws_bytes, int Bn, int h, int w, void* stream);
 int64_t bem_niqe_ws_bytes(int Bn, int h, int w);   /* 0 for h or w < 96 */
 
+/* UIQM and UCIQE of Enhancement/eval.py:255-260 (getUIQM / getUCIQE of basicsr/metrics/uciqe_uiqm.py) per candidate, the no-reference scores
+ * that eval.py:276-280 weighs.  final (Bn,3,h,w) f32 in [0,1], RGB as BEMPipeline.candidates returns it.  u8 = img_as_ubyte(final) (rint(255 x),
+ * half to even).  UIQM on Image.fromarray(u8).resize((256, Hr)), Hr = int(256 / w * h) >= 10: Pillow's 8-bit BICUBIC, horizontal pass first,
+ * uint8 between the passes; rs_bh (256 x 2: first source column, tap count) and rs_kh (256 x kh) are the fixed-point (22-bit) coefficients
+ * of the w -> 256 pass, rs_bv / rs_kv (Hr x 2, Hr x kv) of the h -> Hr pass.  UICM (alpha-trimmed means from 511- and 1021-bin histograms,
+ * the trimmed sum in f32 in sorted order), UISM (Sobel, mode reflect; EME over 10 x 10 blocks whose last row / column absorbs the remainder,
+ * f32 terms summed in f32; weights 0.299, 0.587, 0.144), UIConM (10 x 10 x 3 blocks of the cropped image, f64); the UIQM total is rounded
+ * as NumPy 2 does (f32 from the c2 * uism term on).  UCIQE on u8 after OpenCV's 8-bit RGB2Lab_b: lab_tab = sRGB gamma x 2040 (256 ints),
+ * 2^15 f(i / 2040) (3072), the 3 x 3 matrix cvRound(4096 sRGB2XYZ_D65 / D65white) (9).  A plane without Sobel edges makes UISM and UIQM
+ * NaN.  uiqm, uciqe (Bn) f64 out.  ws: bem_uiqm_ws_bytes(Bn, h, w, Hr) bytes; it starts with parts (Bn x 8 f64: uicm, uism, uiconm, uiqm,
+ * var_chr, con_lum, aver_sat, uciqe), then the resized image (Bn,3,Hr,256) u8 and the Lab image (Bn,3,h,w) u8, each region aligned to
+ * 256 bytes. */
+int bem_uiqm_uciqe_f32(const float* final, const int* lab_tab, const int* rs_bh, const int* rs_kh, int kh, const int* rs_bv, const int* rs_kv,
+                       int kv, double* uiqm, double* uciqe, void* ws, int64_t ws_bytes, int Bn, int h, int w, int Hr, void* stream);
+int64_t bem_uiqm_ws_bytes(int Bn, int h, int w, int Hr);   /* 0 for Hr < 10 */
+
 /* Monte-Carlo mean of eval.py:224-225,308-314: out (B,3,h,w) = clamp(mean_n clamp(pred[b*N+n][:, :h, :w], 0, 1), 0, 1), with gt_mean scaled
  * by mean(gray(target)) / mean(gray(out)) (cv2 BGR2GRAY weights on the stored channel order) and clipped.  pred (B*N,3,Hp,Wp);
  * ws: 2 B doubles (zeroed by the call) when gt_mean. */
