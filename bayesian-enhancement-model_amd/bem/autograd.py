@@ -62,7 +62,7 @@ def grad_of(p: torch.Tensor) -> torch.Tensor:
 
 def _pack(holder, key, srcs, make):
     """pack_pw_weight of ``make()`` (an (M,K) matrix), cached on ``holder``."""
-    return _derived(holder).get(key, srcs, lambda: ops.pack_pw_weight(make() if ops.USE_X6 else make().contiguous()))
+    return _derived(holder).get(key, srcs, lambda: ops.pack_pw_weight(make()))
 
 
 def _w2d(w):
@@ -267,40 +267,9 @@ def _transpose_into(src, dst, dst_c0):
 class VSSBlockFn(Function):
     @staticmethod
     def forward(ctx, x, blk, *params):
-        from .modules import _out_features
         x = x.contiguous()
-        op, mlp = blk.op, blk.mlp
-        B, C, H, W = x.shape
-        Ci, R, L = op.d_inner, op.dt_rank, H * W
-        n1, n2, on = blk.norm, blk.norm2, op.out_norm
-        Wp, b = op.in_proj.gemm_weights(B)
-        t = ops.pw_gemm(x, Wp, Ci, ln=(n1.weight.detach(), n1.bias.detach()), ln_eps=n1.eps, bias=b)
-        cw, cb = op.conv2d.dw_weights(B)
-        xc = ops.dwconv3x3(t, cw, cb, mode=1)
-        wall, dtw, dtb, A, Ds = op._scan_params()
-        N = op.d_state
-        M = R + 2 * N                                    # x_dbl rows per direction
-        xd = ops.pw_gemm(xc, wall, 4 * M)
-        xd1 = ops.transpose_plane_slice(xd, 2 * M, 2 * M)
-        xcT = None
-        if N > 1:
-            xcT = ops.transpose_planes(xc)
-            y0, y1T = ops.ss2d_scan_n(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L), dtw, dtb, A, Ds)
-            y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1T.view(B, Ci, W, H))
-        elif ops.ss2d_scan_rm_supported(H, W, R):
-            y0, y1 = ops.ss2d_scan_rm(xc, xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L), dtw, dtb, A, Ds)
-        else:
-            xcT = ops.transpose_planes(xc)
-            y0, y1T = ops.ss2d_scan(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L), dtw, dtb, A, Ds)
-            y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1T.view(B, Ci, W, H))
-        Wp, b = op.out_proj.gemm_weights(B)
-        x2 = ops.pw_gemm(y0, Wp, _out_features(op.out_proj), x2=y1, in_mode=1, ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
-        Wp, b = mlp.project_in.gemm_weights(B)
-        t2 = ops.pw_gemm(x2, Wp, _out_features(mlp.project_in), ln=(n2.weight.detach(), n2.bias.detach()), ln_eps=n2.eps, bias=b)
-        dww, dwb = mlp.dwconv.dw_weights(B)
-        g = ops.dwconv3x3(t2, dww, dwb, mode=2)
-        Wp, b = mlp.project_out.gemm_weights(B)
-        out = ops.pw_gemm(g, Wp, _out_features(mlp.project_out), bias=b, res=x2)
+        x2, (t, xc, xd, xd1, y0, y1) = blk.op.forward_fused(x, blk.norm, keep=True)
+        out, t2, g = blk.mlp.chain(x2, blk.norm2)
         ctx.blk = blk
         ctx.save_for_backward(x, t, xc, xd, xd1, y0, y1, x2, t2, g)
         return out

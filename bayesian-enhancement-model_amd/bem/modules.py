@@ -319,8 +319,8 @@ class _BayesBase(nn.Module):
             ew = ctx.eps[self.module_path + ".weight"].contiguous()
             if self.bias:
                 eb = ctx.eps[self.module_path + ".bias"].contiguous()
-        rec = {"mk": packed_mk if (packed_mk is not None and ops.USE_X6) else None, "b": None}
-        if packed_mk is not None and ops.USE_X6:
+        rec = {"mk": packed_mk, "b": None}
+        if packed_mk is not None:
             # GEMM weights go straight into operand order (same Philox stream ids, same values as sample-then-pack)
             # sigma = log1p(exp(rho)) once per weight version (one launch of the sampler with mu = 0, eps = 1), not once per sample
             w = ops.bnn_sample_packed(self.mu_weight.detach(), self._sigma(), ns, packed_mk[0], packed_mk[1], ew, ctx.seed, ctx.next_stream(), sigma_given=True, stream_add=ctx.epoch_dev)
@@ -333,6 +333,17 @@ class _BayesBase(nn.Module):
             rec["b"] = ctx.counter - ctx.counter0
         self.__dict__["_eval_draw"] = rec            # which streams of the forward this leaf drew from, and in which form (EvalSampleBank)
         return w, b, ns
+
+    def gemm_weights(self, B):
+        """Pointwise interface of a 1x1 conv / Linear2d leaf: (x6-packed weights (nsets, packed(M, K)), bias); (M, K) = self._mk."""
+        if self.deterministic or self.training:
+            w, b, ns = self._sampled(B)
+            bw = self.__dict__.get("_bank_wp")
+            if self.training and bw is not None and bw[0] is self._sample_owner and not self.deterministic:
+                return bw[1], b                      # packed by the bank's one launch for this forward
+            return ops.pack_pw_weight(w.reshape((ns,) + self._mk).contiguous()), b
+        Wp, b, _ = self._sampled(B, self._mk)
+        return Wp, b
 
 
 class BayesBank:
@@ -411,20 +422,19 @@ class BayesBank:
         # the x6 operand forms of every 1x1 weight sample -- forward (M, K) and transposed (K, M, for the input-gradient GEMM) -- by ONE more
         # launch (bem_pack_pw_weight_x6_jobs) instead of two small packing launches per layer and iteration
         jobs, jblk, poff, self.packs = [], [], 0, []
-        if ops.USE_X6:
-            for (m, kind, mu, rho), r in zip(items, rows):
-                if kind != "weight" or not (getattr(m, "_is_pw", False) or isinstance(m, Linear2dReparameterization)):
-                    continue
-                M, K = mu.shape[0], mu.shape[1]
-                src = self.w.data_ptr() + 4 * r[4]
-                ent = []
-                for (Mj, Kj, rs, cs) in ((M, K, K, 1), (K, M, 1, K)):
-                    it = ((Mj + 31) // 32) * ((Kj + 15) // 16) * 64
-                    jobs.append([src, poff, Mj | (Kj << 32), rs, cs, it, 0, 0])
-                    jblk += [[len(jobs) - 1, b] for b in range((it + 255) // 256)]
-                    ent.append((poff, ops.packed_elems(Mj, Kj, True), (Mj, Kj)))
-                    poff += ops.packed_elems(Mj, Kj, True)
-                self.packs.append((m, ent))
+        for (m, kind, mu, rho), r in zip(items, rows):
+            if kind != "weight" or not (getattr(m, "_is_pw", False) or isinstance(m, Linear2dReparameterization)):
+                continue
+            M, K = mu.shape[0], mu.shape[1]
+            src = self.w.data_ptr() + 4 * r[4]
+            ent = []
+            for (Mj, Kj, rs, cs) in ((M, K, K, 1), (K, M, 1, K)):
+                it = ((Mj + 31) // 32) * ((Kj + 15) // 16) * 64
+                jobs.append([src, poff, Mj | (Kj << 32), rs, cs, it, 0, 0])
+                jblk += [[len(jobs) - 1, b] for b in range((it + 255) // 256)]
+                ent.append((poff, ops.packed_elems(Mj, Kj, True), (Mj, Kj)))
+                poff += ops.packed_elems(Mj, Kj, True)
+            self.packs.append((m, ent))
         if jobs:
             self.parena = torch.empty(poff, device=dev, dtype=torch.float32)
             self.jobs = torch.tensor(jobs, dtype=torch.int64).to(dev)
@@ -483,7 +493,7 @@ class EvalSampleBank:
         self.sig = None
 
     def usable(self, ctx):
-        return (ctx is not None and ctx.eps is None and ctx.epoch_dev is None and bool(self.leaves) and ops.USE_X6
+        return (ctx is not None and ctx.eps is None and ctx.epoch_dev is None and bool(self.leaves)
                 and all(not m.training and not m.deterministic and "_eval_draw" in m.__dict__ for m in self.leaves))
 
     def _signature(self, ns):
@@ -549,7 +559,7 @@ class EvalSampleBank:
 
     def take(self, leaf, packed_mk, ns):
         mk, w, b = self.views[id(leaf)]
-        if mk != (packed_mk if (packed_mk is not None and ops.USE_X6) else None):
+        if mk != packed_mk:
             raise BemNativeError("EvalSampleBank: a leaf asked for its weights in another form than in the recorded forward")
         return w, b, ns
 
@@ -561,6 +571,7 @@ class Conv2dReparameterization(_BayesBase):
         self._init_common(sigma_init, decay, bias)
         ks = kernel_size if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
         self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self._mk = (out_channels, in_channels)
         self.stride, self.padding, self.dilation, self.groups = stride, padding, dilation, groups
         shp = (out_channels, in_channels // groups, ks[0], ks[1])
         self.mu_weight = nn.Parameter(torch.empty(shp))
@@ -579,18 +590,7 @@ class Conv2dReparameterization(_BayesBase):
         if not (self._is_dw or self._is_pw):
             raise NotImplementedError("Bayesian conv: only 1x1 dense and 3x3 depthwise occur on the BEM path")
 
-    # pointwise interface
-    def gemm_weights(self, B):
-        if self.deterministic or not ops.USE_X6 or self.training:
-            w, b, ns = self._sampled(B)
-            bw = self.__dict__.get("_bank_wp")
-            if self.training and bw is not None and bw[0] is self._sample_owner and not self.deterministic:
-                return bw[1], b                      # packed by the bank's one launch for this forward
-            return ops.pack_pw_weight(w.reshape(ns, self.out_channels, self.in_channels).contiguous()), b
-        Wp, b, _ = self._sampled(B, (self.out_channels, self.in_channels))
-        return Wp, b
-
-    # depthwise interface
+    # depthwise interface (the pointwise one, gemm_weights, is _BayesBase's)
     def dw_weights(self, B):
         w, b, ns = self._sampled(B)
         return (w if ns > 1 else w[0]), (b if (b is None or ns > 1) else b[0])
@@ -601,6 +601,7 @@ class Linear2dReparameterization(_BayesBase):
         super().__init__()
         self._init_common(sigma_init, decay, bias)
         self.in_features, self.out_features = in_features, out_features
+        self._mk = (out_features, in_features)
         self.mu_weight = nn.Parameter(torch.empty(out_features, in_features))
         self.rho_weight = nn.Parameter(torch.empty(out_features, in_features))
         if bias:
@@ -612,16 +613,6 @@ class Linear2dReparameterization(_BayesBase):
             self.mu_bias.data.zero_()
             self.rho_bias.data.fill_(self._rho_init())
         self._register_priors()
-
-    def gemm_weights(self, B):
-        if self.deterministic or not ops.USE_X6 or self.training:
-            w, b, ns = self._sampled(B)
-            bw = self.__dict__.get("_bank_wp")
-            if self.training and bw is not None and bw[0] is self._sample_owner and not self.deterministic:
-                return bw[1], b
-            return ops.pack_pw_weight(w.contiguous()), b
-        Wp, b, _ = self._sampled(B, (self.out_features, self.in_features))
-        return Wp, b
 
 
 # ------------------------------------------------------------------------------------------------
@@ -660,13 +651,19 @@ class gdMlp(nn.Module):
                         None if po.bias is None else po.bias.detach().contiguous())
             Wg, bg, w10, Wo, bo = self._cache.get("gdmlp_x6", [t for t in (pi.weight, pi.bias, dw.weight, dw.bias, po.weight, po.bias) if t is not None], prep)
             return ops.gdmlp_x6(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wg, bg, w10, Wo, bo, Hd)
+        return self.chain(x, norm)[0]
+
+    def chain(self, x, norm: LayerNorm2d):
+        """The branch as three kernels; returns (out, t2, g): the output and the two intermediates VSSBlockFn.backward needs,
+        t2 = project_in(LN(x)) and g = GELU(h1) * h2."""
+        B = x.shape[0]
         Wp, b = self.project_in.gemm_weights(B)
-        t = ops.pw_gemm(x, Wp, _out_features(self.project_in), ln=(norm.weight.detach(), norm.bias.detach()),
-                        ln_eps=norm.eps, bias=b)
+        t2 = ops.pw_gemm(x, Wp, _out_features(self.project_in), ln=(norm.weight.detach(), norm.bias.detach()),
+                         ln_eps=norm.eps, bias=b)
         w, b = self.dwconv.dw_weights(B)
-        g = ops.dwconv3x3(t, w, b, mode=2)
+        g = ops.dwconv3x3(t2, w, b, mode=2)
         Wp, b = self.project_out.gemm_weights(B)
-        return ops.pw_gemm(g, Wp, _out_features(self.project_out), bias=b, res=x)
+        return ops.pw_gemm(g, Wp, _out_features(self.project_out), bias=b, res=x), t2, g
 
 
 SS2D_MAX_D_STATE = 16       # bem_ss2d_scan_n_f32 / bem_ss2d_scan_n_bwd_f32
@@ -721,72 +718,49 @@ class SS2D(nn.Module):
                     self.Ds.detach().float().contiguous())
         return self._cache.get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
 
-    def forward_fused(self, x, norm: LayerNorm2d):
-        """x + out_proj(out_norm(merge(scan(SiLU(dw(in_proj(LN(x))))))))  (vmamba.py:700-716 + 547-698)."""
-        if self.d_state > 1:
-            return self._forward_fused_n(x, norm)
+    def forward_fused(self, x, norm: LayerNorm2d, keep=False):
+        """x + out_proj(out_norm(y0 + y1)), (y0, y1) = scan(SiLU(dw(in_proj(LN(x)))))  (vmamba.py:700-716 + 547-698), for every d_state.
+        keep=True (the training forward, VSSBlockFn) returns (out, (t, xc, xd, xd1, y0, y1)): the intermediates the backward
+        reads, y0 / y1 row-major (B, Ci, H, W)."""
         B, C, H, W = x.shape
-        Ci, R, L = self.d_inner, self.dt_rank, H * W
+        Ci, R, N, L = self.d_inner, self.dt_rank, self.d_state, H * W
+        M = R + 2 * N                                    # x_dbl rows per direction: [dt_0..dt_{R-1} | B_0..B_{N-1} | C_0..C_{N-1}]
         wall, dtw, dtb, A, Ds = self._scan_params()
-        front = SCAN_RM and ops.ss2d_scan_rm_supported(H, W, R) and ops.ss2d_front_supported(C, 4 * (R + 2)) and Ci == C \
-            and type(self.in_proj) is Linear2d and type(self.conv2d) is DwConv2d and ops.USE_X6
+        lnw, lnb = norm.weight.detach(), norm.bias.detach()
+        # row-major scan (d_state = 1): no transposed copy of xc, y1 comes back row-major (the column orientation goes through LDS)
+        rm = N == 1 and SCAN_RM and ops.ss2d_scan_rm_supported(H, W, R)
+        # LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel (bem_ss2d_front_x6_f32).  The in_proj output t stays in
+        # LDS, so never with keep.  At d_state = 1 it is taken only ahead of the row-major scan: it was wired into that branch
+        # alone when it was added, no reason for leaving the transposed-plane scan out is recorded; d_state > 1 has no such condition.
+        front = not keep and (rm or N > 1) and ops.ss2d_front_supported(C, 4 * M) and Ci == C \
+            and type(self.in_proj) is Linear2d and type(self.conv2d) is DwConv2d
+        Wp, b = self.in_proj.gemm_weights(B)
+        w, bw = self.conv2d.dw_weights(B)
+        t = None
         if front:
-            # LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel (bem_ss2d_front_x6_f32): the in_proj output stays in LDS
-            Wpi, bi = self.in_proj.gemm_weights(B)
-            w, bw = self.conv2d.dw_weights(B)
-            xc, xd = ops.ss2d_front(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wpi, bi, w, bw, wall, 4 * (R + 2))
+            xc, xd = ops.ss2d_front(x, lnw, lnb, norm.eps, Wp, b, w, bw, wall, 4 * M)
         else:
-            Wp, b = self.in_proj.gemm_weights(B)
-            t = ops.pw_gemm(x, Wp, Ci, ln=(norm.weight.detach(), norm.bias.detach()), ln_eps=norm.eps, bias=b)
-            w, b = self.conv2d.dw_weights(B)
-            xc = ops.dwconv3x3(t, w, b, mode=1)
+            t = ops.pw_gemm(x, Wp, Ci, ln=(lnw, lnb), ln_eps=norm.eps, bias=b)
+            xc = ops.dwconv3x3(t, w, bw, mode=1)
+            xd = ops.pw_gemm(xc, wall, 4 * M)            # (B, 4M, H, W), rows [dir 0 | dir 2 | dir 1 | dir 3]
+        # x_dbl of the column-major directions = the row-major GEMM's rows in transposed pixel order: 2M planes to transpose
+        # instead of a second GEMM pass over the C planes of xcT
+        xd1 = ops.transpose_plane_slice(xd, 2 * M, 2 * M)                             # (B, 2M, W, H)
+        xd0v, xd1v = xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L)
+        if rm:
+            y0, y1 = ops.ss2d_scan_rm(xc, xd0v, xd1v, dtw, dtb, A, Ds)
+        else:
+            x0, x1 = xc.view(B, Ci, L), ops.transpose_planes(xc).view(B, Ci, L)
+            if N > 1:
+                y0, y1 = ops.ss2d_scan_n(x0, x1, xd0v, xd1v, dtw, dtb, A, Ds)
+            else:
+                y0, y1 = ops.ss2d_scan(x0, x1, xd0v, xd1v, dtw, dtb, A, Ds)
+            y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1.view(B, Ci, W, H))
         Wp, b = self.out_proj.gemm_weights(B)
         on = self.out_norm
-        if SCAN_RM and ops.ss2d_scan_rm_supported(H, W, R):
-            # row-major scan: no transposed copy of xc, y1 comes back row-major (the column orientation goes through LDS)
-            if not front:
-                xd = ops.pw_gemm(xc, wall, 4 * (R + 2))
-            xd1 = ops.transpose_plane_slice(xd, 2 * (R + 2), 2 * (R + 2))
-            y0, y1 = ops.ss2d_scan_rm(xc, xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L), dtw, dtb, A, Ds)
-            return ops.pw_gemm(y0, Wp, _out_features(self.out_proj), x2=y1, in_mode=1,
-                               ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
-        xcT = ops.transpose_planes(xc)
-        # x_dbl of the column-major directions = the row-major GEMM's rows in transposed pixel order: 2 (R+2) planes to
-        # transpose instead of a second GEMM pass over the C planes of xcT
-        xd = ops.pw_gemm(xc, wall, 4 * (R + 2))                                   # (B, 4(R+2), H, W)
-        xd1 = ops.transpose_plane_slice(xd, 2 * (R + 2), 2 * (R + 2))             # (B, 2(R+2), W, H)
-        y0, y1 = ops.ss2d_scan(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, R + 2, L)[:, :2], xd1.view(B, 2, R + 2, L),
-                               dtw, dtb, A, Ds)
-        y1r = ops.transpose_planes(y1.view(B, Ci, W, H))
-        return ops.pw_gemm(y0.view(B, Ci, H, W), Wp, _out_features(self.out_proj), x2=y1r, in_mode=1,
-                           ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
-
-    def _forward_fused_n(self, x, norm: LayerNorm2d):
-        """forward_fused for d_state N > 1: x_dbl has R + 2N rows per direction and the scan is bem_ss2d_scan_n_f32."""
-        B, C, H, W = x.shape
-        Ci, L, M = self.d_inner, H * W, self.dt_rank + 2 * self.d_state
-        wall, dtw, dtb, A, Ds = self._scan_params()
-        front = ops.ss2d_front_supported(C, 4 * M) and Ci == C and type(self.in_proj) is Linear2d and type(self.conv2d) is DwConv2d \
-            and ops.USE_X6
-        if front:
-            Wpi, bi = self.in_proj.gemm_weights(B)
-            w, bw = self.conv2d.dw_weights(B)
-            xc, xd = ops.ss2d_front(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wpi, bi, w, bw, wall, 4 * M)
-        else:
-            Wp, b = self.in_proj.gemm_weights(B)
-            t = ops.pw_gemm(x, Wp, Ci, ln=(norm.weight.detach(), norm.bias.detach()), ln_eps=norm.eps, bias=b)
-            w, b = self.conv2d.dw_weights(B)
-            xc = ops.dwconv3x3(t, w, b, mode=1)
-            xd = ops.pw_gemm(xc, wall, 4 * M)                                     # (B, 4M, H, W): [dir 0 | dir 2 | dir 1 | dir 3]
-        xcT = ops.transpose_planes(xc)
-        xd1 = ops.transpose_plane_slice(xd, 2 * M, 2 * M)                         # (B, 2M, W, H)
-        y0, y1 = ops.ss2d_scan_n(xc.view(B, Ci, L), xcT.view(B, Ci, L), xd.view(B, 4, M, L)[:, :2], xd1.view(B, 2, M, L),
-                                 dtw, dtb, A, Ds)
-        y1r = ops.transpose_planes(y1.view(B, Ci, W, H))
-        Wp, b = self.out_proj.gemm_weights(B)
-        on = self.out_norm
-        return ops.pw_gemm(y0.view(B, Ci, H, W), Wp, _out_features(self.out_proj), x2=y1r, in_mode=1,
-                           ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
+        out = ops.pw_gemm(y0, Wp, _out_features(self.out_proj), x2=y1, in_mode=1,
+                          ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
+        return (out, (t, xc, xd, xd1, y0, y1)) if keep else out
 
     def forward(self, x):
         raise BemNativeError("SS2D runs fused with its VSSBlock (norm prologue + residual epilogue); call the block")

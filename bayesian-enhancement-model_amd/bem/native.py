@@ -56,7 +56,6 @@ SIGNATURES = {
     "bem_selective_scan_bwd_f32": [P] * 16 + [I, I, I, I, I, I, P],
     "bem_cross_scan_f32": [P, P, I, I, I, I, P],
     "bem_cross_merge_f32": [P, P, I, I, I, I, P],
-    "bem_ss2d_scan_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "bem_ss2d_scan_strided_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I64, I64, P],
     "bem_ss2d_scan_rm_supported": [I, I, I],
     "bem_ss2d_scan_rm_f32": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I64, I64, P],

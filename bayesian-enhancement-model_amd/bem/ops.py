@@ -101,6 +101,18 @@ def cross_merge(ys):
 
 
 # --------------------------------------------------------------------------- fused SS2D -------
+def _xd_bstrides(name, xd0, xd1, B, rows, L):
+    """Batch strides of the x_dbl operands of the scans: (B,2,rows,L) float32, contiguous or channel slices of a wider buffer."""
+    bs = []
+    for n, t in (("xd0", xd0), ("xd1", xd1)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
+        if t.stride()[1:] != (rows * L, L, 1) or (B > 1 and (t.stride(0) < 2 * rows * L or (L % 4 == 0 and t.stride(0) % 4))):
+            raise ValueError(f"{name}: {n}: only the batch stride may differ from a contiguous (B,2,R+2N,L) tensor")
+        bs.append(t.stride(0) if B > 1 else 0)
+    return bs
+
+
 def ss2d_scan(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
     """xd0 / xd1 (B,2,R+2,L): contiguous, or channel slices of a wider (B,*,L) buffer (batch stride taken from the view)."""
     for n, t in (("x0", x0), ("x1", x1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
@@ -111,13 +123,7 @@ def ss2d_scan(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
         raise ValueError(f"ss2d_scan shapes: x {tuple(x0.shape)}/{tuple(x1.shape)} xd {tuple(xd0.shape)}/{tuple(xd1.shape)} R={R}")
     if dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C:
         raise ValueError("ss2d_scan parameter shapes")
-    bs = []
-    for n, t in (("xd0", xd0), ("xd1", xd1)):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
-        if t.stride()[1:] != ((R + 2) * L, L, 1) or (B > 1 and (t.stride(0) < 2 * (R + 2) * L or (L % 4 == 0 and t.stride(0) % 4))):
-            raise ValueError(f"{n}: only the batch stride may differ from a contiguous (B,2,R+2,L) tensor")
-        bs.append(t.stride(0) if B > 1 else 0)
+    bs = _xd_bstrides("ss2d_scan", xd0, xd1, B, R + 2, L)
     y0 = torch.empty_like(x0)
     y1 = torch.empty_like(x0)
     check(lib().bem_ss2d_scan_strided_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1),
@@ -127,17 +133,6 @@ def ss2d_scan(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
 
 def ss2d_scan_n_supported(N):
     return bool(lib().bem_ss2d_scan_n_supported(int(N)))
-
-
-def _xd_bstrides(name, xd0, xd1, B, rows, L):
-    bs = []
-    for n, t in (("xd0", xd0), ("xd1", xd1)):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
-        if t.stride()[1:] != (rows * L, L, 1) or (B > 1 and (t.stride(0) < 2 * rows * L or (L % 4 == 0 and t.stride(0) % 4))):
-            raise ValueError(f"{name}: {n}: only the batch stride may differ from a contiguous (B,2,R+2N,L) tensor")
-        bs.append(t.stride(0) if B > 1 else 0)
-    return bs
 
 
 def ss2d_scan_n(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
@@ -179,13 +174,7 @@ def ss2d_scan_rm(x, xd0, xd1, dtw, dtb, A, Ds):
         raise ValueError(f"ss2d_scan_rm: plane {H}x{W} / dt_rank {R} not supported")
     if xd0.shape != (B, 2, R + 2, L) or xd1.shape != xd0.shape or dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C:
         raise ValueError("ss2d_scan_rm: shapes")
-    bs = []
-    for n, t in (("xd0", xd0), ("xd1", xd1)):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
-        if t.stride()[1:] != ((R + 2) * L, L, 1) or (B > 1 and (t.stride(0) < 2 * (R + 2) * L or (L % 4 == 0 and t.stride(0) % 4))):
-            raise ValueError(f"{n}: only the batch stride may differ from a contiguous (B,2,R+2,L) tensor")
-        bs.append(t.stride(0) if B > 1 else 0)
+    bs = _xd_bstrides("ss2d_scan_rm", xd0, xd1, B, R + 2, L)
     y0, y1 = torch.empty_like(x), torch.empty_like(x)
     check(lib().bem_ss2d_scan_rm_f32(_p(x), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1), B, C, H, W, R, bs[0], bs[1], _stream()),
           "ss2d_scan_rm")
@@ -208,7 +197,6 @@ def transpose_plane_slice(x, c0, C):
 # Two packed operand formats: "x6" (three bf16 limbs per f32 value, six limb products on v_mfma_f32_32x32x16_bf16, bem_pw_gemm_x6_f32 --
 # f32-level error at 6/16 of the f32 matrix-pipe cost), what every pointwise GEMM consumes; and "f32" (v_mfma_f32_32x32x2_f32 operand
 # order, pack_pw_weight(x6=False)), the weight format of the implicit-GEMM convolutions (bem_conv2d_mfma_f32).
-USE_X6 = True          # the pointwise GEMMs run on the bf16-limb kernels only (the f32-MFMA GEMMs were removed in round 3)
 # Bumped whenever parameters are rewritten behind torch's back (the fused optimizer step, bem.train.BemAdamW): every cache of
 # derived weights (packed / transposed / flipped copies) is keyed on it as well as on the tensors' data_ptr / _version.
 WEIGHT_EPOCH = [0]
@@ -228,13 +216,12 @@ def packed_elems(M: int, K: int, x6: bool = False) -> int:
     return int(lib().bem_pw_x6_packed_elems(M, K) if x6 else lib().bem_pw_packed_elems(M, K))
 
 
-def pack_pw_weight(W, x6=None):
+def pack_pw_weight(W, x6=True):
     """(M,K) or (nsets,M,K) natural weights -> packed MFMA operand order, shape (nsets, packed).
-    x6: None = module default (USE_X6), False = f32 operands (also what the MFMA convolution consumes)."""
+    x6: True = bf16-limb operands (every pointwise GEMM), False = f32 operands (what the MFMA convolution consumes)."""
     if W.dim() == 2:
         W = W[None]
     ns, M, K = W.shape
-    x6 = USE_X6 if x6 is None else x6
     out = torch.empty(ns, packed_elems(M, K, x6), device=W.device, dtype=W.dtype)
     if x6 and not W.is_contiguous():            # a transposed / sliced view (W^T of an input-gradient GEMM): packed where it lies
         if not W.is_cuda or W.dtype != torch.float32:
@@ -320,13 +307,20 @@ def empty_padded(shape, device, pad=4):
     return buf[pad:pad + n].view(shape)
 
 
+def _chk_packed1(op, weights):
+    """Each (name, Wp, M, K): Wp is ONE x6-packed (M, K) weight set (the fused kernels take no per-sample weights)."""
+    for nm, Wp, M, K in weights:
+        if Wp.dim() != 2 or Wp.shape[0] != 1 or Wp.shape[1] != packed_elems(M, K, True) or getattr(Wp, "_bem_mk", (M, K)) != (M, K):
+            raise ValueError(f"{op}: {nm} {tuple(Wp.shape)} does not match M={M} K={K} (x6 format, one weight set)")
+
+
 # SS2D front half (LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj) in one kernel for C <= 48, deterministic weights.  BEM_SS2D_FRONT=0
 # restores the three-kernel chain.
 SS2D_FRONT = os.environ.get("BEM_SS2D_FRONT", "1") != "0"
 
 
 def ss2d_front_supported(C, Mx):
-    return USE_X6 and SS2D_FRONT and C <= 48 and C % 8 == 0 and Mx <= 32
+    return SS2D_FRONT and C <= 48 and C % 8 == 0 and Mx <= 32
 
 
 def ss2d_front(x, ln_w, ln_b, ln_eps, Wp_in, bias_in, dww, dwb, Wp_x, Mx):
@@ -336,13 +330,11 @@ def ss2d_front(x, ln_w, ln_b, ln_eps, Wp_in, bias_in, dww, dwb, Wp_x, Mx):
         _chk(t, n_)
     _chk(bias_in, "bias_in", optional=True); _chk(dwb, "dwb", optional=True)
     B, C, H, W = x.shape
-    if not (USE_X6 and C <= 48 and C % 8 == 0 and Mx <= 32):
+    if not (C <= 48 and C % 8 == 0 and Mx <= 32):
         raise ValueError(f"ss2d_front: C = {C} (<= 48, % 8) / Mx = {Mx} (<= 32) not supported")
     if ln_w.numel() != C or ln_b.numel() != C or dww.numel() != 9 * C or (dwb is not None and dwb.numel() != C) or (bias_in is not None and bias_in.numel() != C):
         raise ValueError("ss2d_front: parameter shapes")
-    for Wp, (M, K), nm in ((Wp_in, (C, C), "Wp_in"), (Wp_x, (Mx, C), "Wp_x")):
-        if Wp.dim() != 2 or Wp.shape[0] != 1 or Wp.shape[1] != packed_elems(M, K, True) or getattr(Wp, "_bem_mk", (M, K)) != (M, K):
-            raise ValueError(f"ss2d_front: {nm} {tuple(Wp.shape)} does not match M={M} K={K} (x6 format, one weight set)")
+    _chk_packed1("ss2d_front", (("Wp_in", Wp_in, C, C), ("Wp_x", Wp_x, Mx, C)))
     xc = torch.empty_like(x)
     xd = torch.empty(B, Mx, H, W, device=x.device, dtype=x.dtype)
     check(lib().bem_ss2d_front_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_in), _p(bias_in), _p(dww), _p(dwb), _p(Wp_x), _p(xc), _p(xd),
@@ -365,7 +357,7 @@ GDMLP_X6_MAXC = int(os.environ.get("BEM_GDMLP_X6_MAXC", "80"))
 
 
 def gdmlp_x6_supported(C, Hd):
-    return USE_X6 and GDMLP_X6 and C <= GDMLP_X6_MAXC and Hd % 16 == 0
+    return GDMLP_X6 and C <= GDMLP_X6_MAXC and Hd % 16 == 0
 
 
 def dw_gate_params10(dww, dwb, Hd):
@@ -384,15 +376,13 @@ def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, 
         _chk(t, n_)
     _chk(bias_out, "bias_out", optional=True)
     B, C, H, W = x.shape
-    if not (USE_X6 and C <= 80 and Hd % 16 == 0):
+    if not (C <= 80 and Hd % 16 == 0):
         raise ValueError(f"gdmlp_x6: C = {C} (<= 80) / Hd = {Hd} (% 16) not supported")
     if tuple(dw10.shape) != (Hd, 10, 2):
         raise ValueError("gdmlp_x6: depthwise parameters must come from dw_gate_params10")
     if ln_w.numel() != C or ln_b.numel() != C or bias_gate.numel() != 2 * Hd or (bias_out is not None and bias_out.numel() != C):
         raise ValueError("gdmlp_x6: parameter shapes")
-    for Wp, (M, K), nm in ((Wp_gate, (2 * Hd, C), "Wp_gate"), (Wp_out, (C, Hd), "Wp_out")):
-        if Wp.dim() != 2 or Wp.shape[0] != 1 or Wp.shape[1] != packed_elems(M, K, True) or getattr(Wp, "_bem_mk", (M, K)) != (M, K):
-            raise ValueError(f"gdmlp_x6: {nm} {tuple(Wp.shape)} does not match M={M} K={K} (x6 format, one weight set)")
+    _chk_packed1("gdmlp_x6", (("Wp_gate", Wp_gate, 2 * Hd, C), ("Wp_out", Wp_out, C, Hd)))
     out = torch.empty_like(x)
     s = _timed("gdmlp_x6", 8.0 * x.numel(), 6.0 * 2.0 * B * H * W * (2 * Hd * C + Hd * C)) if _PROF is not None and _PROF["kernel"] == "gdmlp_x6" and _PROF["pred"](C) else None
     check(lib().bem_gdmlp_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_gate), _p(bias_gate), _p(dw10), _p(Wp_out),
@@ -477,7 +467,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
     Ho, Wo = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
     out = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=x.dtype)
     if dilation != 1 or (KH, KW, stride) == (3, 3, 2):
-        if (KH, KW) != (3, 3) or pad != dilation or not USE_X6 or Wo % 2 or Cin % 8 or (c0 * H * W) % 2:
+        if (KH, KW) != (3, 3) or pad != dilation or Wo % 2 or Cin % 8 or (c0 * H * W) % 2:
             raise ValueError("conv2d: dilated / strided 3x3 convolutions run in the tap form only (pad = dilation, even output width, Cin % 8 == 0)")
         for n, r in (("res1", res1), ("res2", res2)):
             if r is not None and r.shape != out.shape:
@@ -492,12 +482,12 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
     if bias is not None and bias.shape != (Cout,):
         raise ValueError("conv2d: bias shape")
     xp = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
-    if USE_CONV_X6 and USE_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
+    if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
         # nine shifted 1x1 taps on the bf16-limb GEMM machinery (pw_gemm_x6.hip)
         check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), _stream()), "conv3x3_x6")
         return out
-    conv4_fast = CONV4_FAST and USE_X6 and (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
+    conv4_fast = CONV4_FAST and (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
     if conv4_fast:
         # the coalesced-row form (conv_rows_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
@@ -1407,7 +1397,7 @@ def pw_wgrad_(dy, x1, dw, x2=None, dbias=None, blk_rows=0, perm=(0, 1, 2, 3), dy
         a.perm[i] = perm[i]
     a.dbias = dbias.data_ptr() if dbias is not None else 0
     a.B, a.L = B, L
-    if WGRAD_X6 and USE_X6 and L % 32 == 0 and B * L >= WGRAD_X6_MIN_PIXELS:
+    if WGRAD_X6 and L % 32 == 0 and B * L >= WGRAD_X6_MIN_PIXELS:
         n = lib().bem_pw_wgrad_x6_ws_elems(M, C1 + C2, B, L)
         ws = _WGX_WS.get(dw.device)
         if ws is None or ws.numel() < n:
@@ -1516,13 +1506,7 @@ def ss2d_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw,
     if dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C or dAlog.numel() != 4 * C or dDs.numel() != 4 * C \
             or ddtw.numel() != 4 * C * R or ddtb.numel() != 4 * C:
         raise ValueError("ss2d_scan_bwd: parameter shapes")
-    bs = []
-    for n, t in (("xd0", xd0), ("xd1", xd1)):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
-        if t.stride()[1:] != ((R + 2) * L, L, 1) or (B > 1 and (t.stride(0) < 2 * (R + 2) * L or (L % 4 == 0 and t.stride(0) % 4))):
-            raise ValueError(f"{n}: only the batch stride may differ from a contiguous (B,2,R+2,L) tensor")
-        bs.append(t.stride(0) if B > 1 else 0)
+    bs = _xd_bstrides("ss2d_scan_bwd", xd0, xd1, B, R + 2, L)
     dx0, dx1 = torch.empty_like(x0), torch.empty_like(x0)
     dxd0 = torch.empty(B, 2, R + 2, L, device=x0.device, dtype=x0.dtype)
     dxd1 = torch.empty(B, 2, R + 2, L, device=x0.device, dtype=x0.dtype)
@@ -1592,11 +1576,11 @@ _KEYS = {
     # the register-resident x6 GEMM for K <= 48 (level-0 in_proj / project_in / x_proj and the small Stage-I layers):
     # every launch of the (vectorised, single-input or concat) instance, whatever M and L
     "pw_x6_res<3,2,1>": ("pw_gemm", "hbm", "pw_x6_res_kernel<3, 2, 1, false, true>",
-                         lambda K, M, ln, L, mode: USE_X6 and K <= 48 and L % 2 == 0 and mode != 1),
+                         lambda K, M, ln, L, mode: K <= 48 and L % 2 == 0 and mode != 1),
     # the streaming x6 GEMM with two M-tiles per pass (project_out / out_proj / fuse 1x1 at K > 48 without LayerNorm):
     # the kernel with the largest share of the step in profiles/r01_bench_kernel_stats.csv
     "pw_x6_stream<2>": ("pw_gemm", "hbm", "pw_x6_stream_kernel<2, 2, false, true, false>",
-                        lambda K, M, ln, L, mode: USE_X6 and K > 48 and not ln and M > 32 and L % 2 == 0 and mode != 1),
+                        lambda K, M, ln, L, mode: K > 48 and not ln and M > 32 and L % 2 == 0 and mode != 1),
     "pw_gemm": ("pw_gemm", "mfma", "pw_gemm* (all variants)", lambda K, M, ln, L, mode: True),
     # the whole gdMlp branch in one kernel: x in, out out -- 8 bytes per element of x are its algorithmic bytes
     # (HBM: 42 us at level 0) -- but its two GEMMs (2Hd x C and C x Hd per pixel) evaluated as six bf16 limb products are 242 GFLOP on the

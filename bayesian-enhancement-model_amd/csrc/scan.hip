@@ -1,6 +1,6 @@
 // Selective scan kernels for CDNA4 (wave64).
 //   - bem_selective_scan_fwd_f32 : operator-seam replacement of selective_scan_cuda_oflex.fwd
-//   - bem_ss2d_scan_f32          : fused x_proj-rows -> dt_proj -> softplus -> 4-direction scan (N = 1)
+//   - bem_ss2d_scan_strided_f32  : fused x_proj-rows -> dt_proj -> softplus -> 4-direction scan (N = 1)
 //   - bem_cross_scan / merge     : operator-seam replacements of the Triton cross scan / merge
 //
 // Scan structure: every thread owns E consecutive sequence positions, folds them into an affine map
@@ -781,16 +781,6 @@ extern "C" int bem_selective_scan_fwd_in16(const void* u, const void* delta, con
                                                      delta_bias, out, batch, dim, L, dstate, ngroups, delta_softplus, stream);
     return selective_scan_fwd_launch<bem_bf16_t>((const bem_bf16_t*)u, (const bem_bf16_t*)delta, A, (const bem_bf16_t*)Bm, (const bem_bf16_t*)Cm, D,
                                                  delta_bias, out, batch, dim, L, dstate, ngroups, delta_softplus, stream);
-}
-
-extern "C" int bem_ss2d_scan_strided_f32(const float* x0, const float* x1, const float* xd0, const float* xd1,
-                                         const float* dtw, const float* dtb, const float* A, const float* Ds, float* y0,
-                                         float* y1, int B, int C, int L, int R, int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
-
-extern "C" int bem_ss2d_scan_f32(const float* x0, const float* x1, const float* xd0, const float* xd1,
-                                 const float* dtw, const float* dtb, const float* A, const float* Ds, float* y0,
-                                 float* y1, int B, int C, int L, int R, void* stream) {
-    return bem_ss2d_scan_strided_f32(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, 0, 0, stream);
 }
 
 extern "C" int bem_ss2d_scan_strided_f32(const float* x0, const float* x1, const float* xd0, const float* xd1,

@@ -1,4 +1,4 @@
-// Backward of the fused SS2D core (bem_ss2d_scan_f32): what autograd runs through
+// Backward of the fused SS2D core (bem_ss2d_scan_strided_f32): what autograd runs through
 //   cross_scan -> x_proj split -> dt_proj -> softplus -> selective scan (4 directions, N = 1) -> cross_merge
 // in the reference (vmamba.py:657-684; CrossScanF / CrossMergeF.backward csm_triton.py:207-273; SelectiveScanCuda.backward
 // csms6s.py:95-113 -> selective_scan_bwd_kernel_oflex.cuh:73-289), without materialising the 4x expanded tensors.
