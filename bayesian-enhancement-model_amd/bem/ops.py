@@ -886,10 +886,23 @@ def row_scale(w, scale):
     return out
 
 
+def _need4(op, x):
+    if x.dim() != 4:
+        raise ValueError(f"{op}: x must be (B, C, H, W), got {tuple(x.shape)}")
+    return tuple(x.shape)
+
+
+def _sa_kernel_size(op, w):
+    k = w.shape[-1] if w.dim() == 4 else 0
+    if k not in (3, 7) or tuple(w.shape) != (1, 2, k, k):
+        raise ValueError(f"{op}: w must be (1, 2, k, k) with k 3 or 7, got {tuple(w.shape)}")
+    return k
+
+
 def se_gate(x, w1, w2, want_mean=False):
     """SEBlock's per-channel gate (B,C) = sigmoid(w2 relu(w1 mean_hw(x)))."""
     _chk(x, "x"); _chk(w1, "w1"); _chk(w2, "w2")
-    B, C = x.shape[0], x.shape[1]
+    B, C, _, _ = _need4("se_gate", x)
     Cr = w1.shape[0]
     if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
         raise ValueError("se_gate: weight shapes")
@@ -902,10 +915,10 @@ def se_gate(x, w1, w2, want_mean=False):
 def spatial_attention(x, w, chan_scale=None, want_map=False):
     """x * chan_scale * sigmoid(conv_kxk([mean_c, max_c](x * chan_scale))); w (1,2,k,k).  want_map: also the (B,2,H,W) map (for the backward)."""
     _chk(x, "x"); _chk(w, "w"); _chk(chan_scale, "chan_scale", optional=True)
-    B, C, H, W = x.shape
-    k = w.shape[-1]
-    if tuple(w.shape) != (1, 2, k, k) or (chan_scale is not None and tuple(chan_scale.shape) != (B, C)):
-        raise ValueError("spatial_attention: weight / gate shapes")
+    B, C, H, W = _need4("spatial_attention", x)
+    k = _sa_kernel_size("spatial_attention", w)
+    if chan_scale is not None and tuple(chan_scale.shape) != (B, C):
+        raise ValueError("spatial_attention: the gate must be (B, C)")
     ws = torch.empty(B, 2, H, W, device=x.device, dtype=x.dtype)
     out = torch.empty_like(x)
     check(lib().bem_spatial_attention_f32(_p(x), _p(chan_scale), _p(w), _p(ws), _p(out), B, C, H, W, k, _stream()), "spatial_attention")
@@ -916,34 +929,56 @@ def spatial_attention_bwd(x, dout, amap, w, dw):
     """Backward of spatial_attention(x, w): returns dx; dw (1,2,k,k) accumulated."""
     for t, n in ((x, "x"), (dout, "dout"), (amap, "map"), (w, "w"), (dw, "dw")):
         _chk(t, n)
-    B, C, H, W = x.shape
+    B, C, H, W = _need4("spatial_attention_bwd", x)
+    k = _sa_kernel_size("spatial_attention_bwd", w)
+    if dout.shape != x.shape:
+        raise ValueError(f"spatial_attention_bwd: dout {tuple(dout.shape)} must have x's shape {tuple(x.shape)}")
+    if tuple(amap.shape) != (B, 2, H, W):
+        raise ValueError(f"spatial_attention_bwd: map must be {(B, 2, H, W)}, got {tuple(amap.shape)}")
+    if dw.numel() != 2 * k * k:
+        raise ValueError(f"spatial_attention_bwd: dw must hold {2 * k * k} elements, got {dw.numel()}")
     dpre = torch.empty(B, H, W, device=x.device, dtype=x.dtype)
     dx = torch.empty_like(x)
-    check(lib().bem_spatial_attention_bwd_f32(_p(x), _p(dout), _p(amap), _p(w), _p(dpre), _p(dx), _p(dw), B, C, H, W, w.shape[-1], _stream()),
+    check(lib().bem_spatial_attention_bwd_f32(_p(x), _p(dout), _p(amap), _p(w), _p(dpre), _p(dx), _p(dw), B, C, H, W, k, _stream()),
           "spatial_attention_bwd")
     return dx
 
 
 def chan_scale(x, scale, add=None, add_bc=None, add_bc_scale=1.0):
-    """scale[(b,) c] * x (+ add) (+ add_bc[b, c] * add_bc_scale); scale (C) or (B, C)."""
+    """scale[(b,) c] * x (+ add) (+ add_bc[b, c] * add_bc_scale); scale: one axis of C elements and otherwise axes of 1 ((C,), (1,C,1,1))
+    for one factor per channel, or exactly (B, C) for one per image and channel (a flat vector of B*C elements with B > 1 is ambiguous
+    and rejected)."""
     _chk(x, "x"); _chk(scale, "scale"); _chk(add, "add", optional=True); _chk(add_bc, "add_bc", optional=True)
+    if x.dim() < 3:
+        raise ValueError(f"chan_scale: x must be (B, C, ...), got {tuple(x.shape)}")
     B, C = x.shape[0], x.shape[1]
     HW = x[0, 0].numel()
-    if scale.numel() not in (C, B * C) or (add is not None and add.shape != x.shape) or (add_bc is not None and add_bc.numel() != B * C):
-        raise ValueError("chan_scale: shapes")
+    if tuple(scale.shape) == (B, C):
+        bstride = C
+    elif scale.numel() == C and C in tuple(scale.shape):
+        bstride = 0
+    else:
+        raise ValueError(f"chan_scale: scale must be one axis of {C} elements or {(B, C)}, got {tuple(scale.shape)}")
+    if add is not None and add.shape != x.shape:
+        raise ValueError(f"chan_scale: add {tuple(add.shape)} must have x's shape {tuple(x.shape)}")
+    if add_bc is not None and tuple(add_bc.shape) != (B, C):
+        raise ValueError(f"chan_scale: add_bc must be {(B, C)}, got {tuple(add_bc.shape)}")
     out = torch.empty_like(x)
-    check(lib().bem_chan_scale_f32(_p(x), _p(scale), C if (scale.numel() == B * C and scale.dim() > 1) else 0, _p(add), _p(add_bc), float(add_bc_scale), _p(out),
-                                   B, C, HW, _stream()), "chan_scale")
+    check(lib().bem_chan_scale_f32(_p(x), _p(scale), bstride, _p(add), _p(add_bc), float(add_bc_scale), _p(out), B, C, HW, _stream()), "chan_scale")
     return out
 
 
 def chan_dot(a, b, out=None):
     """out is None: (B,C) = sum_p a b per image; out (C): += sum over images and pixels (a parameter's gradient)."""
     _chk(a, "a"); _chk(b, "b"); _chk(out, "out", optional=True)
+    if a.dim() < 3:
+        raise ValueError(f"chan_dot: a must be (B, C, ...), got {tuple(a.shape)}")
     B, C = a.shape[0], a.shape[1]
     HW = a[0, 0].numel()
-    if b.shape != a.shape or (out is not None and out.numel() != C):
-        raise ValueError("chan_dot: shapes")
+    if b.shape != a.shape:
+        raise ValueError(f"chan_dot: b {tuple(b.shape)} must have a's shape {tuple(a.shape)}")
+    if out is not None and out.numel() != C:
+        raise ValueError(f"chan_dot: out must hold {C} elements, got {out.numel()}")
     per = out is None
     if per:
         out = torch.empty(B, C, device=a.device, dtype=a.dtype)
@@ -952,11 +987,18 @@ def chan_dot(a, b, out=None):
 
 
 def se_gate_bwd(mean, w1, w2, y, dy, dw1, dw2):
+    """Backward of se_gate's (B,C) gate from its plane means: returns dmean (B,C); dw1 (Cr,C) and dw2 (C,Cr) accumulated."""
     for t, n in ((mean, "mean"), (w1, "w1"), (w2, "w2"), (y, "y"), (dy, "dy"), (dw1, "dw1"), (dw2, "dw2")):
         _chk(t, n)
+    if mean.dim() != 2 or w1.dim() != 2:
+        raise ValueError(f"se_gate_bwd: mean must be (B, C) and w1 (Cr, C), got {tuple(mean.shape)}, {tuple(w1.shape)}")
     B, C = mean.shape
+    Cr = w1.shape[0]
+    for t, n, shape in ((y, "y", (B, C)), (dy, "dy", (B, C)), (w1, "w1", (Cr, C)), (w2, "w2", (C, Cr)), (dw1, "dw1", (Cr, C)), (dw2, "dw2", (C, Cr))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"se_gate_bwd: {n} must be {shape}, got {tuple(t.shape)}")
     dmean = torch.empty_like(mean)
-    check(lib().bem_se_gate_bwd_f32(_p(mean), _p(w1), _p(w2), _p(y), _p(dy), _p(dmean), _p(dw1), _p(dw2), B, C, w1.shape[0], _stream()), "se_gate_bwd")
+    check(lib().bem_se_gate_bwd_f32(_p(mean), _p(w1), _p(w2), _p(y), _p(dy), _p(dmean), _p(dw1), _p(dw2), B, C, Cr, _stream()), "se_gate_bwd")
     return dmean
 
 

@@ -6,6 +6,9 @@
 // SE and attention follow each other on the same tensor (:318-324), so the attention kernels take the SE gate as a per-channel factor:
 // the scaled tensor x * y is never written.  All of it is HBM-bound elementwise / reduction work on the deepest level's planes (H/4 x W/4):
 // coalesced rows of one plane per wavefront access, channels as the loop.
+// The per-pixel / per-channel scalars (SE hidden units and gate, channel mean, pre-sigmoid sum and the sigmoid; sum_c dout x and the transposed
+// conv in the backward) are accumulated in double and rounded to f32 once: they are a C-th of the work, and every output they multiply moves
+// with their rounding (profiles/attn_blocks_parity.txt).  The SE backward recomputes the hidden units exactly as the forward formed them.
 #include "bem_common.h"
 
 namespace {
@@ -25,17 +28,17 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
     for (int c = threadIdx.x; c < C; c += 256) m[c] = mean[(int64_t)b * C + c];
     __syncthreads();
     for (int r = wave; r < Cr; r += 4) {
-        float acc = 0.f;
-        for (int c = lane; c < C; c += 64) acc = fmaf(w1[(int64_t)r * C + c], m[c], acc);
+        double acc = 0.0;
+        for (int c = lane; c < C; c += 64) acc = fma((double)w1[(int64_t)r * C + c], (double)m[c], acc);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
-        if (lane == 0) h[r] = fmaxf(acc, 0.f);
+        if (lane == 0) h[r] = fmaxf((float)acc, 0.f);
     }
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += 256) {
-        float acc = 0.f;
-        for (int r = 0; r < Cr; ++r) acc = fmaf(w2[(int64_t)c * Cr + r], h[r], acc);
-        y[(int64_t)b * C + c] = 1.f / (1.f + expf(-acc));
+        double acc = 0.0;
+        for (int r = 0; r < Cr; ++r) acc = fma((double)w2[(int64_t)c * Cr + r], (double)h[r], acc);
+        y[(int64_t)b * C + c] = (float)(1.0 / (1.0 + exp(-acc)));
     }
 }
 
@@ -46,14 +49,34 @@ __global__ void sa_stats_kernel(const float* __restrict__ x, const float* __rest
     const int64_t b = i / HW, p = i - b * HW;
     const float* xp = x + b * C * HW + p;
     const float* yb = y ? y + b * C : nullptr;
-    float s = 0.f, mx = -INFINITY;
+    double s = 0.0;
+    float mx = -INFINITY;
     for (int c = 0; c < C; ++c) {
         const float v = xp[(int64_t)c * HW] * (yb ? yb[c] : 1.f);
-        s += v;
+        s += (double)v;
         mx = fmaxf(mx, v);
     }
-    map[(b * 2) * HW + p] = s / (float)C;
+    map[(b * 2) * HW + p] = (float)(s / (double)C);
     map[(b * 2 + 1) * HW + p] = mx;
+}
+
+// a = sigmoid(sum_taps w[ch][tap] map[ch][p + tap offset]), zero padding k / 2: the sum and the sigmoid in double, rounded once
+__device__ __forceinline__ float sa_gate(const float* __restrict__ map, const float* __restrict__ w, int64_t b, int py, int px, int H, int W, int k) {
+    const int64_t HW = (int64_t)H * W;
+    const int r = k / 2;
+    double acc = 0.0;
+    for (int ch = 0; ch < 2; ++ch) {
+        const float* mp = map + (b * 2 + ch) * HW;
+        for (int dy = 0; dy < k; ++dy) {
+            const int yy = py + dy - r;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+                const int xx = px + dx - r;
+                if (xx >= 0 && xx < W) acc = fma((double)w[(ch * k + dy) * k + dx], (double)mp[(int64_t)yy * W + xx], acc);
+            }
+        }
+    }
+    return (float)(1.0 / (1.0 + exp(-acc)));
 }
 
 // a thread per pixel: a = sigmoid(conv_kxk(map), zero padding k / 2); out[c] = x[c] * y[c] * a
@@ -62,20 +85,7 @@ __global__ void sa_apply_kernel(const float* __restrict__ x, const float* __rest
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
-    const int py = (int)(p / W), px = (int)(p - (int64_t)py * W), r = k / 2;
-    float acc = 0.f;
-    for (int ch = 0; ch < 2; ++ch) {
-        const float* mp = map + (b * 2 + ch) * HW;
-        for (int dy = 0; dy < k; ++dy) {
-            const int yy = py + dy - r;
-            if (yy < 0 || yy >= H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int xx = px + dx - r;
-                if (xx >= 0 && xx < W) acc = fmaf(w[(ch * k + dy) * k + dx], mp[(int64_t)yy * W + xx], acc);
-            }
-        }
-    }
-    const float a = 1.f / (1.f + expf(-acc));
+    const float a = sa_gate(map, w, b, (int)(p / W), (int)(p % W), H, W, k);
     const float* xp = x + b * C * HW + p;
     float* op = out + b * C * HW + p;
     const float* yb = y ? y + b * C : nullptr;
@@ -139,12 +149,12 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
         dz2[c] = dy[(int64_t)b * C + c] * yv * (1.f - yv);
     }
     __syncthreads();
-    for (int r = wave; r < Cr; r += 4) {
-        float acc = 0.f;
-        for (int c = lane; c < C; c += 64) acc = fmaf(w1[(int64_t)r * C + c], m[c], acc);
+    for (int r = wave; r < Cr; r += 4) {       // the forward's h, bit for bit (same sum, same order): the ReLU mask is the one y was made with
+        double acc = 0.0;
+        for (int c = lane; c < C; c += 64) acc = fma((double)w1[(int64_t)r * C + c], (double)m[c], acc);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
-        if (lane == 0) h[r] = fmaxf(acc, 0.f);
+        if (lane == 0) h[r] = fmaxf((float)acc, 0.f);
     }
     __syncthreads();
     for (int r = wave; r < Cr; r += 4) {       // dh[r] = sum_c W2[c][r] dz2[c]
@@ -166,36 +176,18 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
     }
 }
 
-__device__ __forceinline__ float sa_conv(const float* __restrict__ map, const float* __restrict__ w, int64_t b, int py, int px, int H, int W, int k) {
-    const int64_t HW = (int64_t)H * W;
-    const int r = k / 2;
-    float acc = 0.f;
-    for (int ch = 0; ch < 2; ++ch) {
-        const float* mp = map + (b * 2 + ch) * HW;
-        for (int dy = 0; dy < k; ++dy) {
-            const int yy = py + dy - r;
-            if (yy < 0 || yy >= H) continue;
-            for (int dx = 0; dx < k; ++dx) {
-                const int xx = px + dx - r;
-                if (xx >= 0 && xx < W) acc = fmaf(w[(ch * k + dy) * k + dx], mp[(int64_t)yy * W + xx], acc);
-            }
-        }
-    }
-    return acc;
-}
-
 // dpre[b][p] = (sum_c dout x) a (1 - a),  a = sigmoid(conv(map))
 __global__ void sa_bwd_pre_kernel(const float* __restrict__ x, const float* __restrict__ dout, const float* __restrict__ map, const float* __restrict__ w,
                                   float* __restrict__ dpre, int C, int H, int W, int k, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
-    const float a = 1.f / (1.f + expf(-sa_conv(map, w, b, (int)(p / W), (int)(p % W), H, W, k)));
+    const float a = sa_gate(map, w, b, (int)(p / W), (int)(p % W), H, W, k);
     const float* xp = x + b * C * HW + p;
     const float* dp = dout + b * C * HW + p;
-    float da = 0.f;
-    for (int c = 0; c < C; ++c) da = fmaf(dp[(int64_t)c * HW], xp[(int64_t)c * HW], da);
-    dpre[i] = da * a * (1.f - a);
+    double da = 0.0;
+    for (int c = 0; c < C; ++c) da = fma((double)dp[(int64_t)c * HW], (double)xp[(int64_t)c * HW], da);
+    dpre[i] = (float)da * a * (1.f - a);
 }
 
 // dx[c] = dout[c] a + dmap_mean / C + [c == argmax_c x] dmap_max,  dmap[ch][p] = sum_taps w[ch][tap] dpre[p - tap offset]   (transposed conv)
@@ -205,8 +197,8 @@ __global__ void sa_bwd_dx_kernel(const float* __restrict__ x, const float* __res
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
     const int py = (int)(p / W), px = (int)(p % W), r = k / 2;
-    const float a = 1.f / (1.f + expf(-sa_conv(map, w, b, py, px, H, W, k)));
-    float dmean = 0.f, dmax = 0.f;
+    const float a = sa_gate(map, w, b, py, px, H, W, k);
+    double dmean = 0.0, dmax = 0.0;
     const float* dq = dpre + b * HW;
     for (int dy = 0; dy < k; ++dy) {
         const int yy = py - (dy - r);                      // the output pixel whose window holds this pixel at tap (dy, dx)
@@ -214,9 +206,9 @@ __global__ void sa_bwd_dx_kernel(const float* __restrict__ x, const float* __res
         for (int dxx = 0; dxx < k; ++dxx) {
             const int xx = px - (dxx - r);
             if (xx < 0 || xx >= W) continue;
-            const float g = dq[(int64_t)yy * W + xx];
-            dmean = fmaf(w[(0 * k + dy) * k + dxx], g, dmean);
-            dmax = fmaf(w[(1 * k + dy) * k + dxx], g, dmax);
+            const double g = (double)dq[(int64_t)yy * W + xx];
+            dmean = fma((double)w[(0 * k + dy) * k + dxx], g, dmean);
+            dmax = fma((double)w[(1 * k + dy) * k + dxx], g, dmax);
         }
     }
     const float* xp = x + b * C * HW + p;
@@ -228,8 +220,8 @@ __global__ void sa_bwd_dx_kernel(const float* __restrict__ x, const float* __res
         const float v = xp[(int64_t)c * HW];
         if (v > mx) { mx = v; am = c; }                     // first maximum, as torch.max(dim) reports it
     }
-    const float dmc = dmean / (float)C;
-    for (int c = 0; c < C; ++c) op[(int64_t)c * HW] = dp[(int64_t)c * HW] * a + dmc + (c == am ? dmax : 0.f);
+    const float dmc = (float)(dmean / (double)C), dmx = (float)dmax;
+    for (int c = 0; c < C; ++c) op[(int64_t)c * HW] = dp[(int64_t)c * HW] * a + dmc + (c == am ? dmx : 0.f);
 }
 
 // dw[ch][dy][dx] += sum_{b,p} map[b][ch][p + tap offset] dpre[b][p]        grid = 2 k k workgroups
