@@ -132,8 +132,12 @@ class Decomp(nn.Module):
     def forward(self, x, c0=0):
         """x (B,Ct,H,W); channels [c0, c0+3) hold the RGB image to decompose."""
         _need_cuda(x)
+        return self.forward_from_dwt(ops.quat_dwt(x, c0))
+
+    def forward_from_dwt(self, d):
+        """d (B,32,h,w) = quat_dwt of the image: the entry for callers that form it themselves (ops.cond_dwt)."""
+        _need_cuda(d)
         P = self._prepared()
-        d = ops.quat_dwt(x, c0)
         feat = self.conv_in(d)
         if self.model == "model3" and not self.wavelet_out:
             if self.training and torch.is_grad_enabled():
@@ -286,11 +290,12 @@ class _DualBranch(_Stage2):
         # the registration order above differs from the reference only inside this constructor;
         # state-dict KEYS and shapes are identical (tests/test_host_contract.py)
 
-    def _dual_unet(self, qs):
-        """qs: the inputs of U-Net Q1 and Q2, taken one at a time as each branch starts.  Returns the two proj outputs."""
+    def _dual_unet(self, qs, first_kw=({}, {})):
+        """qs: the inputs of U-Net Q1 and Q2, taken one at a time as each branch starts; first_kw: per branch, further arguments of its
+        first_conv.  Returns the two proj outputs."""
         feats, skips = [], []
-        for br, q in zip(("_Q1", "_Q2"), qs):
-            f, sk = self._encode(br, q)
+        for br, q, kw in zip(("_Q1", "_Q2"), qs, first_kw):
+            f, sk = self._encode(br, q, **kw)
             feats.append(f)
             skips.append(sk)
         fused = self.bottleneck_block(self.bottleneck_fuse(feats[0], x2=feats[1], in_mode=2))
@@ -311,13 +316,32 @@ class DecompDualBranchDDWavelet(_DualBranch):
     def decompose(self, x, c0):
         return self.decomp(x, c0)
 
-    def forward_decomposed(self, d_img, d_cond, img_index=None):
+    def decompose_cond(self, conds, scale):
+        """decompose(bilinear_up(conds, scale), 0) of the Stage-I conditions (R,3,hd,wd), without the enlarged condition image."""
+        return self.decomp.forward_from_dwt(ops.cond_dwt(conds, scale))
+
+    def first_conv_image(self, d_img):
+        """Per branch, the image half of first_conv with its bias: (Bi,n_feat,h,w) each.  first_conv is linear in its input channels and
+        its image half does not depend on the sample, so it is evaluated once per image; forward_decomposed adds it to the condition
+        half of every sample of that image."""
+        fcs = [getattr(self, "first_conv" + br) for br in ("_Q1", "_Q2")]
+        return [ops.conv2d(d_img, fc.weight_part(0, 16), fc.bias.detach(), pad=1, cin_slice=(16 * bi, 16)) for bi, fc in enumerate(fcs)]
+
+    def forward_decomposed(self, d_img, d_cond, img_index=None, p_img=None):
         """d_img (Bi,32,h,w), d_cond (B,32,h,w); img_index: None (Bi == B) or samples-per-image count
-        (image i serves batch rows [i*n, (i+1)*n))."""
+        (image i serves batch rows [i*n, (i+1)*n)); p_img: first_conv_image(d_img) where the caller has it already.
+        Inference: first_conv(cat(d_img[16 bi : 16 bi + 16] per sample, d_cond[16 bi : 16 bi + 16])) runs as the condition half on the B
+        rows with the per-image half as its residual -- the concatenation is never formed.  Training keeps the concatenated input."""
         B, _, h, w = d_cond.shape
         spi = 1 if img_index is None else int(img_index)
         if d_img.shape[0] * spi != B:
             raise ValueError("forward_decomposed: image / sample batch mismatch")
+        if not grad_mode(self):
+            if p_img is None:
+                p_img = self.first_conv_image(d_img)
+            o1, o2 = self._dual_unet((d_cond, d_cond), [dict(cin_slice=(16 * bi, 16), w_part=(16, 16), use_bias=False, res1=p_img[bi], res1_rep=spi)
+                                                        for bi in range(2)])
+            return ops.iwt_hamilton(o1, o2)
 
         def branch_input(bi):
             q = torch.empty(B, 32, h, w, device=d_cond.device, dtype=d_cond.dtype)

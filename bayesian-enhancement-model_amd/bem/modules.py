@@ -189,14 +189,26 @@ class DwConv2d(nn.Conv2d):
 class Conv2dK(nn.Conv2d):
     """Dense conv (3x3 s1 p1 or 4x4 s2 p1) on the direct-conv kernel."""
 
-    def forward(self, x, relu=False, res1=None, res2=None, cin_slice=None):
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self._cache = _Cache()
+
+    def weight_part(self, c0, n):
+        """weight[:, c0:c0+n] as its own contiguous tensor, made once per weight version (it keys the packed-operand caches of ops.conv2d)."""
+        return self._cache.get(("part", c0, n), [self.weight], lambda: self.weight.detach()[:, c0:c0 + n].contiguous())
+
+    def forward(self, x, relu=False, res1=None, res2=None, cin_slice=None, res1_rep=1, w_part=None, use_bias=True):
+        """``w_part=(c0, n)``: the convolution over input channels [c0, c0+n) of the weight only (a convolution is linear in its input
+        channels: the parts of a split layer are summed through ``res1``); ``use_bias=False`` leaves the bias to another part."""
         _need_cuda(x)
         if grad_mode(self) and self.weight.requires_grad:
-            if relu or res1 is not None or res2 is not None:
+            if relu or res1 is not None or res2 is not None or w_part is not None or not use_bias:
                 raise BemNativeError("Conv2dK: the training path covers the plain convolution (+ bias) only")
             return ag.Conv2dFn.apply(x, self.weight, self.bias, self, cin_slice)
-        return ops.conv2d(x, self.weight.detach(), None if self.bias is None else self.bias.detach(),
-                          stride=self.stride[0], pad=self.padding[0], relu=relu, res1=res1, res2=res2, cin_slice=cin_slice, dilation=self.dilation[0])
+        w = self.weight.detach() if w_part is None else self.weight_part(*w_part)
+        return ops.conv2d(x, w, self.bias.detach() if (use_bias and self.bias is not None) else None,
+                          stride=self.stride[0], pad=self.padding[0], relu=relu, res1=res1, res2=res2, cin_slice=cin_slice, dilation=self.dilation[0],
+                          res1_rep=res1_rep)
 
 
 class ConvT2x2(nn.ConvTranspose2d):

@@ -92,16 +92,17 @@ SIGNATURES = {
     "bem_prelu_bwd_f32": [P, P, P, P, P, I64, P],
     "bem_bilinear_up_bwd_f32": [P, P, I, I, I, I, I, P],
     "bem_gdmlp_x6_f32": [P, P, P, F, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_conv3x3_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, P],
+    "bem_conv3x3_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "bem_conv4x4s2_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, P],
     "bem_conv4x4s2_fast_supported": [I, I, I],
     "bem_conv3x3_rows_supported": [I, I, I],
     "bem_ss2d_front_x6_f32": [P, P, P, F, P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_conv_taps_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+    "bem_conv_taps_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "bem_dwconv3x3_f32": [P, P, I64, P, I64, P, I, I, I, I, I, P],
-    "bem_conv2d_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "bem_conv2d_mfma_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "bem_conv2d_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    "bem_conv2d_mfma_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     "bem_quat_dwt_f32": [P, I64, P, I, I, I, P],
+    "bem_cond_dwt_f32": [P, P, I, I, I, I, P],
     "bem_dwt_f32": [P, P, I, I, I, I, P],
     "bem_iwt_f32": [P, P, I, I, I, I, P],
     "bem_iwt_hamilton_f32": [P, P, P, I, I, I, P],

@@ -449,8 +449,9 @@ def _packed_conv_weight_x6(w):
     return hit[1]
 
 
-def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1):
+def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
     """Dense conv.  ``cin_slice=(c0, Cin)`` convolves channels [c0, c0+Cin) of a wider contiguous x.
+    ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
     Runs as an implicit GEMM on the matrix cores (Cout <= 160), else on the direct VALU kernel.
     dilation 2 (3x3, pad 2) and 3x3 stride 2 exist in the shifted-tap form only (QD model2 / model3)."""
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias", optional=True)
@@ -466,18 +467,22 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         raise ValueError(f"conv2d: input has {Ct} channels, weight expects {Cin}")
     Ho, Wo = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
     out = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=x.dtype)
+    res1_rep = int(res1_rep)
+    if res1_rep < 1 or (res1_rep != 1 and res1 is None):
+        raise ValueError("conv2d: res1_rep must be >= 1 and needs res1")
+    res_shapes = (("res1", res1, (B // res1_rep if B % res1_rep == 0 else -1,) + tuple(out.shape[1:])), ("res2", res2, tuple(out.shape)))
     if dilation != 1 or (KH, KW, stride) == (3, 3, 2):
         if (KH, KW) != (3, 3) or pad != dilation or Wo % 2 or Cin % 8 or (c0 * H * W) % 2:
             raise ValueError("conv2d: dilated / strided 3x3 convolutions run in the tap form only (pad = dilation, even output width, Cin % 8 == 0)")
-        for n, r in (("res1", res1), ("res2", res2)):
-            if r is not None and r.shape != out.shape:
+        for n, r, shp in res_shapes:
+            if r is not None and tuple(r.shape) != shp:
                 raise ValueError(f"conv2d: {n} shape")
         xp_ = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
         check(lib().bem_conv_taps_x6_f32(xp_, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
-                                         dilation, int(relu), _stream()), "conv_taps_x6")
+                                         dilation, int(relu), res1_rep, _stream()), "conv_taps_x6")
         return out
-    for n, r in (("res1", res1), ("res2", res2)):
-        if r is not None and r.shape != out.shape:
+    for n, r, shp in res_shapes:
+        if r is not None and tuple(r.shape) != shp:
             raise ValueError(f"conv2d: {n} shape")
     if bias is not None and bias.shape != (Cout,):
         raise ValueError("conv2d: bias shape")
@@ -485,7 +490,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
     if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
         # nine shifted 1x1 taps on the bf16-limb GEMM machinery (pw_gemm_x6.hip)
         check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
-                                       Cout, int(relu), _stream()), "conv3x3_x6")
+                                       Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
         return out
     conv4_fast = CONV4_FAST and (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
@@ -496,10 +501,10 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         return out
     if USE_CONV_MFMA and Cout <= 160 and ((KH, KW, stride) in ((3, 3, 1), (4, 4, 2))):
         check(lib().bem_conv2d_mfma_f32(xp, Ct * H * W, _p(_packed_conv_weight(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
-                                        Cout, KH, KW, stride, pad, int(relu), _stream()), "conv2d_mfma")
+                                        Cout, KH, KW, stride, pad, int(relu), res1_rep, _stream()), "conv2d_mfma")
         return out
     check(lib().bem_conv2d_f32(xp, Ct * H * W, _p(w), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW,
-                               stride, pad, int(relu), _stream()), "conv2d")
+                               stride, pad, int(relu), res1_rep, _stream()), "conv2d")
     return out
 
 
@@ -512,6 +517,19 @@ def quat_dwt(x, c0=0):
         raise ValueError("quat_dwt: needs 3 channels and even H, W")
     out = torch.empty(B, 32, H // 2, W // 2, device=x.device, dtype=x.dtype)
     check(lib().bem_quat_dwt_f32(ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W), Ct * H * W, _p(out), B, H, W, _stream()), "quat_dwt")
+    return out
+
+
+def cond_dwt(conds, s):
+    """conds (R,3,hd,wd) -> (R,32,hd*s/2,wd*s/2) = quat_dwt(bilinear_up(conds, s)), bit for bit, in one kernel: the enlarged condition
+    image is never written."""
+    _chk(conds, "conds")
+    s = int(s)
+    R, C, H, W = conds.shape
+    if C != 3 or s < 1 or (H * s) % 2 or (W * s) % 2:
+        raise ValueError("cond_dwt: needs 3 channels and even enlarged H, W")
+    out = torch.empty(R, 32, H * s // 2, W * s // 2, device=conds.device, dtype=conds.dtype)
+    check(lib().bem_cond_dwt_f32(_p(conds), _p(out), R, H, W, s, _stream()), "cond_dwt")
     return out
 
 

@@ -56,13 +56,14 @@ class BEMPipeline:
         hd, wd = img_down.shape[-2:]
         x1 = img_down[:, None].expand(B, N, 3, hd, wd).reshape(B * N, 3, hd, wd)  # (B*N,3,hd,wd): row = image*N + sample
         hoist = hasattr(self.net2, "forward_decomposed")
-        d_img, main = None, torch.cuda.current_stream()
+        d_img, p_img, main = None, None, torch.cuda.current_stream()
         if hoist and os.environ.get("BEM_DECOMP_OVERLAP", "1") != "0":
             if self._side is None or self._side.device != pad.device:
                 self._side = torch.cuda.Stream(device=pad.device)
             self._side.wait_stream(main)                                         # pad is ready
             with torch.cuda.stream(self._side):
                 d_img = self.net2.decompose(pad, 0)                              # once per image, beside Stage I
+                p_img = self.net2.first_conv_image(d_img)                        # the image half of the two first convs likewise
             pad.record_stream(self._side)
         set_prediction_type(self.net1, deterministic)
         with sampling(None if deterministic else SampleCtx(B * N, eps, seed, rank=rank)) as ctx:
@@ -72,16 +73,18 @@ class BEMPipeline:
             # torch.randn_like of eval.py:209: its own key space (bit 62 of the stream id), per rank and per forward
             noise = ops.randn(tuple(pred.shape), pred.device, seed, (1 << 62) | (rank << 44) | SampleCtx._epoch)
         conds = ops.cond_postproc(pred, tmean, noise if self.noise_level else None, N, self.noise_level)
-        cond_up = ops.bilinear_up(conds, self.scale)                             # (B*N,3,Hp,Wp)
         if hoist:
             if d_img is None:
                 d_img = self.net2.decompose(pad, 0)                              # once per image
+                p_img = self.net2.first_conv_image(d_img)
             else:
                 main.wait_stream(self._side)
-                d_img.record_stream(main)                                        # allocated on the side stream, consumed (and freed) on this one
-            d_cond = self.net2.decompose(cond_up, 0)
-            raw = self.net2.forward_decomposed(d_img, d_cond, None if N == 1 else N)
+                for t in [d_img] + p_img:
+                    t.record_stream(main)                                        # allocated on the side stream, consumed (and freed) on this one
+            d_cond = self.net2.decompose_cond(conds, self.scale)                 # decomp of the enlarged condition, which is never formed
+            raw = self.net2.forward_decomposed(d_img, d_cond, None if N == 1 else N, p_img=p_img)
         else:
+            cond_up = ops.bilinear_up(conds, self.scale)                         # (B*N,3,Hp,Wp)
             # Stage-II archs without a separable decomposition stage (DecompDualBranch, the *2 / *DD / SingleBranch siblings): the
             # reference's own call per candidate, net(cat(img, cond)) (eval.py:211-213), as one batch of B*N rows
             x2 = torch.empty(B * N, 6, Hp, Wp, device=pad.device, dtype=pad.dtype)

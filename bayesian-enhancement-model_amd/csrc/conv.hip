@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const float* __restrict__ x
                                                      const float* __restrict__ w, const float* __restrict__ bias,
                                                      const float* __restrict__ res1, const float* __restrict__ res2,
                                                      float* __restrict__ out, int Cin, int H, int W, int Cout,
-                                                     int Ho, int Wo, int pad, int relu, int tilesX) {
+                                                     int Ho, int Wo, int pad, int relu, int tilesX, int res1_rep) {
     constexpr int PH = (TH - 1) * S + KH, PW = (TW - 1) * S + KW;
     constexpr int PWP = PW + 1;                       // +1 pad: rows of a patch start on different banks
     __shared__ float patch[CIB][PH][PWP];
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const float* __restrict__ x
         float v = acc[o] + (bias ? bias[co] : 0.f);
         if (relu) v = fmaxf(v, 0.f);
         const int64_t idx = (((int64_t)b * Cout + co) * Ho + oy) * Wo + ox;
-        if (res1) v += res1[idx];
+        if (res1) v += res1[(((int64_t)(b / res1_rep) * Cout + co) * Ho + oy) * Wo + ox];      // one residual row per res1_rep output rows
         if (res2) v += res2[idx];
         out[idx] = v;
     }
@@ -290,11 +290,11 @@ __device__ __forceinline__ constexpr int patch_off(int k) {
 
 // epilogue: out = relu?(acc + bias) + res1 + res2.  Optional operands are read through an always-valid pointer (the
 // packed weights, finite) at index 0 and masked by multiplication, rows / pixels past the edge at clamped indices, so
-// the loads carry no branches; only the stores are predicated.
+// the loads carry no branches; only the stores are predicated.  res1 is read at batch row b1 = b / res1_rep (wave-uniform).
 template <int MTW>
 __device__ __forceinline__ void conv_mfma_epilogue(f32x16 (&acc)[MTW][2], const float* __restrict__ Wp, const float* __restrict__ bias,
                                                    const float* __restrict__ res1, const float* __restrict__ res2,
-                                                   float* __restrict__ out, int b, int Cout, int Ho, int Wo, int ty0, int tx0,
+                                                   float* __restrict__ out, int b, int b1, int Cout, int Ho, int Wo, int ty0, int tx0,
                                                    int wave, int half, int j, int relu) {
     const int ox = tx0 + j, oxc = min(ox, Wo - 1);
     const float* bp = bias ? bias : Wp;
@@ -303,6 +303,7 @@ __device__ __forceinline__ void conv_mfma_epilogue(f32x16 (&acc)[MTW][2], const 
     const float bmk = bias ? 1.f : 0.f, m1 = res1 ? 1.f : 0.f, m2 = res2 ? 1.f : 0.f;
     const int64_t k0 = bias ? -1 : 0, k1 = res1 ? -1 : 0, k2 = res2 ? -1 : 0;     // index masks
     const float lo = relu ? 0.f : -3.402823466e38f;
+    const int64_t b1off = (int64_t)(b1 - b) * Cout * Ho * Wo;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int oy = ty0 + 2 * wave + t, oyc = min(oy, Ho - 1);
@@ -319,7 +320,7 @@ __device__ __forceinline__ void conv_mfma_epilogue(f32x16 (&acc)[MTW][2], const 
                     const int co = min(m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, Cout - 1);
                     const int64_t idx = (((int64_t)b * Cout + co) * Ho + oyc) * Wo + oxc;
                     bv[q] = bp[co & k0] * bmk;
-                    r1[q] = p1[idx & k1] * m1;
+                    r1[q] = p1[(idx + b1off) & k1] * m1;
                     r2[q] = p2[idx & k2] * m2;
                 }
 #pragma unroll
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 4 : MTW == 2 ? 3 : MTW == 3 ? 2 : 1
                                                           const float* __restrict__ Wp, const float* __restrict__ bias,
                                                           const float* __restrict__ res1, const float* __restrict__ res2,
                                                           float* __restrict__ out, int Cin, int H, int W, int Cout,
-                                                          int Ho, int Wo, int pad, int relu, int tilesX, int KS) {
+                                                          int Ho, int Wo, int pad, int relu, int tilesX, int KS, int res1_rep) {
     constexpr int KK = KH * KW;
     constexpr int KC = CIB * KK;                          // k values per chunk (even)
     constexpr int PH = (TH - 1) * S + KH, PW = (TW - 1) * S + KW, PWP = PW + 1;
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 4 : MTW == 2 ? 3 : MTW == 3 ? 2 : 1
             }
         }
     }
-    conv_mfma_epilogue<MTW>(acc, Wp, bias, res1, res2, out, b, Cout, Ho, Wo, ty0, tx0, wave, half, j, relu);
+    conv_mfma_epilogue<MTW>(acc, Wp, bias, res1, res2, out, b, b / res1_rep, Cout, Ho, Wo, ty0, tx0, wave, half, j, relu);
 }
 
 // Software-pipelined form of conv2d_mfma_kernel (3x3 stride 1, <= 2 M-tiles).  Both MFMA operands of a channel chunk
@@ -436,7 +437,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 3 : 2) void conv2d_mfma_pipe_kernel
                                                                const float* __restrict__ Wp, const float* __restrict__ bias,
                                                                const float* __restrict__ res1, const float* __restrict__ res2,
                                                                float* __restrict__ out, int Cin, int H, int W, int Cout,
-                                                               int Ho, int Wo, int pad, int relu, int tilesX, int KS) {
+                                                               int Ho, int Wo, int pad, int relu, int tilesX, int KS, int res1_rep) {
     constexpr int KK = KH * KW;
     constexpr int KC = CIB * KK;
     constexpr int NS = KC / 2;                            // k-steps per chunk
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 3 : 2) void conv2d_mfma_pipe_kernel
         __syncthreads();
         buf ^= 1;
     }
-    conv_mfma_epilogue<MTW>(acc, Wp, bias, res1, res2, out, b, Cout, Ho, Wo, ty0, tx0, wave, half, j, relu);
+    conv_mfma_epilogue<MTW>(acc, Wp, bias, res1, res2, out, b, b / res1_rep, Cout, Ho, Wo, ty0, tx0, wave, half, j, relu);
 }
 
 }  // namespace
@@ -576,8 +577,8 @@ extern "C" int bem_dwconv3x3_f32(const float* x, const float* w, int64_t w_bstri
 
 extern "C" int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w, const float* bias,
                               const float* res1, const float* res2, float* out, int B, int Cin, int H, int W,
-                              int Cout, int KH, int KW, int stride, int pad, int relu, void* stream) {
-    BEM_REQUIRE(x && w && out, "conv2d: null tensor");
+                              int Cout, int KH, int KW, int stride, int pad, int relu, int res1_rep, void* stream) {
+    BEM_REQUIRE(x && w && out && res1_rep >= 1, "conv2d: null tensor or res1_rep < 1");
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d: bad shape");
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     BEM_REQUIRE(Ho > 0 && Wo > 0, "conv2d: empty output");
@@ -586,9 +587,9 @@ extern "C" int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w,
     dim3 grid(tilesX * tilesY, cdiv(Cout, COB), B);
     hipStream_t s = (hipStream_t)stream;
     if (KH == 3 && KW == 3 && stride == 1)
-        conv2d_kernel<3, 3, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX);
+        conv2d_kernel<3, 3, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
     else if (KH == 4 && KW == 4 && stride == 2)
-        conv2d_kernel<4, 4, 2><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX);
+        conv2d_kernel<4, 4, 2><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
     else
         BEM_REQUIRE(false, "conv2d: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2)", KH, KW, stride);
     return bem_check_launch("conv2d");
@@ -596,8 +597,8 @@ extern "C" int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w,
 
 extern "C" int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias,
                                    const float* res1, const float* res2, float* out, int B, int Cin, int H, int W,
-                                   int Cout, int KH, int KW, int stride, int pad, int relu, void* stream) {
-    BEM_REQUIRE(x && Wp && out, "conv2d_mfma: null tensor");
+                                   int Cout, int KH, int KW, int stride, int pad, int relu, int res1_rep, void* stream) {
+    BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "conv2d_mfma: null tensor or res1_rep < 1");
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && Cout <= 160 && H > 0 && W > 0, "conv2d_mfma: bad shape (Cout <= 160)");
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     BEM_REQUIRE(Ho > 0 && Wo > 0, "conv2d_mfma: empty output");
@@ -607,12 +608,12 @@ extern "C" int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const floa
     dim3 grid(tilesX * tilesY, B);
     hipStream_t s = (hipStream_t)stream;
 #define BEM_CONV_LAUNCH(KH_, KW_, S_, MTW_) \
-    conv2d_mfma_kernel<KH_, KW_, S_, MTW_><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS)
+    conv2d_mfma_kernel<KH_, KW_, S_, MTW_><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep)
     if (KH == 3 && KW == 3 && stride == 1) {
         static const bool pipe = !(getenv("BEM_CONV_PIPE") && getenv("BEM_CONV_PIPE")[0] == '0');
         if (MT <= 2 && pipe) {
-            if (MT == 1) conv2d_mfma_pipe_kernel<3, 3, 1, 1><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS);
-            else conv2d_mfma_pipe_kernel<3, 3, 1, 2><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS);
+            if (MT == 1) conv2d_mfma_pipe_kernel<3, 3, 1, 1><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
+            else conv2d_mfma_pipe_kernel<3, 3, 1, 2><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
         }
         else if (MT == 1) BEM_CONV_LAUNCH(3, 3, 1, 1);
         else if (MT == 2) BEM_CONV_LAUNCH(3, 3, 1, 2);

@@ -24,7 +24,7 @@ namespace {
 struct CrX {
     const float* x; int64_t x_bs;
     const u32x4* Wp; const float* bias; const float* res1; const float* res2; float* out;
-    int Cin, H, W, Ho, Wo, Cout, KB, MT, wo_shift, relu, mt_first;
+    int Cin, H, W, Ho, Wo, Cout, KB, MT, wo_shift, relu, mt_first, res1_rep;
 };
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
@@ -114,11 +114,13 @@ __global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(CrX k) {
         __syncthreads();
     }
 
-    // epilogue: out = relu?(acc + bias) + res1 + res2, rows (r & 3) + 8 (r >> 2) + 4 kh of each row block, one 4 NPX-byte access per row
+    // epilogue: out = relu?(acc + bias) + res1 + res2, rows (r & 3) + 8 (r >> 2) + 4 kh of each row block, one 4 NPX-byte access per row.
+    // res1 is read at batch row b / res1_rep (one residual row shared by res1_rep output rows): a wave-uniform base, no lane arithmetic
     if (live) {
         typedef float fpx __attribute__((ext_vector_type(NPX)));
         const float lo = k.relu ? 0.f : -3.402823466e38f;
         const int64_t ob = (int64_t)b * k.Cout * Lo + pc;
+        const float* r1b = k.res1 + (int64_t)(b / k.res1_rep) * k.Cout * Lo + pc;
 #pragma unroll
         for (int m = 0; m < MTW; ++m)
 #pragma unroll
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(CrX k) {
                     fpx v;
 #pragma unroll
                     for (int j = 0; j < NPX; ++j) v[j] = fmaxf(acc[m][j][r] + alo[m][j][r] + bv, lo);
-                    if (k.res1) v += *reinterpret_cast<const fpx*>(k.res1 + o);
+                    if (k.res1) v += *reinterpret_cast<const fpx*>(r1b + (int64_t)row * Lo);
                     if (k.res2) v += *reinterpret_cast<const fpx*>(k.res2 + o);
                     *reinterpret_cast<fpx*>(k.out + o) = v;
                 }
@@ -151,9 +153,10 @@ extern "C" int bem_conv3x3_rows_supported(int Cin, int H, int W) {
 
 // KS = 4: the 4x4 stride-2 form; KS = 3: 3x3 stride 1.  Row blocks of output channels in pairs where the registers allow (4x4), singly else.
 int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2, float* out,
-                     int B, int Cin, int H, int W, int Cout, int relu, void* stream) {
+                     int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream) {
     const char* what = KS == 4 ? "conv4x4s2_x6" : "conv3x3_x6";
     BEM_REQUIRE(x && Wp && out, "%s: null tensor", what);
+    BEM_REQUIRE(res1_rep >= 1, "%s: res1_rep %d", what, res1_rep);
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && (KS == 4 ? bem_conv4x4s2_fast_supported(Cin, H, W) : bem_conv3x3_rows_supported(Cin, H, W)),
                 "%s: shape outside the row form", what);
     BEM_REQUIRE((((uintptr_t)Wp | (uintptr_t)x | (uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 15) == 0 && (x_bstride % 4) == 0,
@@ -163,7 +166,7 @@ int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp,
     if (B == 0) return BEM_OK;
     CrX k;
     k.x = x; k.x_bs = x_bstride; k.Wp = reinterpret_cast<const u32x4*>(Wp); k.bias = bias; k.res1 = res1; k.res2 = res2; k.out = out;
-    k.Cin = Cin; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.Cout = Cout; k.KB = cdiv(Cin, 16); k.MT = cdiv(Cout, 32); k.relu = relu;
+    k.Cin = Cin; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.Cout = Cout; k.KB = cdiv(Cin, 16); k.MT = cdiv(Cout, 32); k.relu = relu; k.res1_rep = res1_rep;
     k.wo_shift = __builtin_ctz(Wo);
     hipStream_t s = (hipStream_t)stream;
     if (KS == 4) {

@@ -12,6 +12,24 @@ namespace {
 #define GRID1D(n) dim3((unsigned)cdiv64((n), 256))
 
 // ---------------------------------------------------------------- quaternion + Haar ----------
+// The 8-channel quaternion stack of one RGB sample (QD/model4.py:7-18), into column s of q.
+__device__ __forceinline__ void quat_stack(float r, float g, float bl, float (&q)[8][4], int s) {
+    const float den = fmaxf(fmaxf(r, g), bl) + 1e-7f;
+    q[0][s] = 0.f; q[1][s] = 0.f;
+    q[2][s] = r / den; q[3][s] = r;
+    q[4][s] = g / den; q[5][s] = g;
+    q[6][s] = bl / den; q[7][s] = bl;
+}
+
+// Haar butterfly of a 2x2 block q = [(even row, even col), (odd row, even col), (even, odd), (odd, odd)] -> LL, HL, LH, HH (model4.py:216-236)
+__device__ __forceinline__ void haar_bands(const float (&q)[4], float (&o)[4]) {
+    const float a = q[0] / 2, bb = q[1] / 2, cc = q[2] / 2, d = q[3] / 2;
+    o[0] = a + bb + cc + d;
+    o[1] = -a - bb + cc + d;
+    o[2] = -a + bb - cc + d;
+    o[3] = a - bb - cc + d;
+}
+
 // One thread per output (half-res) pixel: reads the 2x2 RGB block, forms the 8-channel quaternion
 // stack and writes the 4 Haar bands (QD/model4.py:7-18,216-236).
 __global__ void quat_dwt_kernel(const float* __restrict__ rgb, int64_t x_bs, float* __restrict__ out, int H, int W,
@@ -26,22 +44,16 @@ __global__ void quat_dwt_kernel(const float* __restrict__ rgb, int64_t x_bs, flo
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const int yy = 2 * y + (s & 1), xx = 2 * x + (s >> 1);
-        const float r = p[(int64_t)yy * W + xx], g = p[HW + (int64_t)yy * W + xx], bl = p[2 * HW + (int64_t)yy * W + xx];
-        const float den = fmaxf(fmaxf(r, g), bl) + 1e-7f;
-        q[0][s] = 0.f; q[1][s] = 0.f;
-        q[2][s] = r / den; q[3][s] = r;
-        q[4][s] = g / den; q[5][s] = g;
-        q[6][s] = bl / den; q[7][s] = bl;
+        quat_stack(p[(int64_t)yy * W + xx], p[HW + (int64_t)yy * W + xx], p[2 * HW + (int64_t)yy * W + xx], q, s);
     }
     const int64_t hw2 = (int64_t)h2 * w2;
     float* o = out + (int64_t)b * 32 * hw2 + (int64_t)y * w2 + x;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const float a = q[c][0] / 2, bb = q[c][1] / 2, cc = q[c][2] / 2, d = q[c][3] / 2;
-        o[(int64_t)(c) * hw2] = a + bb + cc + d;
-        o[(int64_t)(8 + c) * hw2] = -a - bb + cc + d;
-        o[(int64_t)(16 + c) * hw2] = -a + bb - cc + d;
-        o[(int64_t)(24 + c) * hw2] = a - bb - cc + d;
+        float v[4];
+        haar_bands(q[c], v);
+#pragma unroll
+        for (int band = 0; band < 4; ++band) o[(int64_t)(8 * band + c) * hw2] = v[band];
     }
 }
 
@@ -356,25 +368,72 @@ __global__ void add_channels_kernel(const float* __restrict__ src, int64_t src_b
     dst[b * dst_bs + r] += src[b * src_bs + r];
 }
 
+// PyTorch upsample_bilinear2d, align_corners=False, scale_factor given: src = (dst + 0.5)/s - 0.5 clamped at 0.  Value of output pixel
+// (yo, xo) of the H x W plane p enlarged by s = 1 / rs,
+//     hy (hx p[y0][x0] + lx p[y0][x1]) + ly (hx p[y1][x0] + lx p[y1][x1]),
+// shared by bilinear_up_kernel and cond_dwt_kernel.  Which products are rounded and which are fused is written out (contraction is off
+// inside): left to the compiler it depends on the code around the expression, and the two kernels have to agree to the bit.
+__device__ __forceinline__ float bilinear_at(const float* __restrict__ p, int H, int W, float rs, int yo, int xo) {
+#pragma clang fp contract(off)
+    float sy = __builtin_fmaf((float)yo + 0.5f, rs, -0.5f); sy = sy < 0.f ? 0.f : sy;
+    float sx = __builtin_fmaf((float)xo + 0.5f, rs, -0.5f); sx = sx < 0.f ? 0.f : sx;
+    const int y0 = (int)sy, x0 = (int)sx;
+    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+    const float ly = sy - (float)y0, lx = sx - (float)x0;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float t0 = __builtin_fmaf(lx, p[(int64_t)y0 * W + x1], hx * p[(int64_t)y0 * W + x0]);
+    const float t1 = __builtin_fmaf(hx, p[(int64_t)y1 * W + x0], lx * p[(int64_t)y1 * W + x1]);
+    return hy * t0 + ly * t1;
+}
+
 __global__ void bilinear_up_kernel(const float* __restrict__ src, int64_t src_bs, float* __restrict__ dst,
                                    int64_t dst_bs, int C, int H, int W, int s, int64_t total) {
-    // PyTorch upsample_bilinear2d, align_corners=False, scale_factor given: src = (dst + 0.5)/s - 0.5 clamped at 0
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int Wo = W * s, Ho = H * s;
     const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho);
     const int c = (int)((i / ((int64_t)Wo * Ho)) % C), b = (int)(i / ((int64_t)Wo * Ho * C));
     const float rs = 1.f / (float)s;
-    float sy = ((float)yo + 0.5f) * rs - 0.5f; sy = sy < 0.f ? 0.f : sy;
-    float sx = ((float)xo + 0.5f) * rs - 0.5f; sx = sx < 0.f ? 0.f : sx;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
     const float* p = src + (int64_t)b * src_bs + (int64_t)c * H * W;
-    const float v = hy * (hx * p[(int64_t)y0 * W + x0] + lx * p[(int64_t)y0 * W + x1]) +
-                    ly * (hx * p[(int64_t)y1 * W + x0] + lx * p[(int64_t)y1 * W + x1]);
-    dst[(int64_t)b * dst_bs + ((int64_t)c * Ho + yo) * Wo + xo] = v;
+    dst[(int64_t)b * dst_bs + ((int64_t)c * Ho + yo) * Wo + xo] = bilinear_at(p, H, W, rs, yo, xo);
+}
+
+// quat_dwt(bilinear_up(cond, s)) of the Stage-I conditions (R,3,H,W) without the enlarged image: a thread owns NPX neighbouring pixels of a
+// row of the (R,32,H s/2,W s/2) output, interpolates their 2 x 2 NPX x 3 samples from the candidate's 3 H W source values (12 KiB of
+// conditions per 8 MiB of output: every read after the first is an L1 hit), and writes each of the 32 planes with one 4 NPX-byte store.
+template <int NPX>
+__global__ __launch_bounds__(256) void cond_dwt_kernel(const float* __restrict__ cond, float* __restrict__ out, int H, int W, int s, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int h2 = (H * s) >> 1, w2 = (W * s) >> 1, wq = w2 / NPX;
+    const int x = (int)(i % wq) * NPX, y = (int)((i / wq) % h2), b = (int)(i / ((int64_t)wq * h2));
+    const float rs = 1.f / (float)s;
+    const float* p = cond + (int64_t)b * 3 * H * W;
+    const int HW = H * W;
+    float q[NPX][8][4];
+#pragma unroll
+    for (int j = 0; j < NPX; ++j)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int yy = 2 * y + (t & 1), xx = 2 * (x + j) + (t >> 1);
+            quat_stack(bilinear_at(p, H, W, rs, yy, xx), bilinear_at(p + HW, H, W, rs, yy, xx), bilinear_at(p + 2 * HW, H, W, rs, yy, xx), q[j], t);
+        }
+    typedef float fpx __attribute__((ext_vector_type(NPX)));
+    const int64_t hw2 = (int64_t)h2 * w2;
+    float* o = out + (int64_t)b * 32 * hw2 + (int64_t)y * w2 + x;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        float v[NPX][4];
+#pragma unroll
+        for (int j = 0; j < NPX; ++j) haar_bands(q[j][c], v[j]);
+#pragma unroll
+        for (int band = 0; band < 4; ++band) {
+            fpx w;
+#pragma unroll
+            for (int j = 0; j < NPX; ++j) w[j] = v[j][band];
+            *reinterpret_cast<fpx*>(o + (int64_t)(8 * band + c) * hw2) = w;
+        }
+    }
 }
 
 __global__ void space_to_depth_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W,
@@ -743,6 +802,22 @@ extern "C" int bem_quat_dwt_f32(const float* rgb, int64_t x_bstride, float* out,
     const int64_t total = (int64_t)B * (H / 2) * (W / 2);
     quat_dwt_kernel<<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(rgb, x_bstride, out, H, W, total);
     return bem_check_launch("quat_dwt");
+}
+
+extern "C" int bem_cond_dwt_f32(const float* cond, float* out, int R, int H, int W, int s, void* stream) {
+    BEM_REQUIRE(cond && out, "cond_dwt: null tensor");
+    BEM_REQUIRE(R >= 0 && H > 0 && W > 0 && s >= 1 && (int64_t)H * s < (1 << 24) && (int64_t)W * s < (1 << 24) && (H * s) % 2 == 0 && (W * s) % 2 == 0,
+                "cond_dwt: the enlarged image (%d x %d times %d) must have even sides", H, W, s);
+    if (R == 0) return BEM_OK;
+    const int h2 = H * s / 2, w2 = W * s / 2;
+    if (w2 % 4 == 0 && ((uintptr_t)out & 15) == 0) {
+        const int64_t total = (int64_t)R * h2 * (w2 / 4);
+        cond_dwt_kernel<4><<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(cond, out, H, W, s, total);
+    } else {
+        const int64_t total = (int64_t)R * h2 * w2;
+        cond_dwt_kernel<1><<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(cond, out, H, W, s, total);
+    }
+    return bem_check_launch("cond_dwt");
 }
 
 extern "C" int bem_dwt_f32(const float* x, float* out, int B, int C, int H, int W, void* stream) {

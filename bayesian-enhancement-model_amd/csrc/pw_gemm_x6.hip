@@ -901,7 +901,7 @@ namespace {
 struct CvX {
     const float* x; int64_t x_bs;
     const u32x4* Wp; const float* bias; const float* res1; const float* res2; float* out;
-    int Cin, H, W, Ho, Wo, Cout, KB, MT, relu, pad, dil;
+    int Cin, H, W, Ho, Wo, Cout, KB, MT, relu, pad, dil, res1_rep;
 };
 
 template <int MTW, int KH, int KW, int S>
@@ -1004,7 +1004,7 @@ __global__ __launch_bounds__(256, 2) void conv_taps_x6_kernel(CvX k) {
     const float lo = k.relu ? 0.f : -3.402823466e38f;
     const uint32_t loff = (uint32_t)(4 * kh) * (uint32_t)Lo + (uint32_t)pc;
     float* outb = k.out + (int64_t)b * k.Cout * Lo;
-    const float* r1b = k.res1 ? k.res1 + (int64_t)b * k.Cout * Lo : nullptr;
+    const float* r1b = k.res1 ? k.res1 + (int64_t)(b / k.res1_rep) * k.Cout * Lo : nullptr;      // one residual row per res1_rep output rows
     const float* r2b = k.res2 ? k.res2 + (int64_t)b * k.Cout * Lo : nullptr;
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
@@ -1037,8 +1037,9 @@ __global__ __launch_bounds__(256, 2) void conv_taps_x6_kernel(CvX k) {
 }  // namespace
 
 static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                            float* out, int B, int Cin, int H, int W, int Cout, int KH, int stride, int dil, int relu, void* stream, const char* what) {
-    BEM_REQUIRE(x && Wp && out, "%s: null tensor", what);
+                            float* out, int B, int Cin, int H, int W, int Cout, int KH, int stride, int dil, int relu, int res1_rep, void* stream,
+                            const char* what) {
+    BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "%s: null tensor or res1_rep < 1", what);
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", what);
     BEM_REQUIRE((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1),
                 "%s: supported forms are 3x3 s1 (dilation 1 / 2, padding = dilation) and 3x3 s2 p1", what);
@@ -1051,7 +1052,7 @@ static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, 
     if (B == 0) return BEM_OK;
     CvX k;
     k.x = x; k.x_bs = x_bstride; k.Wp = reinterpret_cast<const u32x4*>(Wp); k.bias = bias; k.res1 = res1; k.res2 = res2; k.out = out;
-    k.Cin = Cin; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.Cout = Cout; k.KB = cdiv(Cin, 16); k.MT = cdiv(Cout, 32); k.relu = relu; k.pad = pad; k.dil = dil;
+    k.Cin = Cin; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.Cout = Cout; k.KB = cdiv(Cin, 16); k.MT = cdiv(Cout, 32); k.relu = relu; k.pad = pad; k.dil = dil; k.res1_rep = res1_rep;
     const int mtw = k.MT == 1 ? 1 : 2;
     dim3 grid(cdiv(Ho * Wo, 256), cdiv(k.MT, mtw), B);
     hipStream_t s = (hipStream_t)stream;
@@ -1068,18 +1069,18 @@ static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, 
 extern "C" int bem_conv4x4s2_fast_supported(int Cin, int H, int W);
 extern "C" int bem_conv3x3_rows_supported(int Cin, int H, int W);
 int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2, float* out,
-                     int B, int Cin, int H, int W, int Cout, int relu, void* stream);                    // conv_rows_x6.hip
+                     int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream);      // conv_rows_x6.hip
 static bool rows_aligned(const float* x, int64_t x_bstride, const float* out, const float* res1, const float* res2) {
     return x && out && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 15) == 0 && x_bstride % 4 == 0;
 }
 
 extern "C" int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                                  const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream) {
+                                  const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream) {
     // the row form (conv_rows_x6.hip) where the shape allows; nine shifted taps otherwise (BEM_CONV3_ROWS=0: always)
     static const bool rows = !(getenv("BEM_CONV3_ROWS") && atoi(getenv("BEM_CONV3_ROWS")) == 0);
     if (rows && Cin > 0 && bem_conv3x3_rows_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2))
-        return conv_rows_launch(3, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, stream);
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, 3, 1, 1, relu, stream, "conv3x3_x6");
+        return conv_rows_launch(3, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, res1_rep, stream);
+    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, 3, 1, 1, relu, res1_rep, stream, "conv3x3_x6");
 }
 
 
@@ -1088,10 +1089,11 @@ extern "C" int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const flo
     // the row form (conv_rows_x6.hip); shapes outside it (bem_conv4x4s2_fast_supported == 0) belong to bem_conv2d_mfma_f32
     BEM_REQUIRE(Cin > 0 && bem_conv4x4s2_fast_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2),
                 "conv4x4s2_x6: needs W = 2 Wo with Wo a power of two <= 64, even H, Cin %% 8 == 0 and 16-byte aligned tensors");
-    return conv_rows_launch(4, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, stream);
+    return conv_rows_launch(4, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, 1, stream);
 }
 
 extern "C" int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                                    float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, void* stream) {
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, K, stride, dilation, relu, stream, "conv_taps_x6");
+                                    float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
+                                    void* stream) {
+    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, K, stride, dilation, relu, res1_rep, stream, "conv_taps_x6");
 }

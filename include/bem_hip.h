@@ -179,22 +179,24 @@ int bem_dwconv3x3_f32(const float* x, const float* w, int64_t w_bstride, const f
 /* Dense direct convolution KHxKW, given stride / zero padding (nn.Conv2d semantics), optional bias,
  * ReLU and up to two residual tensors added after the activation:
  *   out = relu?(conv(x) + bias) + res1 + res2.      x (B,Cin,H,W) -> out (B,Cout,Ho,Wo)
- * x may be a channel slice of a wider tensor: x_bstride = elements between batch items. */
+ * x may be a channel slice of a wider tensor: x_bstride = elements between batch items.
+ * res1_rep >= 1 (here and in the convolutions below): output row b adds res1 row b / res1_rep, so res1 has B / res1_rep rows -- a term
+ * that is the same for the res1_rep Monte-Carlo samples of an image is computed once per image.  1: one residual row per output row. */
 int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w, const float* bias, const float* res1,
                    const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                   int stride, int pad, int relu, void* stream);
+                   int stride, int pad, int relu, int res1_rep, void* stream);
 
 /* The same convolution as an implicit GEMM on the f32 matrix cores; Wp = the (Cout, Cin*KH*KW) view of the weight
  * packed by bem_pack_pw_weight_f32.  Cout <= 160; 3x3 stride 1 and 4x4 stride 2. */
 int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
                         const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                        int stride, int pad, int relu, void* stream);
+                        int stride, int pad, int relu, int res1_rep, void* stream);
 
 /* The 3x3 stride-1 pad-1 case as nine shifted 1x1 taps on the bf16-limb GEMM (see bem_pw_gemm_x6_f32): no im2col patch,
  * f32-level error.  Wp = bem_pack_pw_weight_x6 of the (9, Cout, Cin) tap matrices, tap = ky*3 + kx (nsets = 9).
  * W even, Cin % 8 == 0; x_bstride as above; out = relu?(conv + bias) + res1 + res2. */
 int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                       const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream);
+                       const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream);
 /* The 4x4 stride-2 pad-1 down-sampling convolution (DecompDualBranchDDWavelet_arch.py:40-41) on the same machinery, tap = ky*4 + kx; even output
  * width, Cin % 8 == 0.  Shapes bem_conv4x4s2_fast_supported accepts (W = 2 Wo with Wo a power of two <= 64, even H; x and x_bstride 16-byte
  * aligned; no residual inputs) run the coalesced-row kernel of conv4_x6.hip: one aligned 16-byte load per lane, channel and input row, the two
@@ -210,7 +212,8 @@ int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const float* Wp, con
  * branch convolutions of QD/model2.py:171-181), 3x3 s2 d1 (pad 1: down_conv of QD/model3.py:176), 4x4 s2 d1 (pad 1).  Wp as above
  * (K*K tap matrices, tap = ky*K + kx). */
 int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                         float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, void* stream);
+                         float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Quaternion / Haar primitives (basicsr/QD/model4.py:7-37,216-232; QD/quaternion.py:3-17).
@@ -218,6 +221,9 @@ int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, con
 /* RGB (B,3,H,W; x_bstride elements between batch items) -> quaternion stack (8 ch) -> Haar DWT
  * -> out (B,32,H/2,W/2), channel = band*8 + q, bands LL,HL,LH,HH. */
 int bem_quat_dwt_f32(const float* rgb, int64_t x_bstride, float* out, int B, int H, int W, void* stream);
+/* bem_quat_dwt_f32 of bem_bilinear_up_f32(cond, s) in one pass, bit for bit, without the enlarged image in memory: the Stage-I conditions
+ * cond (R,3,H,W) -> out (R,32,H*s/2,W*s/2); H*s and W*s even. */
+int bem_cond_dwt_f32(const float* cond, float* out, int R, int H, int W, int s, void* stream);
 int bem_dwt_f32(const float* x, float* out, int B, int C, int H, int W, void* stream);
 int bem_iwt_f32(const float* x, float* out, int B, int C4, int H, int W, void* stream);
 /* IWT of q1w, q2w (B,16,h,w) + Hamilton product, real part dropped -> out (B,3,2h,2w).
