@@ -851,7 +851,7 @@ class Network(nn.Module):
             set_module_paths(self)
             x = x.contiguous()
             bank = None
-            if ctx.eps is None and ctx.nsets > 1 and os.environ.get("BEM_EVAL_SAMPLE_BANK", "1") != "0":
+            if ctx.eps is None and ctx.nsets > 1:
                 from .modules import EvalSampleBank
                 bank = self.__dict__.get("_eval_bank")
                 if bank is None:

@@ -9,7 +9,6 @@ the modules run under ``torch.no_grad`` semantics (outputs carry no autograd gra
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict, List, Optional
 
 import torch
@@ -38,9 +37,6 @@ class _Cache:
             val = fn()
         self._d[key] = (sig, val)
         return val
-
-
-SCAN_RM = os.environ.get("BEM_SCAN_RM", "1") != "0"          # row-major SS2D scan (no transposes of xc / y1) where the plane size allows
 
 
 def grad_mode(m: nn.Module) -> bool:
@@ -740,7 +736,7 @@ class SS2D(nn.Module):
         wall, dtw, dtb, A, Ds = self._scan_params()
         lnw, lnb = norm.weight.detach(), norm.bias.detach()
         # row-major scan (d_state = 1): no transposed copy of xc, y1 comes back row-major (the column orientation goes through LDS)
-        rm = N == 1 and SCAN_RM and ops.ss2d_scan_rm_supported(H, W, R)
+        rm = N == 1 and ops.ss2d_scan_rm_supported(H, W, R)
         # LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel (bem_ss2d_front_x6_f32).  The in_proj output t stays in
         # LDS, so never with keep.  At d_state = 1 it is taken only ahead of the row-major scan: it was wired into that branch
         # alone when it was added, no reason for leaving the transposed-plane scan out is recorded; d_state > 1 has no such condition.

@@ -314,13 +314,9 @@ def _chk_packed1(op, weights):
             raise ValueError(f"{op}: {nm} {tuple(Wp.shape)} does not match M={M} K={K} (x6 format, one weight set)")
 
 
-# SS2D front half (LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj) in one kernel for C <= 48, deterministic weights.  BEM_SS2D_FRONT=0
-# restores the three-kernel chain.
-SS2D_FRONT = os.environ.get("BEM_SS2D_FRONT", "1") != "0"
-
-
+# SS2D front half (LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj) in one kernel, deterministic weights; wider blocks run the three-kernel chain.
 def ss2d_front_supported(C, Mx):
-    return SS2D_FRONT and C <= 48 and C % 8 == 0 and Mx <= 32
+    return C <= 48 and C % 8 == 0 and Mx <= 32
 
 
 def ss2d_front(x, ln_w, ln_b, ln_eps, Wp_in, bias_in, dww, dwb, Wp_x, Mx):
@@ -330,7 +326,7 @@ def ss2d_front(x, ln_w, ln_b, ln_eps, Wp_in, bias_in, dww, dwb, Wp_x, Mx):
         _chk(t, n_)
     _chk(bias_in, "bias_in", optional=True); _chk(dwb, "dwb", optional=True)
     B, C, H, W = x.shape
-    if not (C <= 48 and C % 8 == 0 and Mx <= 32):
+    if not ss2d_front_supported(C, Mx):
         raise ValueError(f"ss2d_front: C = {C} (<= 48, % 8) / Mx = {Mx} (<= 32) not supported")
     if ln_w.numel() != C or ln_b.numel() != C or dww.numel() != 9 * C or (dwb is not None and dwb.numel() != C) or (bias_in is not None and bias_in.numel() != C):
         raise ValueError("ss2d_front: parameter shapes")
@@ -351,13 +347,9 @@ def gate_interleave(Hd, device):
     return (s_ * Hd + 16 * j + c).reshape(-1)
 
 
-# the fully fused gdMlp branch (bem_gdmlp_x6_f32): C <= GDMLP_X6_MAXC, deterministic weights.  BEM_GDMLP_X6=0 restores the chains.
-GDMLP_X6 = os.environ.get("BEM_GDMLP_X6", "1") != "0"
-GDMLP_X6_MAXC = int(os.environ.get("BEM_GDMLP_X6_MAXC", "80"))
-
-
+# the fully fused gdMlp branch (bem_gdmlp_x6_f32), deterministic weights; wider blocks run the kernel chains.
 def gdmlp_x6_supported(C, Hd):
-    return GDMLP_X6 and C <= GDMLP_X6_MAXC and Hd % 16 == 0
+    return C <= 80 and Hd % 16 == 0
 
 
 def dw_gate_params10(dww, dwb, Hd):
@@ -376,7 +368,7 @@ def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, 
         _chk(t, n_)
     _chk(bias_out, "bias_out", optional=True)
     B, C, H, W = x.shape
-    if not (C <= 80 and Hd % 16 == 0):
+    if not gdmlp_x6_supported(C, Hd):
         raise ValueError(f"gdmlp_x6: C = {C} (<= 80) / Hd = {Hd} (% 16) not supported")
     if tuple(dw10.shape) != (Hd, 10, 2):
         raise ValueError("gdmlp_x6: depthwise parameters must come from dw_gate_params10")
@@ -414,7 +406,7 @@ def dwconv3x3(x, w, bias=None, mode=0):
 
 
 _CONV_PACK = {}          # (data_ptr, version, shape) -> packed (Cout, Cin*KH*KW) weight for the MFMA conv
-USE_CONV_MFMA = __import__("os").environ.get("BEM_CONV_MFMA", "1") != "0"
+USE_CONV_MFMA = True
 
 
 def _packed_conv_weight(w):
@@ -430,11 +422,8 @@ def _packed_conv_weight(w):
 
 
 _CONV_PACK_X6 = {}       # same keys -> (9 taps, x6-packed (Cout, Cin)) weights for the shifted-tap 3x3 convolution
-USE_CONV_X6 = __import__("os").environ.get("BEM_CONV_X6", "1") != "0"
-# the 16-tap form of the 4x4 stride-2 convolution measured no faster than the f32-MFMA im2col kernel (504 vs 537 us at 40 -> 80): off by default
-# 4x4 stride-2 down-sampling convs on the x6 matrix-core kernel with coalesced row loads and LDS-staged tap weights (conv4_x6.hip);
-# BEM_CONV4_FAST=0 restores the f32-MFMA im2col kernel
-CONV4_FAST = __import__("os").environ.get("BEM_CONV4_FAST", "1") != "0"
+USE_CONV_X6 = True
+# 4x4 stride-2 convs take the coalesced-row x6 kernel (conv_rows_x6.hip) where bem_conv4x4s2_fast_supported allows, the f32-MFMA im2col kernel otherwise
 
 
 def _packed_conv_weight_x6(w):
@@ -492,7 +481,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
         return out
-    conv4_fast = CONV4_FAST and (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
+    conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
     if conv4_fast:
         # the coalesced-row form (conv_rows_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
@@ -1428,7 +1417,7 @@ def dwact_bwd(t, w, bias, dout, dw, dbias, mode):
 WGRAD_X6 = os.environ.get("BEM_WGRAD_X6", "1") != "0"      # 1x1 weight gradients on the bf16 matrix cores (no LDS transposes) when L % 32 == 0
 # below this many pixels per launch the x6 form's fixed costs (one wave per SIMD, second reduction launch) lose to the f32-MFMA kernel:
 # Stage-I training (8 x 8 planes) 34.7 -> 23.8 ms per step
-WGRAD_X6_MIN_PIXELS = int(os.environ.get("BEM_WGRAD_X6_MIN_PIXELS", "16384"))
+WGRAD_X6_MIN_PIXELS = 16384
 _WGX_WS = {}                                               # per-device scratch of the x6 weight-gradient kernel (stream-ordered reuse)
 
 

@@ -1,7 +1,6 @@
 // Spatial convolutions: depthwise 3x3 (with fused SiLU / gated-GELU / PostSmooth epilogues) and a
 // dense direct convolution (3x3 s1, 4x4 s2, ...) staged through LDS.
 #include "bem_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -610,13 +609,10 @@ extern "C" int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const floa
 #define BEM_CONV_LAUNCH(KH_, KW_, S_, MTW_) \
     conv2d_mfma_kernel<KH_, KW_, S_, MTW_><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep)
     if (KH == 3 && KW == 3 && stride == 1) {
-        static const bool pipe = !(getenv("BEM_CONV_PIPE") && getenv("BEM_CONV_PIPE")[0] == '0');
-        if (MT <= 2 && pipe) {
+        if (MT <= 2) {
             if (MT == 1) conv2d_mfma_pipe_kernel<3, 3, 1, 1><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
             else conv2d_mfma_pipe_kernel<3, 3, 1, 2><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
         }
-        else if (MT == 1) BEM_CONV_LAUNCH(3, 3, 1, 1);
-        else if (MT == 2) BEM_CONV_LAUNCH(3, 3, 1, 2);
         else if (MT == 3) BEM_CONV_LAUNCH(3, 3, 1, 3);
         else BEM_CONV_LAUNCH(3, 3, 1, 5);
     } else if (KH == 4 && KW == 4 && stride == 2) {

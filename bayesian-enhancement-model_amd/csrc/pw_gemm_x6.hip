@@ -24,7 +24,6 @@
 //     "stream" kernel (no LayerNorm, any K): x is streamed k-block by k-block, one block ahead of the MFMAs.
 #include "bem_common.h"
 #include "x6_common.h"
-#include <stdlib.h>
 #include <algorithm>
 
 namespace {
@@ -146,10 +145,10 @@ __device__ __forceinline__ void x6_epilogue_generic(const PwX& k, int b, int mt0
 
 // out_mode 0 epilogue with the address arithmetic kept off the vector ALU: a row's plane base is wave-uniform (scalar
 // registers), the lane contributes one 32-bit element offset computed once (its pixel and its 4-row half), so a store
-// is `global_store v_off, v_data, s[base]`; the 16 bias values of an M-tile come as four LDS float4 reads.  PReLU and
+// is `global_store v_off, v_data, s[base]`; the 16 bias values of an M-tile arrive in registers (x6_load_bias).  PReLU and
 // the residual are compile-time variants (chosen by uniform branches in x6_epilogue): without them a value costs one add.
 template <int MTW, int NSUB, bool VEC, bool ACT, bool RES>
-__device__ __forceinline__ void x6_epilogue_rows(const PwX& k, int b, int mt0, int p, const bool (&keep)[NSUB], int kh, const float* s_bias,
+__device__ __forceinline__ void x6_epilogue_rows(const PwX& k, int b, int mt0, int p, const bool (&keep)[NSUB], int kh,
                                                  const float4 (&bq)[MTW][4], const f32x16 (&acc)[MTW][NSUB]) {
     const float slope = ACT ? k.prelu[0] : 0.f;
     const int pv = VEC ? (keep[0] ? p : 0) : min(p, k.L - 1);
@@ -162,25 +161,10 @@ __device__ __forceinline__ void x6_epilogue_rows(const PwX& k, int b, int mt0, i
         const int rb = (mt0 + m) * 32;                        // uniform
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-#ifdef BEM_X6_BIAS_LDS      // A/B diagnostic builds only (make dbg, scripts/x6_bias_ab.py): bias read back from LDS
-#if BEM_X6_BIAS_LDS == 2      // 2: four separate dword reads, all retired (lgkmcnt(0)) before the first use
-            const float* sb = s_bias + rb + 8 * g + 4 * kh;
-            const float4 b4 = make_float4(sb[0], sb[1], sb[2], sb[3]);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-#elif BEM_X6_BIAS_LDS >= 3    // 3: one 16-byte read retired before the first use (the builtin keeps the compiler from sinking components); 4: + scalar adds
-            const float4 b4 = *reinterpret_cast<const float4*>(s_bias + rb + 8 * g + 4 * kh);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-#else                         // 1: the round-1 form: the compiler sinks the components into the conditional row blocks as
-                              //    ds_read2_b32 + 2 x ds_read_b32 and waits for them with COUNTED lgkmcnt(1) / lgkmcnt(0)
-            const float4 b4 = *reinterpret_cast<const float4*>(s_bias + rb + 8 * g + 4 * kh);
-#endif
-            const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#else
             // through a VALU copy: a packed add that takes the HIGH register of a freshly loaded pair for its LOW result read the pair's
             // pre-load content in lanes 48..63 (round 3: the M = 32, K = 64 attention-fuse GEMM at 280 workgroups, scripts/dbg_gemm_cat.py;
             // round 2 saw the same with LDS-loaded pairs) -- DESIGN.md section 6.4, scripts/isa_audit.py check 2
             const float bv[4] = {valu_copy(bq[m][g].x), valu_copy(bq[m][g].y), valu_copy(bq[m][g].z), valu_copy(bq[m][g].w)};
-#endif
             float rv[4][NSUB];
             if (RES) {
 #pragma unroll
@@ -205,9 +189,6 @@ __device__ __forceinline__ void x6_epilogue_rows(const PwX& k, int b, int mt0, i
 #pragma unroll
                 for (int t = 0; t < NSUB; ++t) {
                     o[t] = acc[m][t][r] + bv[i];
-#if defined(BEM_X6_BIAS_LDS) && BEM_X6_BIAS_LDS == 4    // diagnostic: keep the two adds of a row scalar (no v_pk_add_f32)
-                    asm volatile("" : "+v"(o[t]));
-#endif
                     if (ACT) o[t] = o[t] >= 0.f ? o[t] : slope * o[t];
                     if (RES) o[t] += rv[i][t];
                 }
@@ -259,10 +240,10 @@ __device__ __forceinline__ void x6_epilogue(const PwX& k, int b, int mt0, int p,
                                             const float* __restrict__ s_bias, const float4 (&bq)[MTW][4], const f32x16 (&acc)[MTW][NSUB]) {
     if (k.out_mode != 0 || k.M < 8) { x6_epilogue_generic<MTW, NSUB, VEC>(k, b, mt0, p, keep, kh, s_bias, acc); return; }
     const bool act = k.act == 1, res = k.res != nullptr;      // uniform
-    if (!act && !res) x6_epilogue_rows<MTW, NSUB, VEC, false, false>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
-    else if (!act) x6_epilogue_rows<MTW, NSUB, VEC, false, true>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
-    else if (!res) x6_epilogue_rows<MTW, NSUB, VEC, true, false>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
-    else x6_epilogue_rows<MTW, NSUB, VEC, true, true>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
+    if (!act && !res) x6_epilogue_rows<MTW, NSUB, VEC, false, false>(k, b, mt0, p, keep, kh, bq, acc);
+    else if (!act) x6_epilogue_rows<MTW, NSUB, VEC, false, true>(k, b, mt0, p, keep, kh, bq, acc);
+    else if (!res) x6_epilogue_rows<MTW, NSUB, VEC, true, false>(k, b, mt0, p, keep, kh, bq, acc);
+    else x6_epilogue_rows<MTW, NSUB, VEC, true, true>(k, b, mt0, p, keep, kh, bq, acc);
 }
 
 // bias of this batch row -> LDS (zeros without a bias); M <= BEM_X6_MAXM
@@ -847,9 +828,7 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
     // one M-tile at a time where a wave holds two sub-tiles: the accumulator pairs double the register cost of an M-tile
     if (k.KB <= 3) BEM_X6_RES(3, 2, 1);
     if (ln && k.KB <= 5) BEM_X6_RES(5, 2, 1);
-    static const bool res10 = !(getenv("BEM_X6_RES10") && atoi(getenv("BEM_X6_RES10")) == 0);       // A/B: the two-sweep streaming form instead
-    static const bool reslds = !(getenv("BEM_X6_RES_LDS") && atoi(getenv("BEM_X6_RES_LDS")) == 0);   // A/B: every wave streams its own weights from L2
-    if (ln && k.KB == 10 && k.K == 160 && k.MT >= 8 && res10 && reslds && (int64_t)a->B * cdiv(a->L, 32) >= 2048) {
+    if (ln && k.KB == 10 && k.K == 160 && k.MT >= 8 && (int64_t)a->B * cdiv(a->L, 32) >= 2048) {
         // many M-tiles over a full-width K and enough pixels that a workgroup walks all of them: an M-tile's weights go through LDS once per
         // workgroup (pw_x6_res_lds_kernel; level-2 project_in 335 -> 188 us).  With few pixels (Stage I) M is sliced over grid.y and the
         // per-wave streaming form below is the faster one (50 vs 63 us).
@@ -859,16 +838,13 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
         else pw_x6_res_lds_kernel<10, true, false><<<grid, 256, 0, s>>>(k);
         return bem_check_launch("pw_x6_res_lds");
     }
-    if (ln && k.KB <= 10 && res10) { if (k.MT == 1) BEM_X6_RES(10, 1, 1); else BEM_X6_RES(10, 1, 2); }
+    if (ln && k.KB <= 10) { if (k.MT == 1) BEM_X6_RES(10, 1, 1); else BEM_X6_RES(10, 1, 2); }
 #undef BEM_X6_RES
     {
-        // M-tiles per pass over x: every extra grid.y slice re-reads the input.  Two with 64-pixel waves; for exactly three
-        // M-tiles (level-1 project_out, M = 80) three with 32-pixel waves -- half the bytes per load / store instruction,
-        // but x is read once instead of twice
-        // (measured: 227 us vs 219 us for the two-slice form at K = 320, M = 80, 64x64 -- the re-read is served by L2; kept off)
-        const bool three = false && k.MT == 3 && !ln;
-        const int mtw = three ? 3 : (k.MT == 1 ? 1 : 2);
-        dim3 grid(cdiv(a->L, three ? 128 : 256), cdiv(k.MT, mtw), a->B);
+        // two M-tiles per pass over x with 64-pixel waves; every further grid.y slice re-reads the input from L2 (three M-tiles per pass
+        // with 32-pixel waves measured 227 us against 219 us for this form at K = 320, M = 80, 64x64)
+        const int mtw = k.MT == 1 ? 1 : 2;
+        dim3 grid(cdiv(a->L, 256), cdiv(k.MT, mtw), a->B);
 #define BEM_X6_STREAM(MTW, LN)                                                                \
     do {                                                                                      \
         if (vec && !sum) pw_x6_stream_kernel<MTW, 2, false, true, LN><<<grid, 256, 0, s>>>(k);   \
@@ -876,11 +852,7 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
         else if (!sum) pw_x6_stream_kernel<MTW, 2, false, false, LN><<<grid, 256, 0, s>>>(k);    \
         else pw_x6_stream_kernel<MTW, 2, true, false, LN><<<grid, 256, 0, s>>>(k);               \
     } while (0)
-        if (three) {
-            if (!sum) pw_x6_stream_kernel<3, 1, false, false, false><<<grid, 256, 0, s>>>(k);
-            else pw_x6_stream_kernel<3, 1, true, false, false><<<grid, 256, 0, s>>>(k);
-        }
-        else if (ln) { if (mtw == 1) BEM_X6_STREAM(1, true); else BEM_X6_STREAM(2, true); }
+        if (ln) { if (mtw == 1) BEM_X6_STREAM(1, true); else BEM_X6_STREAM(2, true); }
         else { if (mtw == 1) BEM_X6_STREAM(1, false); else BEM_X6_STREAM(2, false); }
 #undef BEM_X6_STREAM
     }
@@ -1076,9 +1048,8 @@ static bool rows_aligned(const float* x, int64_t x_bstride, const float* out, co
 
 extern "C" int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
                                   const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream) {
-    // the row form (conv_rows_x6.hip) where the shape allows; nine shifted taps otherwise (BEM_CONV3_ROWS=0: always)
-    static const bool rows = !(getenv("BEM_CONV3_ROWS") && atoi(getenv("BEM_CONV3_ROWS")) == 0);
-    if (rows && Cin > 0 && bem_conv3x3_rows_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2))
+    // the row form (conv_rows_x6.hip) where the shape allows; nine shifted taps otherwise
+    if (Cin > 0 && bem_conv3x3_rows_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2))
         return conv_rows_launch(3, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, res1_rep, stream);
     return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, 3, 1, 1, relu, res1_rep, stream, "conv3x3_x6");
 }

@@ -1,4 +1,4 @@
-"""The 3x3 convs of the eval step at the bench shapes: row-form x6 kernel (conv_rows_x6.hip) vs the nine shifted taps (BEM_CONV3_ROWS=0).
+"""The 3x3 convs of the eval step at the bench shapes on the row-form x6 kernel (conv_rows_x6.hip).
    python scripts/conv3_micro.py [reps]"""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesian-enhancement-model_amd"))
@@ -15,7 +15,6 @@ def timeit(fn, n=reps):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-print("BEM_CONV3_ROWS =", os.environ.get("BEM_CONV3_ROWS", "1"))
 for (B, Ci, Co, H, W) in [(64, 32, 32, 128, 128), (64, 32, 40, 128, 128), (64, 40, 16, 128, 128), (8, 32, 32, 128, 128), (16, 32, 32, 128, 128)]:
     g = torch.Generator().manual_seed(0)
     x = torch.randn(B, Ci, H, W, generator=g).cuda(); w = (torch.randn(Co, Ci, 3, 3, generator=g) * (Ci * 9) ** -0.5).cuda(); b = torch.randn(Co, generator=g).cuda()

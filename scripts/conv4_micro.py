@@ -1,5 +1,5 @@
-"""The two 4x4 stride-2 down-sampling convs of the Stage-II net at the bench shapes: coalesced-row x6 kernel (conv4_x6.hip) against the
-f32-MFMA im2col kernel it replaces (BEM_CONV4_FAST=0 in a second process).   python scripts/conv4_micro.py [reps]"""
+"""The two 4x4 stride-2 down-sampling convs of the Stage-II net at the bench shapes on the coalesced-row x6 kernel (conv_rows_x6.hip).
+   python scripts/conv4_micro.py [reps]"""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesian-enhancement-model_amd"))
 from bem import ops
@@ -15,7 +15,6 @@ def timeit(fn, n=reps):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-print("BEM_CONV4_FAST =", ops.CONV4_FAST)
 for (B, Ci, Co, H, W) in [(64, 40, 80, 128, 128), (64, 80, 160, 64, 64), (16, 40, 80, 128, 128), (16, 80, 160, 64, 64)]:
     g = torch.Generator().manual_seed(0)
     x = torch.randn(B, Ci, H, W, generator=g).cuda(); w = (torch.randn(Co, Ci, 4, 4, generator=g) * (Ci * 16) ** -0.5).cuda(); b = torch.randn(Co, generator=g).cuda()

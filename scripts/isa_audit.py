@@ -11,9 +11,9 @@ Checks (tests/test_isa_audit.py runs them as part of the CPU suite):
                    pair for its LOW result (op_sel = 1 on that source) when the pair's last writer is a memory return -- an LDS read
                    (ds_read*) or a global / buffer / scratch load (round 3: the stale-bias corruption reappeared with a
                    global_load_dwordx4 pair consumed out of place, scripts/dbg_gemm_cat.py).  On gfx950 that instruction returned the register's PRE-LOAD content in lanes 48..63 a few times per
-                   10^7 outputs when two workgroups shared a CU, with correct s_waitcnt placement (scripts/x6_bias_ab.py reproduces
-                   it with `make dbg`; LDS-loaded pairs consumed out of place -- the LayerNorm parameters of the x6 GEMMs -- ran
-                   3.8e9 outputs clean in scripts/x6_ln_stress.py).
+                   10^7 outputs when two workgroups shared a CU, with correct s_waitcnt placement (the diagnostic builds of that
+                   round reproduced it, profiles/r02_x6_bias_ab*.log; LDS-loaded pairs consumed out of place -- the LayerNorm
+                   parameters of the x6 GEMMs -- ran 3.8e9 outputs clean).
   3. asm loads     conv2d_mfma_pipe_kernel issues its operand loads from inline asm and waits for them in a separate asm
                    statement: between an asm `global_load` and the asm `s_waitcnt vmcnt(0)` no compiler instruction may read,
                    copy or spill the destination registers.
@@ -33,15 +33,14 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 # kernel-name regex (demangled) -> reason.  Everything else must have ScratchSize == 0.
 ALLOW_SCRATCH = {
-    r"conv2d_mfma_kernel<3, 3, 1": "f32-MFMA im2col 3x3: only with BEM_CONV_X6=0 / odd widths (default 3x3 path is conv_taps_x6_kernel)",
+    r"conv2d_mfma_kernel<3, 3, 1": "f32-MFMA im2col 3x3 with three or more M-tiles: only with ops.USE_CONV_X6 off / odd widths (the default 3x3 paths are the x6 row and tap kernels)",
     r"conv2d_mfma_pipe_kernel<3, 3, 1, 1>": "3x3 with Cin % 8 != 0 and Cout <= 32 (Stage-I first_conv at 16x16): 36 B, launch-bound size",
-    r"conv2d_mfma_kernel<4, 4, 2": "f32-MFMA im2col 4x4 stride-2: only for shapes the coalesced-row x6 kernel (conv4_x6.hip) does not take (output widths that are not a power of two <= 64, e.g. config 5) or BEM_CONV4_FAST=0",
+    r"conv2d_mfma_kernel<4, 4, 2": "f32-MFMA im2col 4x4 stride-2: only for shapes the coalesced-row x6 kernel (conv_rows_x6.hip) does not take (output widths that are not a power of two <= 64, e.g. config 5)",
     r"attn_fold_kernel": "one 1024-thread workgroup per image folding 8 32x32 matrices: 8 B, ~40 us per step",
     r"sample_pack_x6_kernel": "Stage-I weight sampling (Philox + Box-Muller + limb split per element, transcendental-bound): 48 B, 0.4 % of the step",
     r"pw_x6_res_lds_kernel<10": "K = 160 resident with the M-tiles' weights shared through LDS (level-2 project_in): 8-12 B parked across the LayerNorm statistics of the prologue, none in the M-tile loop",
     r"pw_x6_res_kernel<10, 1, 2": "K <= 160 with LayerNorm and all K resident (level-2 blocks, 32x32 planes): 92 B; 0.5 % of the step",
     r"pw_x6_res_kernel<(5|10), (1|2), 1, (true|false), (true|false)>": "8 B in three rarely dispatched variants (odd L / sum input at level 1-2)",
-    r"pw_x6_stream_kernel<3, 1,": "three M-tiles x one pixel sub-tile: measured variant kept for A/B, not dispatched by default",
     r"pw_x6_stream_kernel<2, 2, (true|false), false,": "VEC = false: odd plane sizes only (tests, ragged crops)",
     r"pw_x6_stream_kernel<2, 2, true, true, true>": "sum input + LayerNorm at K > 160: not reached by the shipped widths (n_feat 40: K <= 160 uses the resident kernel)",
     r"ss2d_scan_bwd_kernel<1024, 4>": "general-L fallback of the scan backward (ragged planes); the shipped plane sizes use ss2d_scan_bwd_rows_kernel",
@@ -51,7 +50,7 @@ ALLOW_SCRATCH = {
 
 # check 2 exemptions: kernel-name regex -> reason
 ALLOW_LDS_PK = {
-    r"^conv2d_kernel<": "direct VALU convolution: fallback for shapes no matrix-core kernel takes (or BEM_CONV_MFMA=0); not dispatched by the shipped nets",
+    r"^conv2d_kernel<": "direct VALU convolution: fallback for shapes no matrix-core kernel takes (or ops.USE_CONV_MFMA off); not dispatched by the shipped nets",
 }
 
 PK = re.compile(r"^v_pk_(add|mul|fma)_f32\b")

@@ -1,5 +1,5 @@
 """The 1x1 GEMMs of a level-2 VSSBlock (C = 160, 32x32 planes, 64 rows) and of level 1 (C = 80, 64x64) as the eval step calls them:
-in_proj (LayerNorm prologue), x_proj, out_proj (LayerNorm of y0 + y1, residual).   BEM_X6_RES10=0: streaming two-sweep LayerNorm form at K = 160.
+in_proj (LayerNorm prologue), x_proj, out_proj (LayerNorm of y0 + y1, residual).
    python scripts/pw_level2_micro.py [reps]"""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesian-enhancement-model_amd"))
@@ -16,7 +16,6 @@ def timeit(fn, n=reps):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-print("BEM_X6_RES10 =", os.environ.get("BEM_X6_RES10", "1"))
 B = 64
 for C, H, R in ((160, 32, 10), (80, 64, 5), (40, 128, 3)):
     g = torch.Generator().manual_seed(0)

@@ -17,4 +17,4 @@ for K, M, ln in ((40, 40, True), (40, 320, True), (40, 10, False), (160, 40, Fal
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 5
     by = 4.0 * B * H * H * (K + M)
-    print(f"K={K} M={M} ln={ln}: {dt*1e6:.0f} us  {2.0*B*H*H*K*M/dt/1e12:.1f} TF/s  {by/dt/1e12:.2f} TB/s  dbg={os.environ.get('BEM_PW_DBG','0')}")
+    print(f"K={K} M={M} ln={ln}: {dt*1e6:.0f} us  {2.0*B*H*H*K*M/dt/1e12:.1f} TF/s  {by/dt/1e12:.2f} TB/s")

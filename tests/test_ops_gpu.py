@@ -217,14 +217,19 @@ def test_pw_gemm_identity_asymmetric(ops):
     assert torch.equal(y[0, 3], 2 * x[0, 17]) and torch.equal(y[0, 39], -x[0, 0]) and y[0, 5].abs().max() == 0
 
 
-@pytest.mark.parametrize("cfg", [(2, 40, 40, 16, 12), (1, 80, 640, 8, 8), (2, 160, 80, 4, 4), (1, 16, 24, 3, 5)])
+@pytest.mark.parametrize("cfg", [(2, 40, 40, 16, 12), (1, 80, 640, 8, 8), (2, 160, 80, 4, 4), (1, 16, 24, 3, 5),
+                                 (2, 176, 40, 5, 7), (1, 168, 24, 16, 16), (2, 176, 40, 4, 6, "sum")])
 def test_pw_gemm_layernorm(ops, cfg):
-    B, K, M, H, W = cfg
+    """K <= 160: the register-resident forms.  K > 160 (any net wider than n_feat 40): the streaming form, two sweeps over x for the statistics
+    and the parameters in LDS -- first K past the resident form on a ragged odd plane with two M-tiles; a half-filled last k-block with one
+    M-tile on the vector path; the sum input."""
+    B, K, M, H, W = cfg[:5]
     g = torch.Generator().manual_seed(K + M)
     x = torch.randn(B, K, H, W, generator=g) * 2 + 0.5
     w, lw, lb = torch.randn(M, K, generator=g) * K ** -0.5, torch.randn(K, generator=g), torch.randn(K, generator=g)
-    ref = F.conv2d(O.layernorm2d_ref(x, lw, lb), w[:, :, None, None])
-    y = ops.pw_gemm(dev(x), ops.pack_pw_weight(dev(w)), M, ln=(dev(lw), dev(lb)))
+    x2 = torch.randn(B, K, H, W, generator=g) if len(cfg) > 5 else None
+    ref = F.conv2d(O.layernorm2d_ref(x if x2 is None else x + x2, lw, lb), w[:, :, None, None])
+    y = ops.pw_gemm(dev(x), ops.pack_pw_weight(dev(w)), M, x2=None if x2 is None else dev(x2), in_mode=int(x2 is not None), ln=(dev(lw), dev(lb)))
     close(y, ref, 1e-4, 3e-5, f"ln pw {cfg}")
 
 
@@ -817,7 +822,7 @@ def test_conv4x4s2_coalesced_rows(ops, cfg):
     half-filled last k-block (Cin % 16 == 8), output rows of 2 .. 64 pixels (1 .. 32 lanes per row: every DPP neighbour / padding case),
     odd output heights, a partly empty last wave, relu, a channel-slice input; against F.conv2d in float64 with the f32 run as yardstick."""
     B, Ci, Co, H, W, relu = cfg
-    assert ops.CONV4_FAST and ops.lib().bem_conv4x4s2_fast_supported(Ci, H, W) == 1
+    assert ops.lib().bem_conv4x4s2_fast_supported(Ci, H, W) == 1
     g = torch.Generator().manual_seed(Ci + Co + H + W)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, 4, 4, generator=g) * (Ci * 16) ** -0.5, torch.randn(Co, generator=g)
 
