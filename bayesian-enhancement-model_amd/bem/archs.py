@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import autograd as ag
 from . import ops
-from .modules import (Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _Cache, _need_cuda, grad_mode, make_vss_level,
+from .modules import (Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _need_cuda, grad_mode, make_vss_level,
                       set_module_paths)
 from .native import BemNativeError
 
@@ -88,7 +88,6 @@ class Decomp(nn.Module):
         if model == "model4" and not wavelet_out:
             self.smooth_q1 = nn.Module(); self.smooth_q1.conv = nn.Conv2d(4, 4, 3, padding=1, groups=4, bias=True)
             self.smooth_q2 = nn.Module(); self.smooth_q2.conv = nn.Conv2d(4, 4, 3, padding=1, groups=4, bias=True)
-        self._cache = _Cache()
 
     @classmethod
     def from_shipped(cls, model, wavelet_out):
@@ -120,14 +119,14 @@ class Decomp(nn.Module):
             ca = self.cross_attn
             aw = torch.cat([torch.cat([getattr(ca, n).weight.detach().reshape(-1), getattr(ca, n).bias.detach().reshape(-1)])
                             for n in ("q1_proj", "k2_proj", "v2_proj", "q2_proj", "k1_proj", "v1_proj", "out1", "out2")]).contiguous()
-            d = dict(co_w=self.conv_out.weight.detach()[p].contiguous(), co_b=self.conv_out.bias.detach()[p].contiguous(),
-                     sh_w=self.sharpening.weight.detach()[p][:, p].contiguous(), sh_b=self.sharpening.bias.detach()[p].contiguous(),
+            d = dict(co_w=ops.ConvWeight(self.conv_out.weight.detach()[p].contiguous()), co_b=self.conv_out.bias.detach()[p].contiguous(),
+                     sh_w=ops.ConvWeight(self.sharpening.weight.detach()[p][:, p].contiguous()), sh_b=self.sharpening.bias.detach()[p].contiguous(),
                      aw=aw, fw=self.fuse.weight.detach().reshape(32, 64).contiguous(), fb=self.fuse.bias.detach().contiguous())
             if hasattr(self, "smooth_q1"):
                 d["sm_w"] = torch.cat([self.smooth_q1.conv.weight.detach(), self.smooth_q2.conv.weight.detach()], 0).contiguous()
                 d["sm_b"] = torch.cat([self.smooth_q1.conv.bias.detach(), self.smooth_q2.conv.bias.detach()], 0).contiguous()
             return d
-        return self._cache.get("prep", srcs, prep)
+        return ops.derived(self).get("prep", srcs, prep)
 
     def forward(self, x, c0=0):
         """x (B,Ct,H,W); channels [c0, c0+3) hold the RGB image to decompose."""
@@ -147,8 +146,8 @@ class Decomp(nn.Module):
             feat = ops.add(feat, self.up_conv._forward_nograd(mid))
         dil = self.branch_q1[2].dilation[0]
         b1, b2 = self.branch_q1[2], self.branch_q2[2]
-        f1 = ops.conv2d(self.branch_q1[0](feat, relu=True), b1.weight.detach(), b1.bias.detach(), pad=dil, dilation=dil, res1=feat)
-        f2 = ops.conv2d(self.branch_q2[0](feat, relu=True), b2.weight.detach(), b2.bias.detach(), pad=dil, dilation=dil, res1=feat)
+        f1 = ops.conv2d(self.branch_q1[0](feat, relu=True), b1.conv_weight(), b1.bias.detach(), pad=dil, dilation=dil, res1=feat)
+        f2 = ops.conv2d(self.branch_q2[0](feat, relu=True), b2.conv_weight(), b2.bias.detach(), pad=dil, dilation=dil, res1=feat)
         Wp, bias = ops.attn_fold(f1, f2, P["aw"], P["fw"], P["fb"])
         fused = ops.pw_gemm(f1, Wp, 32, x2=f2, in_mode=2, bias=bias)
         out = ops.conv2d(fused, P["co_w"], P["co_b"], pad=1)
@@ -325,7 +324,7 @@ class DecompDualBranchDDWavelet(_DualBranch):
         its image half does not depend on the sample, so it is evaluated once per image; forward_decomposed adds it to the condition
         half of every sample of that image."""
         fcs = [getattr(self, "first_conv" + br) for br in ("_Q1", "_Q2")]
-        return [ops.conv2d(d_img, fc.weight_part(0, 16), fc.bias.detach(), pad=1, cin_slice=(16 * bi, 16)) for bi, fc in enumerate(fcs)]
+        return [ops.conv2d(d_img, fc.conv_weight((0, 16)), fc.bias.detach(), pad=1, cin_slice=(16 * bi, 16)) for bi, fc in enumerate(fcs)]
 
     def forward_decomposed(self, d_img, d_cond, img_index=None, p_img=None):
         """d_img (Bi,32,h,w), d_cond (B,32,h,w); img_index: None (Bi == B) or samples-per-image count
@@ -420,14 +419,13 @@ class CrossFusionBlock(nn.Module):
         super().__init__()
         self.transform = PwConv2d(ch, ch, bias=True)
         self.gate = nn.Parameter(torch.ones(1, ch, 1, 1))
-        self._cache = _Cache()
 
     def forward(self, x_src, x_tgt):
         _need_cuda(x_src)
         if grad_mode(self):                      # training: the transform as its own autograd node, then x_tgt + gate * t
             return ag.GateAddFn.apply(self.transform(x_src), self.gate, x_tgt)
         t, C = self.transform, self.transform.out_channels
-        Wp, b = self._cache.get("gated", [t.weight, t.bias, self.gate], lambda: (
+        Wp, b = ops.derived(self).get("gated", [t.weight, t.bias, self.gate], lambda: (
             ops.pack_pw_weight(ops.row_scale(t.weight.detach().reshape(C, C).contiguous(), self.gate.detach().reshape(C).contiguous())),
             ops.row_scale(t.bias.detach().contiguous(), self.gate.detach().reshape(C).contiguous())))
         return ops.pw_gemm(x_src, Wp, C, bias=b, res=x_tgt)
@@ -862,7 +860,7 @@ class Network(nn.Module):
             fea0 = self.first_conv(x)
             dec = self.subnets[0](fea0)
             # proj(fea0 + dec) = proj_nobias(fea0) + proj(dec)   (UNet_arch.py:361,470-472; conv is linear)
-            base = ops.conv2d(fea0, self.proj.weight.detach(), None, pad=1)
+            base = ops.conv2d(fea0, self.proj.conv_weight(), None, pad=1)
             out = self.proj(dec, res1=base)
             ctx.bank = None
         return [x, out]

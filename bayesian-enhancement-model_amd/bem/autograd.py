@@ -23,33 +23,6 @@ from . import ops
 from .native import BemNativeError
 from .native import check, lib
 
-WEIGHT_EPOCH = ops.WEIGHT_EPOCH      # see bem.ops: bumped by optimizer steps that rewrite parameters in place
-
-
-class _Derived:
-    """Cache of tensors derived from parameters, valid for one weight epoch and parameter version."""
-
-    def __init__(self):
-        self.d = {}
-
-    def get(self, key, srcs, fn):
-        sig = (WEIGHT_EPOCH[0],) + tuple((t.data_ptr(), ops.tensor_version(t)) for t in srcs)
-        hit = self.d.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        with torch.no_grad():
-            val = fn()
-        self.d[key] = (sig, val)
-        return val
-
-
-def _derived(holder) -> _Derived:
-    c = getattr(holder, "_bem_derived", None)
-    if c is None:
-        c = _Derived()
-        object.__setattr__(holder, "_bem_derived", c)
-    return c
-
 
 def grad_of(p: torch.Tensor) -> torch.Tensor:
     """The buffer the kernels accumulate this parameter's gradient into."""
@@ -62,7 +35,7 @@ def grad_of(p: torch.Tensor) -> torch.Tensor:
 
 def _pack(holder, key, srcs, make):
     """pack_pw_weight of ``make()`` (an (M,K) matrix), cached on ``holder``."""
-    return _derived(holder).get(key, srcs, lambda: ops.pack_pw_weight(make()))
+    return ops.derived(holder).get(key, srcs, lambda: ops.pack_pw_weight(make()))
 
 
 def _w2d(w):
@@ -228,7 +201,7 @@ class Conv2dFn(Function):
         x = x.contiguous()
         ctx.save_for_backward(x)
         ctx.holder, ctx.weight, ctx.bias, ctx.cin_slice = holder, weight, bias, cin_slice
-        return ops.conv2d(x, weight.detach(), None if bias is None else bias.detach(), stride=holder.stride[0], pad=holder.padding[0],
+        return ops.conv2d(x, holder.conv_weight(), None if bias is None else bias.detach(), stride=holder.stride[0], pad=holder.padding[0],
                           cin_slice=cin_slice)
 
     @staticmethod
@@ -244,9 +217,9 @@ class Conv2dFn(Function):
                 raise NotImplementedError("Conv2dFn: input gradient of a channel-sliced input")
             k = tuple(w.shape[2:])
             if (k, s, p) == ((3, 3), 1, 1):
-                dx = ops.conv2d(dout, _derived(h).get("flip", [w], lambda: _wflip3(w)), None, stride=1, pad=1)
+                dx = ops.conv2d(dout, ops.derived(h).get("flip", [w], lambda: ops.ConvWeight(_wflip3(w))), None, stride=1, pad=1)
             elif (k, s, p) == ((4, 4), 2, 1):
-                d4 = ops.conv2d(dout, _derived(h).get("T4", [w], lambda: _wT4(w)), None, stride=1, pad=1)
+                d4 = ops.conv2d(dout, ops.derived(h).get("T4", [w], lambda: ops.ConvWeight(_wT4(w))), None, stride=1, pad=1)
                 dx = ops.pixel_shuffle2(d4)
             else:
                 raise NotImplementedError(f"Conv2dFn: input gradient for kernel {k} stride {s} pad {p}")
@@ -291,7 +264,7 @@ class VSSBlockFn(Function):
         dg = ops.pw_gemm(dout, _pack(po, "T", [pow_], lambda: _w2d(pow_).t()), Hd)
         dh = ops.dwact_bwd(t2, dww.detach(), None if dwb is None else dwb.detach(), dg, grad_of(dww), None if dwb is None else grad_of(dwb), 2)
         del dg
-        dt2 = ops.dwconv3x3(dh, _derived(dwc).get("flip", [dww], lambda: dww.detach().flip(2, 3).contiguous()), None, mode=0)
+        dt2 = ops.dwconv3x3(dh, ops.derived(dwc).get("flip", [dww], lambda: dww.detach().flip(2, 3).contiguous()), None, mode=0)
         del dh
         dn2 = ops.pw_gemm(dt2, _pack(pi, "T", [piw], lambda: _w2d(piw).t()), C)
         dx2, nrm = ops.ln_bwd(x2, dn2, n2.weight.detach(), n2.bias.detach(), n2.eps, grad_of(n2.weight), grad_of(n2.bias), dres=dout)
@@ -328,7 +301,7 @@ class VSSBlockFn(Function):
         cv = op.conv2d
         cvw, cvb = wb(cv)
         dpre = ops.dwact_bwd(t, cvw.detach(), None if cvb is None else cvb.detach(), dxc, grad_of(cvw), None if cvb is None else grad_of(cvb), 1)
-        dt = ops.dwconv3x3(dpre, _derived(cv).get("flip", [cvw], lambda: cvw.detach().flip(2, 3).contiguous()), None, mode=0)
+        dt = ops.dwconv3x3(dpre, ops.derived(cv).get("flip", [cvw], lambda: cvw.detach().flip(2, 3).contiguous()), None, mode=0)
         del dpre, dxc
         ipw = op.in_proj
         iww, iwb = wb(ipw)

@@ -3,8 +3,9 @@
 Same class names, constructor arguments, parameter names/shapes (state-dict contract, SURVEY.md
 section 8b) and ``forward(x)`` meaning as the reference modules cited in each docstring -- but every
 forward is a sequence of hand-written gfx950 kernels (bem.ops).  There is no CPU implementation:
-calling a module on CPU tensors raises ``BemNativeError``.  Inference (forward) only in this round;
-the modules run under ``torch.no_grad`` semantics (outputs carry no autograd graph).
+calling a module on CPU tensors raises ``BemNativeError``.  In eval() mode, or with autograd disabled, a forward
+runs the inference kernels and its output carries no graph; in train() mode with autograd enabled it records the
+``bem.autograd`` nodes, whose backward is HIP kernels too.
 """
 from __future__ import annotations
 
@@ -22,23 +23,6 @@ from .native import BemNativeError
 # ------------------------------------------------------------------------------------------------
 # helpers
 # ------------------------------------------------------------------------------------------------
-class _Cache:
-    """Derived device tensors (packed / permuted weights) keyed on the source tensors' identity+version."""
-
-    def __init__(self):
-        self._d = {}
-
-    def get(self, key, srcs, fn):
-        sig = (ops.WEIGHT_EPOCH[0],) + tuple((t.data_ptr(), ops.tensor_version(t), t.device) for t in srcs)
-        hit = self._d.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        with torch.no_grad():
-            val = fn()
-        self._d[key] = (sig, val)
-        return val
-
-
 def grad_mode(m: nn.Module) -> bool:
     """True when a forward has to record the training graph: module in train() mode with autograd enabled (the reference's
     training step, image_enhancer_model.py:165-216).  Everything else runs the inference kernels only."""
@@ -122,7 +106,6 @@ class Linear2d(nn.Linear):
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
-        self._cache = _Cache()
         self.module_path = ""
 
     def _load_from_state_dict(self, state_dict, prefix, *args):
@@ -131,7 +114,7 @@ class Linear2d(nn.Linear):
         return super()._load_from_state_dict(state_dict, prefix, *args)
 
     def gemm_weights(self, B):
-        Wp = self._cache.get("p", [self.weight], lambda: ops.pack_pw_weight(self.weight.detach().contiguous()))
+        Wp = ops.derived(self).get("p", [self.weight], lambda: ops.pack_pw_weight(self.weight.detach().contiguous()))
         return Wp, (self.bias.detach() if self.bias is not None else None)
 
     def forward(self, x, **kw):
@@ -155,11 +138,10 @@ class PwConv2d(nn.Conv2d):
 
     def __init__(self, cin, cout, bias=True):
         super().__init__(cin, cout, 1, 1, 0, bias=bias)
-        self._cache = _Cache()
         self.module_path = ""
 
     def gemm_weights(self, B):
-        Wp = self._cache.get("p", [self.weight], lambda: ops.pack_pw_weight(
+        Wp = ops.derived(self).get("p", [self.weight], lambda: ops.pack_pw_weight(
             self.weight.detach().reshape(self.out_channels, self.in_channels).contiguous()))
         return Wp, (self.bias.detach() if self.bias is not None else None)
 
@@ -187,11 +169,12 @@ class Conv2dK(nn.Conv2d):
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
-        self._cache = _Cache()
 
-    def weight_part(self, c0, n):
-        """weight[:, c0:c0+n] as its own contiguous tensor, made once per weight version (it keys the packed-operand caches of ops.conv2d)."""
-        return self._cache.get(("part", c0, n), [self.weight], lambda: self.weight.detach()[:, c0:c0 + n].contiguous())
+    def conv_weight(self, part=None):
+        """ops.ConvWeight of the weight, or for ``part=(c0, n)`` of its input channels [c0, c0+n), made once per weight version."""
+        w = self.weight
+        return ops.derived(self).get(("part", part), [w], lambda: ops.ConvWeight(
+            w.detach() if part is None else w.detach()[:, part[0]:part[0] + part[1]].contiguous()))
 
     def forward(self, x, relu=False, res1=None, res2=None, cin_slice=None, res1_rep=1, w_part=None, use_bias=True):
         """``w_part=(c0, n)``: the convolution over input channels [c0, c0+n) of the weight only (a convolution is linear in its input
@@ -201,8 +184,7 @@ class Conv2dK(nn.Conv2d):
             if relu or res1 is not None or res2 is not None or w_part is not None or not use_bias:
                 raise BemNativeError("Conv2dK: the training path covers the plain convolution (+ bias) only")
             return ag.Conv2dFn.apply(x, self.weight, self.bias, self, cin_slice)
-        w = self.weight.detach() if w_part is None else self.weight_part(*w_part)
-        return ops.conv2d(x, w, self.bias.detach() if (use_bias and self.bias is not None) else None,
+        return ops.conv2d(x, self.conv_weight(w_part), self.bias.detach() if (use_bias and self.bias is not None) else None,
                           stride=self.stride[0], pad=self.padding[0], relu=relu, res1=res1, res2=res2, cin_slice=cin_slice, dilation=self.dilation[0],
                           res1_rep=res1_rep)
 
@@ -212,7 +194,6 @@ class ConvT2x2(nn.ConvTranspose2d):
 
     def __init__(self, cin, cout):
         super().__init__(cin, cout, kernel_size=2, stride=2, padding=0, output_padding=0)
-        self._cache = _Cache()
 
     def forward(self, x):
         _need_cuda(x)
@@ -227,7 +208,7 @@ class ConvT2x2(nn.ConvTranspose2d):
             w = self.weight.detach()                                  # (Cin, Cout, 2, 2)
             w4 = w.permute(2, 3, 1, 0).reshape(4 * co, self.in_channels).contiguous()   # row = (dy*2+dx)*Co + co
             return ops.pack_pw_weight(w4), self.bias.detach().repeat(4).contiguous()
-        Wp, b4 = self._cache.get("p", [self.weight, self.bias], prep)
+        Wp, b4 = ops.derived(self).get("p", [self.weight, self.bias], prep)
         return ops.pw_gemm(x, Wp, 4 * co, bias=b4, convT_Win=x.shape[3])
 
 
@@ -240,7 +221,6 @@ class _BayesBase(nn.Module):
         self.decay, self.sigma_init, self.step = decay, sigma_init, 0
         self.bias = bias
         self.module_path = ""
-        self._cache = _Cache()
 
     def _rho_init(self):
         return math.log(math.expm1(abs(self.sigma_init)) + 1e-20)
@@ -305,7 +285,7 @@ class _BayesBase(nn.Module):
 
     def _sigma(self):
         rho = self.rho_weight
-        return self._cache.get("sigma", [rho], lambda: ops.bnn_sample(torch.zeros_like(rho), rho.detach(), 1, torch.ones_like(rho))[0])
+        return ops.derived(self).get("sigma", [rho], lambda: ops.bnn_sample(torch.zeros_like(rho), rho.detach(), 1, torch.ones_like(rho))[0])
 
     def _sampled(self, B, packed_mk=None):
         """(weights (nsets,*shape), bias (nsets,C)|None, nsets) for this forward; with ``packed_mk = (M, K)`` the sampled
@@ -471,8 +451,7 @@ class BayesBank:
             ops.pack_pw_weight_jobs(self.jobs, self.jblks, self.njblk, self.parena)
             for m, fwd, tr in self.packs:
                 m.__dict__["_bank_wp"] = (step, fwd)                                        # gemm_weights of this training forward
-                wv = m.__dict__["_bank_wv"]
-                ag._derived(m).d["T"] = ((ops.WEIGHT_EPOCH[0], (wv.data_ptr(), ops.tensor_version(wv))), tr)   # autograd._pack(m, "T", [w], ...) hits
+                ops.derived(m).put("T", [m.__dict__["_bank_wv"]], tr)                       # autograd._pack(m, "T", [w], ...) hits
         for m, kind, wv, ev in self.views:
             if kind == "weight":
                 m._ws, m._eps_w, m._bs, m._eps_b = wv, ev, None, None
@@ -639,7 +618,6 @@ class gdMlp(nn.Module):
         self.dwconv = DwConv2d(hidden_features * 2)
         self.project_out = PwConv2d(hidden_features, out_features)
         self.act = act_layer()
-        self._cache = _Cache()
 
     def forward_fused(self, x, norm: LayerNorm2d):
         """x + project_out(GELU(h1) * h2), h = dwconv(project_in(LN(x)))."""
@@ -657,7 +635,7 @@ class gdMlp(nn.Module):
                         ops.dw_gate_params10(dw.weight.detach(), None if dw.bias is None else dw.bias.detach(), Hd),
                         ops.pack_pw_weight(po.weight.detach().reshape(po.out_channels, Hd).contiguous(), x6=True),
                         None if po.bias is None else po.bias.detach().contiguous())
-            Wg, bg, w10, Wo, bo = self._cache.get("gdmlp_x6", [t for t in (pi.weight, pi.bias, dw.weight, dw.bias, po.weight, po.bias) if t is not None], prep)
+            Wg, bg, w10, Wo, bo = ops.derived(self).get("gdmlp_x6", [t for t in (pi.weight, pi.bias, dw.weight, dw.bias, po.weight, po.bias) if t is not None], prep)
             return ops.gdmlp_x6(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wg, bg, w10, Wo, bo, Hd)
         return self.chain(x, norm)[0]
 
@@ -711,7 +689,6 @@ class SS2D(nn.Module):
         self.A_logs = nn.Parameter(torch.log(torch.arange(1, N + 1, dtype=torch.float32)).view(1, -1).repeat(K * d_inner, 1).contiguous())
         self.Ds = nn.Parameter(torch.ones(K * d_inner))
         self.out_norm = LayerNorm2d(d_inner)
-        self._cache = _Cache()
 
     def _scan_params(self):
         R = self.dt_rank
@@ -724,7 +701,7 @@ class SS2D(nn.Module):
             A = (A.reshape(-1) if self.d_state == 1 else A).contiguous()
             return (wall, self.dt_projs_weight.detach().contiguous(), self.dt_projs_bias.detach().contiguous(), A,
                     self.Ds.detach().float().contiguous())
-        return self._cache.get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
+        return ops.derived(self).get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
 
     def forward_fused(self, x, norm: LayerNorm2d, keep=False):
         """x + out_proj(out_norm(y0 + y1)), (y0, y1) = scan(SiLU(dw(in_proj(LN(x)))))  (vmamba.py:700-716 + 547-698), for every d_state.

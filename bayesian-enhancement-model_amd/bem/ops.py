@@ -197,8 +197,8 @@ def transpose_plane_slice(x, c0, C):
 # Two packed operand formats: "x6" (three bf16 limbs per f32 value, six limb products on v_mfma_f32_32x32x16_bf16, bem_pw_gemm_x6_f32 --
 # f32-level error at 6/16 of the f32 matrix-pipe cost), what every pointwise GEMM consumes; and "f32" (v_mfma_f32_32x32x2_f32 operand
 # order, pack_pw_weight(x6=False)), the weight format of the implicit-GEMM convolutions (bem_conv2d_mfma_f32).
-# Bumped whenever parameters are rewritten behind torch's back (the fused optimizer step, bem.train.BemAdamW): every cache of
-# derived weights (packed / transposed / flipped copies) is keyed on it as well as on the tensors' data_ptr / _version.
+# Bumped whenever parameters are rewritten behind torch's back (the fused optimizer step, bem.train.BemAdamW): every Derived
+# cache (packed / transposed / flipped copies of weights) is keyed on it as well as on the tensors' data_ptr / _version.
 WEIGHT_EPOCH = [0]
 
 
@@ -210,6 +210,40 @@ def tensor_version(t) -> int:
     """t._version for cache keys; tensors created under torch.inference_mode() (the reference's eval.py runs there) carry no
     version counter and cannot be modified in place later, so a constant serves."""
     return -1 if t.is_inference() else t._version
+
+
+class Derived:
+    """The tensors one holder derives from its parameters: packed, transposed, flipped or folded copies.  An entry is valid for one
+    weight epoch and one (data_ptr, version, device) of each source; a changed signature replaces it, which frees the old value."""
+
+    def __init__(self):
+        self.d = {}
+
+    @staticmethod
+    def _sig(srcs):
+        return (WEIGHT_EPOCH[0],) + tuple((t.data_ptr(), tensor_version(t), t.device) for t in srcs)
+
+    def get(self, key, srcs, fn):
+        sig = self._sig(srcs)
+        hit = self.d.get(key)
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        with torch.no_grad():
+            val = fn()
+        self.d[key] = (sig, val)
+        return val
+
+    def put(self, key, srcs, val):
+        """Store a value made elsewhere (BayesBank packs all its leaves' operands in one launch) as ``get(key, srcs, ...)`` would."""
+        self.d[key] = (self._sig(srcs), val)
+
+
+def derived(holder) -> Derived:
+    """The one Derived cache of a module (or any object), created on first use; it is no parameter, buffer or submodule."""
+    c = holder.__dict__.get("_derived")
+    if c is None:
+        c = holder.__dict__["_derived"] = Derived()
+    return c
 
 
 def packed_elems(M: int, K: int, x6: bool = False) -> int:
@@ -405,44 +439,40 @@ def dwconv3x3(x, w, bias=None, mode=0):
     return out
 
 
-_CONV_PACK = {}          # (data_ptr, version, shape) -> packed (Cout, Cin*KH*KW) weight for the MFMA conv
 USE_CONV_MFMA = True
-
-
-def _packed_conv_weight(w):
-    key = (w.data_ptr(), tensor_version(w), tuple(w.shape), WEIGHT_EPOCH[0])
-    hit = _CONV_PACK.get(key)
-    if hit is None:
-        if len(_CONV_PACK) > 256:
-            _CONV_PACK.clear()
-        # the source tensor is kept alive with its packed copy: a freed-and-reused address must never alias a stale entry
-        hit = (w, pack_pw_weight(w.reshape(w.shape[0], -1).contiguous(), x6=False))
-        _CONV_PACK[key] = hit
-    return hit[1]
-
-
-_CONV_PACK_X6 = {}       # same keys -> (9 taps, x6-packed (Cout, Cin)) weights for the shifted-tap 3x3 convolution
 USE_CONV_X6 = True
 # 4x4 stride-2 convs take the coalesced-row x6 kernel (conv_rows_x6.hip) where bem_conv4x4s2_fast_supported allows, the f32-MFMA im2col kernel otherwise
 
 
-def _packed_conv_weight_x6(w):
-    key = (w.data_ptr(), tensor_version(w), tuple(w.shape), WEIGHT_EPOCH[0])
-    hit = _CONV_PACK_X6.get(key)
-    if hit is None:
-        if len(_CONV_PACK_X6) > 256:
-            _CONV_PACK_X6.clear()
-        taps = w.permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3], w.shape[0], w.shape[1]).contiguous()       # tap = ky * KW + kx
-        hit = (w, pack_pw_weight(taps, x6=True))
-        _CONV_PACK_X6[key] = hit
-    return hit[1]
+class ConvWeight:
+    """A dense-conv weight (Cout, Cin, KH, KW) and the operand forms conv2d's matrix-core kernels read, each packed on first request and
+    kept as long as this object.  Whoever owns the weight keeps the ConvWeight (modules.Conv2dK.conv_weight: in its Derived cache)."""
+
+    def __init__(self, w):
+        self.w, self._x6, self._f32 = w, None, None
+
+    def x6(self):
+        """(KH*KW taps, x6-packed (Cout, Cin)), tap = ky * KW + kx: the shifted-tap 3x3 and the coalesced-row 4x4 convolutions."""
+        if self._x6 is None:
+            w = self.w
+            self._x6 = pack_pw_weight(w.permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3], w.shape[0], w.shape[1]).contiguous(), x6=True)
+        return self._x6
+
+    def f32(self):
+        """Packed (Cout, Cin*KH*KW) f32 operand of the implicit-GEMM convolution (bem_conv2d_mfma_f32)."""
+        if self._f32 is None:
+            self._f32 = pack_pw_weight(self.w.reshape(self.w.shape[0], -1).contiguous(), x6=False)
+        return self._f32
 
 
 def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
     """Dense conv.  ``cin_slice=(c0, Cin)`` convolves channels [c0, c0+Cin) of a wider contiguous x.
     ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
     Runs as an implicit GEMM on the matrix cores (Cout <= 160), else on the direct VALU kernel.
-    dilation 2 (3x3, pad 2) and 3x3 stride 2 exist in the shifted-tap form only (QD model2 / model3)."""
+    dilation 2 (3x3, pad 2) and 3x3 stride 2 exist in the shifted-tap form only (QD model2 / model3).
+    ``w``: a ConvWeight, whose packed forms are reused, or a plain (Cout, Cin, KH, KW) tensor, packed for this call alone."""
+    cw = w if isinstance(w, ConvWeight) else ConvWeight(w)
+    w = cw.w
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias", optional=True)
     _chk(res1, "res1", optional=True); _chk(res2, "res2", optional=True)
     B, Ct, H, W = x.shape
@@ -467,7 +497,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
             if r is not None and tuple(r.shape) != shp:
                 raise ValueError(f"conv2d: {n} shape")
         xp_ = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
-        check(lib().bem_conv_taps_x6_f32(xp_, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
+        check(lib().bem_conv_taps_x6_f32(xp_, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
                                          dilation, int(relu), res1_rep, _stream()), "conv_taps_x6")
         return out
     for n, r, shp in res_shapes:
@@ -478,18 +508,18 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
     xp = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
     if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
         # nine shifted 1x1 taps on the bf16-limb GEMM machinery (pw_gemm_x6.hip)
-        check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
         return out
     conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
     if conv4_fast:
         # the coalesced-row form (conv_rows_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
-        check(lib().bem_conv4x4s2_x6_f32(xp, Ct * H * W, _p(_packed_conv_weight_x6(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv4x4s2_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                          Cout, int(relu), _stream()), "conv4x4s2_x6")
         return out
     if USE_CONV_MFMA and Cout <= 160 and ((KH, KW, stride) in ((3, 3, 1), (4, 4, 2))):
-        check(lib().bem_conv2d_mfma_f32(xp, Ct * H * W, _p(_packed_conv_weight(w)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv2d_mfma_f32(xp, Ct * H * W, _p(cw.f32()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                         Cout, KH, KW, stride, pad, int(relu), res1_rep, _stream()), "conv2d_mfma")
         return out
     check(lib().bem_conv2d_f32(xp, Ct * H * W, _p(w), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW,
@@ -1712,10 +1742,11 @@ def _wrap_profiled():
         if _PROF is None:
             return _cv(x, w, bias, stride, pad, **kw)
         B, _, H, W = x.shape
-        Co, Ci, KH, KW = w.shape
+        wn = w.w if isinstance(w, ConvWeight) else w
+        Co, Ci, KH, KW = wn.shape
         Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
         nres = (kw.get("res1") is not None) + (kw.get("res2") is not None)
-        s = _timed("conv2d", 4.0 * B * (Ci * H * W + Co * Ho * Wo * (1 + nres)) + 4.0 * w.numel(), 2.0 * B * Co * Ci * KH * KW * Ho * Wo)
+        s = _timed("conv2d", 4.0 * B * (Ci * H * W + Co * Ho * Wo * (1 + nres)) + 4.0 * wn.numel(), 2.0 * B * Co * Ci * KH * KW * Ho * Wo)
         out = _cv(x, w, bias, stride, pad, **kw)
         _timed_end(s)
         return out
