@@ -881,6 +881,8 @@ def pad_reflect(x, Hp, Wp):
     B, C, H, W = x.shape
     if Hp == H and Wp == W:
         return x
+    if not (0 <= Hp - H < H and 0 <= Wp - W < W):
+        raise ValueError(f"pad_reflect: the pad must be smaller than the image ({H}x{W} -> {Hp}x{Wp})")
     out = torch.empty(B, C, Hp, Wp, device=x.device, dtype=x.dtype)
     check(lib().bem_pad_reflect_f32(_p(x), _p(out), B * C, H, W, Hp, Wp, _stream()), "pad_reflect")
     return out
@@ -1039,6 +1041,16 @@ def se_gate_bwd(mean, w1, w2, y, dy, dw1, dw2):
     return dmean
 
 
+_GRID_MAX = 65535        # the y and z extent of a launch grid: the selection tail puts candidates (x 3 channels) or images there
+
+
+def _spi(op, Bn, samples_per_image):
+    """Bn candidates in groups of samples_per_image -> the number of images."""
+    if samples_per_image < 1 or Bn % samples_per_image:
+        raise ValueError(f"{op}: {Bn} candidates are not a multiple of samples_per_image = {samples_per_image}")
+    return Bn // samples_per_image
+
+
 def cond_postproc(pred, target_mean, noise, samples_per_image, noise_level):
     _chk(pred, "pred"); _chk(target_mean, "target_mean", optional=True); _chk(noise, "noise", optional=True)
     Bn, C, h, w = pred.shape
@@ -1055,11 +1067,16 @@ def cond_postproc(pred, target_mean, noise, samples_per_image, noise_level):
 
 
 def candidate_finalize(pred, target, samples_per_image, h, w, gt_mean):
-    """pred (Bn,3,Hp,Wp), target (n_img,3,h,w)|None -> (final (Bn,3,h,w), psnr (Bn))."""
+    """pred (Bn,3,Hp,Wp), target (n_img,3,h,w)|None -> (final (Bn,3,h,w), psnr (Bn)).  3 Bn <= 65535 (one grid row per candidate channel)."""
     _chk(pred, "pred"); _chk(target, "target", optional=True)
     Bn, C, Hp, Wp = pred.shape
-    if C != 3 or Bn % samples_per_image or h > Hp or w > Wp:
+    _spi("candidate_finalize", Bn, samples_per_image)
+    if C != 3 or not (0 < h <= Hp and 0 < w <= Wp):
         raise ValueError("candidate_finalize: shapes")
+    if 3 * Bn > _GRID_MAX:
+        raise ValueError(f"candidate_finalize: at most {_GRID_MAX // 3} candidates per call, got {Bn}")
+    if gt_mean and target is None:
+        raise ValueError("candidate_finalize: gt_mean needs a target")
     if target is not None and tuple(target.shape) != (Bn // samples_per_image, 3, h, w):
         raise ValueError("candidate_finalize: target shape")
     fin = torch.empty(Bn, 3, h, w, device=pred.device, dtype=pred.dtype)
@@ -1071,13 +1088,15 @@ def candidate_finalize(pred, target, samples_per_image, h, w, gt_mean):
 
 
 def select_best(final, psnr, samples_per_image):
-    """eval.py:284-285 on the device: (best (B) int32, best_psnr (B), best_images (B,3,h,w)); row = image*N + sample."""
+    """eval.py:284-285 on the device: (best (B) int32, best_psnr (B), best_images (B,3,h,w)); row = image*N + sample.  B <= 65535."""
     _chk(final, "final"); _chk(psnr, "psnr")
     Bn = final.shape[0]
     N = samples_per_image
-    if Bn % N or psnr.numel() != Bn:
+    B = _spi("select_best", Bn, N)
+    if psnr.numel() != Bn:
         raise ValueError("select_best: shapes")
-    B = Bn // N
+    if B > _GRID_MAX:
+        raise ValueError(f"select_best: at most {_GRID_MAX} images per call, got {B}")
     best = torch.empty(B, device=final.device, dtype=torch.int32)
     bp = torch.empty(B, device=final.device, dtype=torch.float32)
     img = torch.empty((B,) + tuple(final.shape[1:]), device=final.device, dtype=final.dtype)
@@ -1086,10 +1105,13 @@ def select_best(final, psnr, samples_per_image):
 
 
 def ssim(final, target, samples_per_image):
-    """Enhancement/utils.py calculate_ssim per candidate: final (Bn,3,h,w) in [0,1], target (Bn/N,3,h,w) -> (Bn) f32."""
+    """Enhancement/utils.py calculate_ssim per candidate: final (Bn,3,h,w) in [0,1], target (Bn/N,3,h,w) -> (Bn) f32.  Bn <= 65535."""
     _chk(final, "final"); _chk(target, "target")
     Bn, C, h, w = final.shape
-    if C != 3 or Bn % samples_per_image or tuple(target.shape) != (Bn // samples_per_image, 3, h, w) or h <= 10 or w <= 10:
+    _spi("ssim", Bn, samples_per_image)
+    if Bn > _GRID_MAX:
+        raise ValueError(f"ssim: at most {_GRID_MAX} candidates per call, got {Bn}")
+    if C != 3 or tuple(target.shape) != (Bn // samples_per_image, 3, h, w) or h <= 10 or w <= 10:
         raise ValueError("ssim: shapes (3-channel images larger than the 11x11 window)")
     out = torch.empty(Bn, device=final.device, dtype=torch.float32)
     ws = torch.empty(Bn, device=final.device, dtype=torch.float64)
@@ -1099,11 +1121,15 @@ def ssim(final, target, samples_per_image):
 
 def select_scores(final, s1, samples_per_image, s2=None, weight=1.0, rule="weighted"):
     """Per-image selection on the device (eval.py:268-297): rule 'weighted' (weight s1/max + (1-weight) s2/max), 'max', 'min';
-    first index on ties.  Returns (best (B) int32, best s1 (B), best s2 (B)|None, best images (B,3,h,w)|None)."""
+    first index on ties.  Returns (best (B) int32, best s1 (B), best s2 (B)|None, best images (B,3,h,w)|None).  B <= 65535."""
     _chk(s1, "s1"); _chk(s2, "s2", optional=True); _chk(final, "final", optional=True)
     N = samples_per_image
     Bn = s1.numel()
-    if Bn % N or (s2 is not None and s2.numel() != Bn) or (final is not None and final.shape[0] != Bn):
+    if rule not in ("weighted", "max", "min"):
+        raise ValueError(f"select_scores: unknown rule {rule!r}")
+    if _spi("select_scores", Bn, N) > _GRID_MAX:
+        raise ValueError(f"select_scores: at most {_GRID_MAX} images per call, got {Bn // N}")
+    if (s2 is not None and s2.numel() != Bn) or (final is not None and final.shape[0] != Bn):
         raise ValueError("select_scores: shapes")
     r = {"weighted": 0, "max": 1, "min": 2}[rule]
     B = Bn // N
@@ -1117,11 +1143,13 @@ def select_scores(final, s1, samples_per_image, s2=None, weight=1.0, rule="weigh
 
 
 def mc_mean(raw, target, samples_per_image, h, w, gt_mean):
-    """Monte-Carlo mean prediction (eval.py:224-225,308-314): raw (Bn,3,Hp,Wp) -> (B,3,h,w)."""
+    """Monte-Carlo mean prediction (eval.py:224-225,308-314): raw (Bn,3,Hp,Wp) -> (B,3,h,w).  B <= 65535."""
     _chk(raw, "raw"); _chk(target, "target", optional=True)
     Bn, C, Hp, Wp = raw.shape
     N = samples_per_image
-    if C != 3 or Bn % N or h > Hp or w > Wp or (gt_mean and (target is None or tuple(target.shape) != (Bn // N, 3, h, w))):
+    if _spi("mc_mean", Bn, N) > _GRID_MAX:
+        raise ValueError(f"mc_mean: at most {_GRID_MAX} images per call, got {Bn // N}")
+    if C != 3 or not (0 < h <= Hp and 0 < w <= Wp) or (gt_mean and (target is None or tuple(target.shape) != (Bn // N, 3, h, w))):
         raise ValueError("mc_mean: shapes")
     B = Bn // N
     out = torch.empty(B, 3, h, w, device=raw.device, dtype=raw.dtype)
