@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import autograd as ag
 from . import ops
-from .modules import (Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _need_cuda, grad_mode, make_vss_level,
+from .modules import (Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _need_cuda, fold_up_fuse, grad_mode, make_vss_level,
                       set_module_paths)
 from .native import BemNativeError
 
@@ -241,10 +241,19 @@ class _Stage2(nn.Module):
             f = down(f)
         return f, skips
 
-    def _decode(self, sfx, f, skips):
-        """(up, fuse with the skip, block) per level, then proj."""
+    def _decode(self, sfx, f, skips, pre=None):
+        """(up, fuse with the skip, block) per level, then proj.  ``pre``: a bias-free 1x1 layer applied to f ahead of the first level.
+        Inference: up and fuse (and pre) are linear with nothing in between, so a level runs them as one folded kernel (ops.up_fuse,
+        modules.fold_up_fuse) and the up-sampled tensor is never formed; training keeps the layers as their own autograd nodes."""
+        folded = ops.USE_UPFUSE and not grad_mode(self)
+        if pre is not None and not (folded and pre.bias is None):
+            f, pre = pre(f), None
         for dec, skip in zip(getattr(self, "decoders" + sfx), reversed(skips)):
-            f = dec["block"](dec["fuse"](dec["up"](f), x2=skip, in_mode=2))
+            if folded and dec["fuse"].bias is None:
+                f = ops.up_fuse(f, skip, fold_up_fuse(dec["up"], dec["fuse"], pre, holder=dec))
+            else:
+                f = dec["fuse"](dec["up"](f if pre is None else pre(f)), x2=skip, in_mode=2)
+            f, pre = dec["block"](f), None
         return getattr(self, "proj" + sfx)(f)
 
     def _cross_fuse(self, f1, f2):
@@ -298,7 +307,7 @@ class _DualBranch(_Stage2):
             feats.append(f)
             skips.append(sk)
         fused = self.bottleneck_block(self.bottleneck_fuse(feats[0], x2=feats[1], in_mode=2))
-        return [self._decode(br, getattr(self, "bottleneck_to" + br)(fz), sk) for br, fz, sk in zip(("_Q1", "_Q2"), ag.fork(fused), skips)]
+        return [self._decode(br, fz, sk, pre=getattr(self, "bottleneck_to" + br)) for br, fz, sk in zip(("_Q1", "_Q2"), ag.fork(fused), skips)]
 
     def _full_res(self, qs):
         """Full-resolution tail: q1, q2 (B,Cin,H,W) -> Hamilton(Q1_out, Q2_out)[1:] (B,3,H,W).  Kernels only in inference, bem.autograd

@@ -212,6 +212,39 @@ class ConvT2x2(nn.ConvTranspose2d):
         return ops.pw_gemm(x, Wp, 4 * co, bias=b4, convT_Win=x.shape[3])
 
 
+def compose_up_fuse(up_w, up_b, fuse_w, pre_w=None):
+    """The algebra of the folded decoder level, in float64 (plain torch, any device).  up_w (C, C/2, 2, 2) and up_b (C/2) of the
+    ConvTranspose2d, fuse_w (C/2, C[, 1, 1]) = [Wf1 | Wf2] of the bias-free 1x1 conv over cat(up(f), skip), pre_w (C, C[, 1, 1]) of a
+    bias-free 1x1 conv applied to f first.  Returns Wc (4, C/2, C), phase 2a + b = Wf1 Wt[:, :, a, b]^T [pre_w]; bc (C/2) = Wf1 bt; Wf2:
+        out[:, 2i+a, 2j+b] = Wc[2a+b] f[:, i, j] + Wf2 skip[:, 2i+a, 2j+b] + bc"""
+    co = up_w.shape[1]
+    wf = fuse_w.double().reshape(fuse_w.shape[0], -1)
+    wf1, wf2 = wf[:, :co], wf[:, co:]
+    wc = torch.einsum("mc,kcab->abmk", wf1, up_w.double())
+    if pre_w is not None:
+        wc = wc @ pre_w.double().reshape(pre_w.shape[0], -1)
+    return wc.reshape(4, wf.shape[0], -1), wf1 @ up_b.double(), wf2
+
+
+def fold_up_fuse(up: "ConvT2x2", fuse: PwConv2d, pre: Optional[PwConv2d] = None, holder: Optional[nn.Module] = None) -> "ops.UpFuseWeights":
+    """ops.UpFuseWeights of fuse(cat(up(pre(f)), skip)): composed in float64 on the weights' device, rounded once to f32 and packed.  The
+    result lives in the Derived cache of ``holder`` (the decoder level; default ``up``), valid for one version of the source weights and
+    one weight epoch.  A ``fuse`` or ``pre`` with a bias is refused (no shipped arch has one)."""
+    if fuse.bias is not None or (pre is not None and pre.bias is not None):
+        raise ValueError("fold_up_fuse: a fuse / pre layer with a bias is not folded")
+    c, co = up.in_channels, up.out_channels
+    if c != 2 * co or (fuse.in_channels, fuse.out_channels) != (c, co) or (pre is not None and (pre.in_channels, pre.out_channels) != (c, c)):
+        raise ValueError(f"fold_up_fuse: needs up C -> C/2, fuse C -> C/2 and pre C -> C (got up {c} -> {co}, fuse {fuse.in_channels} -> "
+                         f"{fuse.out_channels}" + (f", pre {pre.in_channels} -> {pre.out_channels})" if pre is not None else ")"))
+    srcs = [up.weight, up.bias, fuse.weight] + ([pre.weight] if pre is not None else [])
+
+    def prep():
+        wc, bc, wf2 = compose_up_fuse(up.weight.detach(), up.bias.detach(), fuse.weight.detach(), None if pre is None else pre.weight.detach())
+        return ops.UpFuseWeights(ops.pack_pw_weight(wc.float().contiguous()), ops.pack_pw_weight(wf2.float().contiguous()),
+                                 bc.float().contiguous(), c)
+    return ops.derived(up if holder is None else holder).get(("upfuse", pre is not None), srcs, prep)
+
+
 # ------------------------------------------------------------------------------------------------
 # Bayesian leaves (basicsr/bayesian/conv.py:10-128, linear.py:8-104)
 # ------------------------------------------------------------------------------------------------

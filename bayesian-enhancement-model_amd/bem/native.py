@@ -67,6 +67,7 @@ SIGNATURES = {
     "bem_pack_pw_weight_x6_jobs": [P, P, I, P, P],
     "bem_pw_x6_packed_elems": [I, I],
     "bem_bnn_sample_pack_x6": [P, P, P, P, I, I, I, U64, U64, P, I, P],
+    "bem_upfuse_x6_f32": [P, P, P, P, P, P, I, I, I, I, P],
     "bem_store_words": [P, P, I, P],
     "bem_bnn_ebank_sample_f32": [P, P, I, P, U64, U64, P],
     "bem_bnn_bank_sample_f32": [P, P, I, P, P, P, P, P, F, P, U64, U64, P, P],

@@ -331,6 +331,40 @@ def pw_gemm(x1, Wp, M, *, x2=None, in_mode=0, ln=None, ln_eps=1e-5, bias=None, r
     return out
 
 
+# Reaches the unfolded decoder chain (ConvT2x2 -> concat-input 1x1 GEMM) from a test; the shipped path is the folded kernel.
+USE_UPFUSE = True
+
+
+class UpFuseWeights:
+    """The folded operands of one decoder level (bem.modules.fold_up_fuse): Wc = pack_pw_weight of the four composed phase matrices
+    (4, Cin/2, Cin), Wf2 = pack_pw_weight of the skip half of the fuse weight (Cin/2, Cin/2), bias (Cin/2) the composed bias."""
+
+    def __init__(self, Wc, Wf2, bias, cin):
+        self.Wc, self.Wf2, self.bias, self.cin = Wc, Wf2, bias, int(cin)
+
+
+def up_fuse(f, skip, folded: UpFuseWeights):
+    """fuse(cat(up(f), skip)) of a decoder level as one kernel: f (B,Cin,h,w), skip (B,Cin/2,2h,2w) -> (B,Cin/2,2h,2w)."""
+    _chk(f, "f"); _chk(skip, "skip"); _chk(folded.Wc, "Wc"); _chk(folded.Wf2, "Wf2"); _chk(folded.bias, "bias")
+    if f.dim() != 4:
+        raise ValueError("up_fuse: f must be (B, Cin, h, w)")
+    B, C, h, w = f.shape
+    if C != folded.cin or C < 2 or C % 2:
+        raise ValueError(f"up_fuse: f has {C} channels, the folded weights were made for {folded.cin} (even, >= 2)")
+    Co = C // 2
+    if tuple(skip.shape) != (B, Co, 2 * h, 2 * w):
+        raise ValueError(f"up_fuse: skip shape {tuple(skip.shape)} != {(B, Co, 2 * h, 2 * w)}")
+    if tuple(folded.Wc.shape) != (4, packed_elems(Co, C, True)) or getattr(folded.Wc, "_bem_mk", (Co, C)) != (Co, C):
+        raise ValueError(f"up_fuse: Wc packed shape {tuple(folded.Wc.shape)} does not match four ({Co}, {C}) matrices")
+    if tuple(folded.Wf2.shape) != (1, packed_elems(Co, Co, True)) or getattr(folded.Wf2, "_bem_mk", (Co, Co)) != (Co, Co):
+        raise ValueError(f"up_fuse: Wf2 packed shape {tuple(folded.Wf2.shape)} does not match one ({Co}, {Co}) matrix")
+    if folded.bias.numel() != Co:
+        raise ValueError("up_fuse: bias size")
+    out = torch.empty_like(skip)
+    check(lib().bem_upfuse_x6_f32(_p(f), _p(skip), _p(folded.Wc), _p(folded.Wf2), _p(folded.bias), _p(out), B, C, h, w, _stream()), "up_fuse")
+    return out
+
+
 def empty_padded(shape, device, pad=4):
     """Contiguous float32 tensor of ``shape`` that may be read ``pad`` elements before its first and after its last element
     (it is a view into a larger allocation; the 16-byte alignment of a fresh allocation is kept for pad % 4 == 0)."""
@@ -1699,6 +1733,8 @@ _KEYS = {
     "dwconv3x3": ("dwconv3x3", "hbm", "dwconv3x3_kernel", None),
     "ss2d_scan": ("ss2d_scan", "hbm", "ss2d_scan_kernel", None),
     "transpose_planes": ("transpose_planes", "hbm", "transpose_planes_kernel", None),
+    # a decoder level's up + fuse as one kernel: f in, skip in, out out are its algorithmic bytes
+    "up_fuse": ("up_fuse", "hbm", "upfuse_x6_kernel<2>", None),
     # training step (bench.py --config train)
     "pw_wgrad": ("pw_wgrad_", "hbm", "wgrad_x6_kernel<2, 2> + wgrad_x6_reduce_kernel (1x1 weight gradients; wgrad_kernel<*> for L % 32 != 0)", None),
     "conv_wgrad": ("conv_wgrad_", "mfma", "wgrad_kernel<*> (dense conv weight gradients)", None),
@@ -1844,7 +1880,11 @@ def _wrap_profiled():
     def c_ln(x1, dn, gamma, beta, eps, dgamma, dbeta, x2=None, dres=None, want_n=True):
         return 4.0 * x1.numel() * (3 + (x2 is not None) + (dres is not None) + bool(want_n)), 0.0
 
-    for nm, fn in (("pw_wgrad_", c_pw_wgrad), ("conv_wgrad_", c_conv_wgrad), ("ss2d_scan_bwd", c_scan_bwd), ("dwact_bwd", c_dwact), ("ln_bwd", c_ln)):
+    def c_up_fuse(f, skip, folded):
+        Co = skip.shape[1]
+        return 4.0 * (f.numel() + 2 * skip.numel() + folded.Wc.numel() + folded.Wf2.numel()), 2.0 * skip.numel() * (f.shape[1] + Co)
+
+    for nm, fn in (("up_fuse", c_up_fuse), ("pw_wgrad_", c_pw_wgrad), ("conv_wgrad_", c_conv_wgrad), ("ss2d_scan_bwd", c_scan_bwd), ("dwact_bwd", c_dwact), ("ln_bwd", c_ln)):
         wrap(nm, fn)
 
 

@@ -164,6 +164,14 @@ int64_t bem_pw_x6_packed_elems(int M, int K);
 int bem_bnn_sample_pack_x6(const float* mu, const float* rho, const float* eps, float* Wp, int nsets, int M, int K,
                            uint64_t seed, uint64_t stream_id, const uint64_t* stream_add, int sigma_given,
                            void* stream);   /* sigma_given: rho already holds log1p(exp(rho)); stream_add: see bem_bnn_sample_f32 */
+/* A Stage-II decoder level's fuse(cat(up(f), skip)) -- ConvTranspose2d(Cin, Cin/2, 2, stride 2) followed by a bias-free 1x1 conv over the
+ * concatenation with the skip -- as ONE x6 GEMM; the up-sampled tensor is never formed:
+ *   out[b][co][2i+a][2j+b'] = sum_k Wc[a,b'][co][k] f[b][k][i][j] + sum_c Wf2[co][c] skip[b][c][2i+a][2j+b'] + bias[co]
+ * f (B, Cin, h, w), skip and out (B, Cin/2, 2h, 2w), 8-byte aligned; Cin even, >= 2.  Wc_packed = bem_pack_pw_weight_x6 of the four composed
+ * phase matrices (4, Cin/2, Cin), set = 2a + b'; Wf2_packed = the same of (Cin/2, Cin/2); bias (Cin/2) the composed bias.  One weight set
+ * for the whole batch. */
+int bem_upfuse_x6_f32(const float* f, const float* skip, const float* Wc_packed, const float* Wf2_packed, const float* bias, float* out,
+                      int B, int Cin, int h, int w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Convolutions.
