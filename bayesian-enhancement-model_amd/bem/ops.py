@@ -475,7 +475,7 @@ def dwconv3x3(x, w, bias=None, mode=0):
 
 USE_CONV_MFMA = True
 USE_CONV_X6 = True
-# 4x4 stride-2 convs take the coalesced-row x6 kernel (conv_rows_x6.hip) where bem_conv4x4s2_fast_supported allows, the f32-MFMA im2col kernel otherwise
+# 4x4 stride-2 convs take the coalesced-row x6 kernel (conv_x6.hip) where bem_conv4x4s2_fast_supported allows, the f32-MFMA im2col kernel otherwise
 
 
 class ConvWeight:
@@ -541,14 +541,14 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         raise ValueError("conv2d: bias shape")
     xp = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
     if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
-        # nine shifted 1x1 taps on the bf16-limb GEMM machinery (pw_gemm_x6.hip)
+        # nine shifted 1x1 taps on the bf16-limb GEMM machinery (conv_x6.hip)
         check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
         return out
     conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
     if conv4_fast:
-        # the coalesced-row form (conv_rows_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
+        # the coalesced-row form (conv_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
         check(lib().bem_conv4x4s2_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                          Cout, int(relu), _stream()), "conv4x4s2_x6")
         return out

@@ -64,7 +64,7 @@ __device__ __forceinline__ float bem_erf_fast(float x) {
 __device__ __forceinline__ float bem_gelu_fast(float x) { return 0.5f * x * (1.f + bem_erf_fast(x * 0.70710678118654752440f)); }
 
 // Philox4x32-10 counter-based generator + Box-Muller: one N(0,1) draw per (element index, stream id) under a 64-bit seed.
-// Shared by the Bayesian weight sampler (elementwise.hip) and the fused sample-and-pack kernel (pw_gemm_x6.hip): the same
+// Shared by the Bayesian weight sampler (elementwise.hip) and the fused sample-and-pack kernels (pack.hip): the same
 // (i, seed, stream) gives the same draw in both.
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll

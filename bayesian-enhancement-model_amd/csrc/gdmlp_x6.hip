@@ -27,7 +27,7 @@
 //   * epilogue: + b_o + x (residual), 128-byte row segments per half-wave.
 // Two barriers per chunk.
 #include "bem_common.h"
-#include "x6_common.h"
+#include "x6_tile.h"
 
 namespace {
 
@@ -40,13 +40,7 @@ struct GdX {
     int C, Hd, H, W, NCH, tx;
 };
 
-constexpr int GD_TH = 4, GD_TW = 32, GD_HW = GD_TW + 2;
-constexpr int GD_NPH = (GD_TH + 2) * GD_HW;          // 204 halo pixels
-constexpr int GD_NPB = (GD_NPH + 31) / 32;           // 7 blocks
-constexpr int GD_TS = 208;                           // row stride of T (>= 205: the clamp slot of the unused lanes of block 6)
 constexpr int GD_GS = 20;                            // dwords per pixel row of G (16 + 4: conflict-free b128 writes and reads)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // GELU(a) * b (erf by Abramowitz & Stegun 7.1.26 on the hardware rcp / exp2, as bem_gelu_fast).  Scalar f32 instructions on purpose:
 // on gfx950 a v_pk_*_f32 instruction does not overlap with another wave's MFMAs on the same SIMD, plain v_fma_f32 / v_exp_f32 do
@@ -67,7 +61,7 @@ __device__ __forceinline__ float gelu_gate1(float a, float b) {
 template <int KBM, int MTO, int WOB, bool PL2>
 __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
     constexpr int NPI = 3 * KBM, NPO = 3 * MTO;                                        // 1 KiB pieces of a W_i / W_o chunk
-    __shared__ __attribute__((aligned(16))) f32x2 T[16 * GD_TS];                       // [gate channel c][halo pixel] = (h1 input, h2 input)
+    __shared__ __attribute__((aligned(16))) f32x2 T[16 * XT_TS];                       // [gate channel c][halo pixel] = (h1 input, h2 input)
     __shared__ __attribute__((aligned(16))) float G[128 * GD_GS];                      // [tile pixel][16 gate channels (+4 pad)]
     __shared__ __attribute__((aligned(16))) u32x4 Wis[2][NPI * 64];                    // W_i chunk [kb][limb][lane], chunk j in buffer j & 1
     __shared__ __attribute__((aligned(16))) u32x4 Wos[WOB][NPO * 64];                  // W_o chunk [mt][limb][lane], chunk j in buffer j & (WOB - 1)
@@ -75,9 +69,8 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     __shared__ __attribute__((aligned(16))) f32x2 DWs[2][16 * 10];                     // depthwise taps + bias of the chunk
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kh = lane >> 5, n = lane & 31;
     const int b = blockIdx.z;
-    const int tile = xcd_tile(blockIdx.x, gridDim.x);
-    const int tyi = tile / k.tx, txi = tile - tyi * k.tx;
-    const int y0 = tyi * GD_TH, x0 = txi * GD_TW;
+    int y0, x0;
+    tile_origin(k.tx, y0, x0);
     const int L = k.H * k.W;
     const float* xb = k.x + (int64_t)b * k.C * L;
 
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
 
     // phase-C geometry: wave = tile row, lane (n, kh) = pixel n, k-half kh
     const int oy = y0 + wave, ox = x0 + n;
-    // residual + output bias of this wave's pixel row (rows (r & 3) + 8 (r >> 2) + 4 kh of each M-tile): requested
+    // residual + output bias of this wave's pixel row (rows acc_row(r, kh) of each M-tile): requested
     // ahead of the last phase C
     f32x16 rs[MTO];
     const bool opix = oy < k.H && ox < k.W;
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
         for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = min(32 * mt + (r & 3) + 8 * (r >> 2) + 4 * kh, k.C - 1);
+                const int row = min(acc_row(r, kh, 32 * mt), k.C - 1);
                 rs[mt][r] = fmaf(bpo[row], bomul, rb[(int64_t)row * L]);
             }
     };
@@ -146,11 +139,11 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
         // bench.py, profiles/r03_gdmlp_insitu_variants.txt): 665 us against 651 us for one block after the other -- off
         float xr[2][KBM][8];
         auto load_block = [&](int i) {
-            const int hp = min((wave + 4 * i) * 32 + n, GD_TS - 1);
+            const int hp = min((wave + 4 * i) * 32 + n, XT_TS - 1);
             hpo[i] = hp;
-            const int hy = hp / GD_HW, hx = hp - hy * GD_HW;
+            const int hy = hp / XT_HW, hx = hp - hy * XT_HW;
             const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const bool in = hp < GD_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < GD_NPB;
+            const bool in = hp < XT_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < XT_NPB;
             msk[i] = in ? 1.f : 0.f;
             mbit[i] = in ? 0xffffffffu : 0u;
             const int off = min(max(gy, 0), k.H - 1) * k.W + min(max(gx, 0), k.W - 1);
@@ -195,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     }
 
     // phase-B geometry: lane = column n, tile rows 2 kh and 2 kh + 1; the window of both starts at halo (2 kh, n)
-    const int wb_lds = 2 * kh * GD_HW + n;
+    const int wb_lds = 2 * kh * XT_HW + n;
     const int c_lo = 4 * wave;
 
     f32x16 oh[MTO];
@@ -236,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
         // ---- phase A (chunk j) and phase C (chunk j - 1): matrix-core work
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if (wave + 4 * i < GD_NPB) {                                               // wave-uniform
+            if (wave + 4 * i < XT_NPB) {                                               // wave-uniform
                 // accumulator rows 2(q&1) + 8(q>>1) + 4kh (+1) are the (h1, h2) inputs of gate channel c = (q&1) + 4(q>>1) + 2kh:
                 // the small-product accumulator starts from the channel's bias pair (zero outside the image: the conv pads t with zeros)
                 f32x16 hi, lo;
@@ -258,10 +251,10 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
                     lo = mfma16(wl[0], xl[i][kb][1], lo);
                     lo = mfma16(wl[1], xl[i][kb][0], lo);
                 }
-                f32x2* tp = T + 2 * kh * GD_TS + hpo[i];
+                f32x2* tp = T + 2 * kh * XT_TS + hpo[i];
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
-                    tp[((q & 1) + 4 * (q >> 1)) * GD_TS] = f32x2{hi[2 * q] + lo[2 * q], hi[2 * q + 1] + lo[2 * q + 1]};
+                    tp[((q & 1) + 4 * (q >> 1)) * XT_TS] = f32x2{hi[2 * q] + lo[2 * q], hi[2 * q + 1] + lo[2 * q + 1]};
             }
         }
         if (j) phase_c(Wos[(j - 1) & (WOB - 1)]);
@@ -277,12 +270,12 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
                 const f32x2 wq[9] = {{w01[0], w01[1]}, {w01[2], w01[3]}, {w23[0], w23[1]}, {w23[2], w23[3]}, {w45[0], w45[1]},
                                      {w45[2], w45[3]}, {w67[0], w67[1]}, {w67[2], w67[3]}, {w8b[0], w8b[1]}};
                 const f32x2 bias = {w8b[2], w8b[3]};
-                const f32x2* tp = T + (c_lo + cc) * GD_TS + wb_lds;
+                const f32x2* tp = T + (c_lo + cc) * XT_TS + wb_lds;
                 f32x2 win[4][3];
 #pragma unroll
                 for (int dy = 0; dy < 4; ++dy)
 #pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) win[dy][dx] = tp[dy * GD_HW + dx];
+                    for (int dx = 0; dx < 3; ++dx) win[dy][dx] = tp[dy * XT_HW + dx];
                 float a0x = bias[0], a0y = bias[1], a1x = bias[0], a1y = bias[1];         // (h1, h2) of pixel rows 2kh and 2kh + 1
 #pragma unroll
                 for (int ty = 0; ty < 3; ++ty)
@@ -304,14 +297,14 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     load_res();                                                                        // requested ahead of the last matrix phase
     phase_c(Wos[(k.NCH - 1) & (WOB - 1)]);
 
-    // ---- epilogue: + bias + residual, rows (r & 3) + 8 (r >> 2) + 4 kh of each M-tile, 128-byte segments per half-wave
+    // ---- epilogue: + bias + residual, rows acc_row(r, kh) of each M-tile, 128-byte segments per half-wave
     if (opix) {
         float* ob = out + (int64_t)b * k.C * L + po;
 #pragma unroll
         for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int row = acc_row(r, kh, 32 * mt);
                 if (row < k.C) ob[(int64_t)row * L] = oh[mt][r] + rs[mt][r];
             }
     }
@@ -334,11 +327,11 @@ extern "C" int bem_gdmlp_x6_f32(const float* x, const float* ln_w, const float* 
     k.x = x; k.ln_w = ln_w; k.ln_b = ln_b; k.ln_eps = ln_eps;
     k.Wpi = reinterpret_cast<const u32x4*>(Wp_gate); k.Wpo = reinterpret_cast<const u32x4*>(Wp_out); k.bgi = bias_gate;
     k.dw10 = dw_gate10;
-    k.C = C; k.Hd = Hd; k.H = H; k.W = W; k.NCH = Hd / 16; k.tx = cdiv(W, GD_TW);
+    k.C = C; k.Hd = Hd; k.H = H; k.W = W; k.NCH = Hd / 16; k.tx = cdiv(W, XT_TW);
     // absent output bias: read an always-present array and multiply by zero -- no branch next to a load
     const float* bpop = bias_out ? bias_out : ln_w;
     const float bomul = bias_out ? 1.f : 0.f;
-    dim3 grid(k.tx * cdiv(H, GD_TH), 1, B);
+    dim3 grid(k.tx * cdiv(H, XT_TH), 1, B);
     hipStream_t s = (hipStream_t)stream;
     const int KB = cdiv(C, 16);
     // two workgroups per CU in every variant (LDS: T 26 KB + G 10 KB + two W_i buffers + one or two W_o buffers <= 80 KB)

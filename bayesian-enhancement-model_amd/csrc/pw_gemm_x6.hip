@@ -18,7 +18,7 @@
 //   * weights arrive pre-split and pre-packed by bem_pack_pw_weight_x6: Wp[mtile][kb][limb][lane] is one 16-byte
 //     vector = W[32 mtile + (lane & 31)][16 kb + 8 (lane >> 5) + e], e = 0..7, so an A operand is one coalesced
 //     1 KiB load per (M-tile, k-block, limb), L1/L2 resident.
-//   * D layout: column = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
+//   * D layout: column = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (acc_row, x6_common.h).
 //   * "resident" kernel: the wave's whole input tile (all K channels, already normalised and split) stays in
 //     registers while the wave walks over every M-tile, so x is read once and LayerNorm evaluated once;
 //     "stream" kernel (no LayerNorm, any K): x is streamed k-block by k-block, one block ahead of the MFMAs.
@@ -81,7 +81,7 @@ __device__ __forceinline__ void x6_epilogue_generic(const PwX& k, int b, int mt0
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
         if (mt0 + m >= k.MT) continue;
-        const int rbase = (mt0 + m) * 32 + 4 * kh;
+        const int rbase = (mt0 + m) * 32;
 #pragma unroll
         for (int rh = 0; rh < 16; rh += 8) {
             float rv[8][NSUB];
@@ -93,7 +93,7 @@ __device__ __forceinline__ void x6_epilogue_generic(const PwX& k, int b, int mt0
 #pragma unroll
                 for (int r8 = 0; r8 < 8; ++r8) {
                     const int r = rh + r8;
-                    const float* rp = resp + (int64_t)min(rbase + (r & 3) + 8 * (r >> 2), k.M - 1) * k.L;
+                    const float* rp = resp + (int64_t)min(rbase + acc_row(r, kh), k.M - 1) * k.L;
                     if (NSUB == 2 && VEC) {
                         const float2 q = *reinterpret_cast<const float2*>(rp + pv);
                         rv[r8][0] = q.x; rv[r8][NSUB - 1] = q.y;
@@ -106,7 +106,7 @@ __device__ __forceinline__ void x6_epilogue_generic(const PwX& k, int b, int mt0
 #pragma unroll
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int r = rh + r8;
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
+                const int row = rbase + acc_row(r, kh);
                 if (row >= k.M) continue;
                 const float bv = s_bias[row];
                 float o[NSUB];
@@ -334,12 +334,7 @@ __global__ __launch_bounds__(256, 2) void pw_x6_res_kernel(PwX k) {
         for (int m = 0; m < MTW; ++m) {
             const bool ok = kb < k.KB && mt + m < k.MT;
             const u32x4* wp = wbase + (int64_t)(mt + m < k.MT ? mt + m : 0) * mt_stride + (int64_t)min(kb, k.KB - 1) * 3 * 64;
-            const uint32_t mk = ok ? 0xffffffffu : 0u;
-#pragma unroll
-            for (int li = 0; li < 3; ++li) {
-                const u32x4 w = wp[li * 64];
-                dst[m][li] = u32x4{w[0] & mk, w[1] & mk, w[2] & mk, w[3] & mk};
-            }
+            load_w3_masked(wp, ok ? 0xffffffffu : 0u, dst[m]);
         }
     };
     u32x4 wn[MTW][3];
@@ -350,11 +345,9 @@ __global__ __launch_bounds__(256, 2) void pw_x6_res_kernel(PwX k) {
         float4 bq[MTW][4];
         x6_load_bias<MTW>(k, b, mt0, kh, bq);
 #pragma unroll
-        for (int m = 0; m < MTW; ++m)
+for (int m = 0; m < MTW; ++m)
 #pragma unroll
-            for (int t = 0; t < NSUB; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][t][r] = alo[m][t][r] = 0.f;
+            for (int t = 0; t < NSUB; ++t) acc[m][t] = alo[m][t] = zero16();
 #pragma unroll
         for (int kb = 0; kb < KBM; ++kb) {
             u32x4 wc[MTW][3];
@@ -459,8 +452,7 @@ __global__ __launch_bounds__(256, 2) void pw_x6_res_lds_kernel(PwX k) {
         f32x16 acc[1][1], alo;
         float4 bq[1][4];
         x6_load_bias<1>(k, b, mt0, kh, bq);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][0][r] = alo[r] = 0.f;
+        acc[0][0] = alo = zero16();
         const u32x4* wl = &Ws[buf][lane];
         u32x4 wn[3] = {wl[0], wl[64], wl[128]};
 #pragma unroll
@@ -543,7 +535,7 @@ __global__ __launch_bounds__(256, 2) void pw_x6_stream_kernel(PwX k) {
     }
     f32x16 acc[MTW][NSUB], alo[MTW][NSUB];
 #pragma unroll
-    for (int m = 0; m < MTW; ++m)
+for (int m = 0; m < MTW; ++m)
 #pragma unroll
         for (int t = 0; t < NSUB; ++t)
 #pragma unroll
@@ -555,12 +547,7 @@ __global__ __launch_bounds__(256, 2) void pw_x6_stream_kernel(PwX k) {
         for (int m = 0; m < MTW; ++m) {
             const bool ok = kb < k.KB && mt0 + m < k.MT;
             const u32x4* wp = wbase + (int64_t)(mt0 + m < k.MT ? mt0 + m : 0) * mt_stride + (int64_t)min(kb, k.KB - 1) * 3 * 64;
-            const uint32_t mk = ok ? 0xffffffffu : 0u;
-#pragma unroll
-            for (int li = 0; li < 3; ++li) {
-                const u32x4 w = wp[li * 64];
-                dst[m][li] = u32x4{w[0] & mk, w[1] & mk, w[2] & mk, w[3] & mk};
-            }
+            load_w3_masked(wp, ok ? 0xffffffffu : 0u, dst[m]);
         }
     };
     // x two k-blocks ahead (the HBM stream: with 2 waves per SIMD one block in flight per wave covers ~4 TB/s at 2 us of
@@ -606,181 +593,7 @@ __global__ __launch_bounds__(256, 2) void pw_x6_stream_kernel(PwX k) {
     x6_epilogue<MTW, NSUB, VEC>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
 }
 
-// natural (nsets, M, K) f32 -> (nsets, MT, KB, 3, 64) 16-byte vectors of bf16 limbs
-__device__ __forceinline__ void pack_x6_item(int64_t i, const float* __restrict__ W, u32x4* __restrict__ Wp, int M, int K, int MT, int KB,
-                                             int64_t ss, int64_t rs, int64_t cs) {      // element strides of W over (set, row, k): transposed / sliced views pack in place
-    const int lane = (int)(i & 63);
-    const int64_t blk = i >> 6;
-    const int kb = (int)(blk % KB), mt = (int)((blk / KB) % MT);
-    const int64_t set = blk / ((int64_t)KB * MT);
-    const int row = mt * 32 + (lane & 31), k0 = kb * 16 + (lane >> 5) * 8;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (row < M && k0 + e < K) ? W[set * ss + row * rs + (k0 + e) * cs] : 0.f;
-    u32x4 h, m, l;
-    split8(v, h, m, l);
-    u32x4* o = Wp + ((set * MT + mt) * KB + kb) * 3 * 64 + lane;
-    o[0] = h; o[64] = m; o[128] = l;
-}
-
-__global__ void pack_x6_kernel(const float* __restrict__ W, u32x4* __restrict__ Wp, int M, int K, int MT, int KB, int64_t total,
-                               int64_t ss, int64_t rs, int64_t cs) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    pack_x6_item(i, W, Wp, M, K, MT, KB, ss, rs, cs);
-}
-
-// Many (M, K) matrices packed by one launch: job = { source pointer, first float of the packed output in `arena` (multiple of 4), int32 M,
-// int32 K, row stride, column stride (elements), work items = ceil(M/32) ceil(K/16) 64 }; blk = { job, first block of 256 work items }.
-// A Stage-I training step re-packs the forward and the transposed operand of every Bayesian 1x1 layer (the weights are new draws each
-// iteration): ~120 launches of a few KiB otherwise.
-struct packjob { const float* src; int64_t out; int32_t M, K; int64_t rs, cs, items, pad0, pad1; };
-static_assert(sizeof(packjob) == 8 * 8, "packjob is eight 64-bit words (bem.modules.BayesBank builds it as an int64 table)");
-
-__global__ __launch_bounds__(256) void pack_x6_jobs_kernel(const packjob* __restrict__ jobs, const int32_t* __restrict__ blks, float* __restrict__ arena) {
-    const packjob jb = jobs[blks[2 * blockIdx.x]];
-    const int64_t i = (int64_t)blks[2 * blockIdx.x + 1] * 256 + threadIdx.x;
-    if (i >= jb.items) return;
-    pack_x6_item(i, jb.src, reinterpret_cast<u32x4*>(arena + jb.out), jb.M, jb.K, (jb.M + 31) / 32, (jb.K + 15) / 16, 0, jb.rs, jb.cs);
-}
-
-// Bayesian weight sets straight into operand order: w[set][row][k] = mu + log1p(exp(rho)) * eps, eps injected or drawn
-// with the sampler's own Philox stream (element index i = set*M*K + row*K + k, as bem_bnn_sample_f32 numbers it), split
-// and stored like pack_x6_kernel does -- the natural-order copy (one write + one read per weight and sample) is skipped.
-__device__ __forceinline__ void sample_pack_x6_item(int64_t i, const float* __restrict__ mu, const float* __restrict__ rho,
-                                                    const float* __restrict__ eps_in, u32x4* __restrict__ Wp, int M, int K, int MT, int KB,
-                                                    uint64_t seed, uint64_t stream_id, int sigma_given) {
-    const int lane = (int)(i & 63);
-    const int64_t blk = i >> 6;
-    const int kb = (int)(blk % KB), mt = (int)((blk / KB) % MT);
-    const int64_t set = blk / ((int64_t)KB * MT);
-    const int row = mt * 32 + (lane & 31), k0 = kb * 16 + (lane >> 5) * 8;
-    float v[8];
-    // the lane's 8 consecutive k of one row are 8 consecutive element indices: at most 3 Philox counter blocks
-    const int64_t g0 = set * M * K + (int64_t)row * K + k0;
-    float z[3][4];
-    if (!eps_in && row < M) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) philox_normal4((g0 >> 2) + q, seed, stream_id, z[q]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        v[e] = 0.f;
-        if (row < M && k0 + e < K) {
-            const int64_t idx = (int64_t)row * K + k0 + e, gi = g0 + e;
-            const int off = (int)(g0 & 3);                                // position of the first element in its block
-            // z[(off + e) >> 2][(off + e) & 3] with compile-time indices (a runtime index would put z into scratch)
-            const float zsel = off == 0 ? z[e >> 2][e & 3] : off == 1 ? z[(e + 1) >> 2][(e + 1) & 3]
-                             : off == 2 ? z[(e + 2) >> 2][(e + 2) & 3] : z[(e + 3) >> 2][(e + 3) & 3];
-            const float eps = eps_in ? eps_in[gi] : zsel;
-            // sigma = log1p(exp(rho)) does not depend on the sample: callers that draw many sets pass it precomputed
-            v[e] = mu[idx] + (sigma_given ? rho[idx] : log1pf(expf(rho[idx]))) * eps;
-        }
-    }
-    u32x4 h, m, l;
-    split8(v, h, m, l);
-    u32x4* o = Wp + ((set * MT + mt) * KB + kb) * 3 * 64 + lane;
-    o[0] = h; o[64] = m; o[128] = l;
-}
-
-__global__ void sample_pack_x6_kernel(const float* __restrict__ mu, const float* __restrict__ rho, const float* __restrict__ eps_in,
-                                      u32x4* __restrict__ Wp, int M, int K, int MT, int KB, int64_t total, uint64_t seed, uint64_t stream_id,
-                                      const uint64_t* __restrict__ stream_add, int sigma_given) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (stream_add) stream_id += stream_add[0];                          // device-resident part of the id (see randn_kernel)
-    sample_pack_x6_item(i, mu, rho, eps_in, Wp, M, K, MT, KB, seed, stream_id, sigma_given);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// All Bayesian tensors of a net drawn for a stochastic (eval) forward in ONE launch: the Stage-I net of the Monte-Carlo loop has 60
-// Bayesian leaves / 90 tensors, i.e. 90 sampling launches per forward that sit between the layers' own kernels on planes of H/16 x W/16
-// pixels, where every dependent launch costs >= 5 us whatever it does.  Segments of a flat output arena:
-//   seg = { mu, sig (sigma = log1p(exp(rho)) precomputed for packed 1x1 weights, rho otherwise), first float of the tensor's nsets outputs
-//           in the arena, n = elements per set, M, K (packed x6 operand order for the GEMM kernels; K = 0: natural order, as
-//           bem_bnn_sample_f32 writes depthwise weights and biases), stream counter, work items, nsets * n }
-//   blk = { segment, first work item }: one workgroup = 256 work items of one segment (packed: sample_pack_x6_item; natural: 4 elements)
-// Values are those of bem_bnn_sample_pack_x6 (sigma_given) / bem_bnn_sample_f32 for (seed, stream_base + counter).
-// ------------------------------------------------------------------------------------------------------------------------
-struct ebank_seg { const float* mu; const float* sig; int64_t out; int64_t n; int32_t M, K; uint64_t counter; int64_t items; int64_t total; };
-static_assert(sizeof(ebank_seg) == 8 * 8, "ebank_seg is eight 64-bit words (bem.modules.EvalSampleBank builds it as an int64 table)");
-struct ebank_blk { int32_t seg; int32_t first; };
-
-__global__ __launch_bounds__(256) void ebank_sample_kernel(const ebank_seg* __restrict__ segs, const ebank_blk* __restrict__ blks,
-                                                           float* __restrict__ arena, uint64_t seed, uint64_t stream_base) {
-    const ebank_blk bk = blks[blockIdx.x];
-    const ebank_seg sg = segs[bk.seg];
-    const int64_t i = (int64_t)bk.first * 256 + threadIdx.x;
-    if (i >= sg.items) return;
-    const uint64_t sid = stream_base + sg.counter;
-    float* out = arena + sg.out;
-    if (sg.K > 0) {
-        sample_pack_x6_item(i, sg.mu, sg.sig, nullptr, reinterpret_cast<u32x4*>(out), sg.M, sg.K, (sg.M + 31) / 32, (sg.K + 15) / 16, seed, sid, 1);
-        return;
-    }
-    const int64_t i0 = 4 * i, total = sg.total;                                       // natural order: total = nsets * n elements
-    float z[4];
-    philox_normal4(i, seed, sid, z);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int64_t e = i0 + q;
-        if (e < total) {
-            const int64_t k = e % sg.n;
-            out[e] = sg.mu[k] + log1pf(expf(sg.sig[k])) * z[q];
-        }
-    }
-}
-
 }  // namespace
-
-extern "C" int bem_bnn_ebank_sample_f32(const void* segs, const void* blks, int nblk, float* arena, uint64_t seed, uint64_t stream_base,
-                                        void* stream) {
-    BEM_REQUIRE(segs && blks && arena && nblk > 0, "bnn_ebank_sample: bad arguments");
-    BEM_REQUIRE(((uintptr_t)arena & 15) == 0, "bnn_ebank_sample: the arena must be 16-byte aligned");
-    ebank_sample_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>((const ebank_seg*)segs, (const ebank_blk*)blks, arena, seed, stream_base);
-    return bem_check_launch("bnn_ebank_sample");
-}
-
-extern "C" int bem_bnn_sample_pack_x6(const float* mu, const float* rho, const float* eps_in, float* Wp, int nsets, int M, int K,
-                                      uint64_t seed, uint64_t stream_id, const uint64_t* stream_add, int sigma_given, void* stream) {
-    BEM_REQUIRE(mu && rho && Wp, "bnn_sample_pack_x6: null tensor");
-    BEM_REQUIRE(nsets >= 0 && M > 0 && K > 0, "bnn_sample_pack_x6: bad shape");
-    BEM_REQUIRE(((uintptr_t)Wp & 15) == 0, "bnn_sample_pack_x6: output must be 16-byte aligned");
-    if (nsets == 0) return BEM_OK;
-    const int MT = cdiv(M, 32), KB = cdiv(K, 16);
-    const int64_t total = (int64_t)nsets * MT * KB * 64;
-    sample_pack_x6_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(mu, rho, eps_in, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB,
-                                                                                       total, seed, stream_id, stream_add, sigma_given);
-    return bem_check_launch("bnn_sample_pack_x6");
-}
-
-extern "C" int64_t bem_pw_x6_packed_elems(int M, int K) {       // in floats (4 per 16-byte vector)
-    return (int64_t)cdiv(M, 32) * cdiv(K, 16) * 3 * 64 * 4;
-}
-
-extern "C" int bem_pack_pw_weight_x6_strided(const float* W, float* Wp, int nsets, int M, int K, int64_t set_stride, int64_t row_stride,
-                                             int64_t col_stride, void* stream) {
-    BEM_REQUIRE(W && Wp, "pack_pw_weight_x6: null tensor");
-    BEM_REQUIRE(nsets >= 0 && M > 0 && K > 0 && set_stride >= 0 && row_stride >= 0 && col_stride >= 0, "pack_pw_weight_x6: bad shape / strides");
-    BEM_REQUIRE(((uintptr_t)Wp & 15) == 0, "pack_pw_weight_x6: output must be 16-byte aligned");
-    if (nsets == 0) return BEM_OK;
-    const int MT = cdiv(M, 32), KB = cdiv(K, 16);
-    const int64_t total = (int64_t)nsets * MT * KB * 64;
-    pack_x6_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(W, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB, total, set_stride,
-                                                                                 row_stride, col_stride);
-    return bem_check_launch("pack_pw_weight_x6");
-}
-
-extern "C" int bem_pack_pw_weight_x6_jobs(const void* jobs, const void* blks, int nblk, float* arena, void* stream) {
-    BEM_REQUIRE(jobs && blks && arena && nblk > 0, "pack_pw_weight_x6_jobs: bad arguments");
-    BEM_REQUIRE(((uintptr_t)arena & 15) == 0, "pack_pw_weight_x6_jobs: the arena must be 16-byte aligned");
-    pack_x6_jobs_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>((const packjob*)jobs, (const int32_t*)blks, arena);
-    return bem_check_launch("pack_pw_weight_x6_jobs");
-}
-
-extern "C" int bem_pack_pw_weight_x6(const float* W, float* Wp, int nsets, int M, int K, void* stream) {
-    return bem_pack_pw_weight_x6_strided(W, Wp, nsets, M, K, (int64_t)M * K, K, 1, stream);
-}
 
 extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
     BEM_REQUIRE(a, "pw_gemm_x6: null args");
@@ -857,214 +670,4 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
 #undef BEM_X6_STREAM
     }
     return bem_check_launch("pw_x6_stream");
-}
-
-// ================================================================================================
-// Dense convolutions as shifted 1x1 GEMM taps on the same x6 machinery (3x3 stride 1 pad 1; 4x4 stride 2 pad 1):
-//     out[co][p] = relu?( sum_{tap} sum_ci W[co][ci][tap] * x[ci][S*p + tap offset] + bias[co] ) + res1 + res2
-// No im2col patch: tap (ky, kx) reads the input pixels of the wave's 64 output pixels straight from global memory (the
-// displaced reads of a k-block overlap and are served by L1 / L2), masks the pixels that fall outside the image, splits
-// them into bf16 limbs and issues the six limb products against that tap's weight block.  The x loads of the next tap
-// are requested before the MFMAs of the current one.  Wp: (KH*KW taps, MT, KB, 3 limbs, 64 lanes) 16-byte vectors =
-// bem_pack_pw_weight_x6 of the (KH*KW, Cout, Cin) tap matrices.  Requires an even output width and Cin % 8 == 0.
-// ================================================================================================
-namespace {
-
-struct CvX {
-    const float* x; int64_t x_bs;
-    const u32x4* Wp; const float* bias; const float* res1; const float* res2; float* out;
-    int Cin, H, W, Ho, Wo, Cout, KB, MT, relu, pad, dil, res1_rep;
-};
-
-template <int MTW, int KH, int KW, int S>
-__global__ __launch_bounds__(256, 2) void conv_taps_x6_kernel(CvX k) {
-    constexpr int NSUB = 2, NTAP = KH * KW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kh = lane >> 5, n = lane & 31;
-    const int b = blockIdx.z, mt0 = blockIdx.y * MTW;
-    const int Lo = k.Ho * k.Wo, Li = k.H * k.W;
-    const int p0 = (xcd_tile(blockIdx.x, gridDim.x) * 4 + wave) * 64;
-    if (p0 >= Lo) return;
-    const int p = p0 + 2 * n;                       // this lane's two output pixels p, p + 1 (same row: Wo is even)
-    const bool live = p < Lo;
-    const int pc = live ? p : 0;
-    const int yo = pc / k.Wo, xo = pc - yo * k.Wo;
-    const int yi0 = yo * S - k.pad, xi0 = xo * S - k.pad;      // input position of tap (0, 0) for the first pixel
-    const float* xb = k.x + (int64_t)b * k.x_bs;
-    f32x16 acc[MTW][NSUB], alo[MTW][NSUB];
-#pragma unroll
-    for (int m = 0; m < MTW; ++m)
-#pragma unroll
-        for (int t = 0; t < NSUB; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][t][r] = alo[m][t][r] = 0.f;
-    const u32x4* wbase = k.Wp + lane;
-    const int64_t tap_stride = (int64_t)k.MT * k.KB * 3 * 64, mt_stride = (int64_t)k.KB * 3 * 64;
-    const int nsteps = k.KB * NTAP;
-    // step s = kb * NTAP + tap.  Loads of a step: 8 channels (16 kb + 8 kh + e) at the two input pixels of this tap.
-    auto load_x = [&](int s, float (&dst)[8][NSUB], float (&mk)[NSUB]) {
-        const int kb = min(s / NTAP, k.KB - 1), tap = s - (s / NTAP) * NTAP;
-        const int ky = tap / KW, kx = tap - ky * KW;
-        const int yy = yi0 + ky * k.dil, x0 = xi0 + kx * k.dil, x1 = x0 + S;
-        const bool rowok = live && yy >= 0 && yy < k.H;
-        mk[0] = (rowok && x0 >= 0 && x0 < k.W) ? 1.f : 0.f;
-        mk[1] = (rowok && x1 >= 0 && x1 < k.W) ? 1.f : 0.f;
-        const int q = yy * k.W + x0;
-        // the upper half-wave reads channels + 8; past Cin (a half-filled last k-block) it re-reads the lower half,
-        // whose weights there are zero
-        const int c0 = 16 * kb, hoff = (c0 + 8 < k.Cin) ? 8 * kh : 0;
-        if (S == 1) {
-            // the pair (q, q + 1) as ONE 8-byte load (global loads need dword alignment only) at a base clamped into the
-            // plane; d = q - base is 0 except at the two ends of the plane, where one of the two pixels is outside anyway
-            const int qb = min(max(q, 0), Li - 2), d = q - qb;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float* pl = xb + (int64_t)(min(c0 + e, k.Cin - 1 - hoff) + hoff) * Li;
-                float2 v;
-                __builtin_memcpy(&v, pl + qb, sizeof(v));
-                dst[e][0] = d > 0 ? v.y : v.x;
-                dst[e][1] = d < 0 ? v.x : v.y;
-            }
-        } else {
-            const int q0 = min(max(q, 0), Li - 1), q1 = min(max(q + S, 0), Li - 1);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float* pl = xb + (int64_t)(min(c0 + e, k.Cin - 1 - hoff) + hoff) * Li;
-                dst[e][0] = pl[q0];
-                dst[e][1] = pl[q1];
-            }
-        }
-    };
-    auto load_w = [&](int s, u32x4 (&dst)[MTW][3]) {
-        const int sc = min(s, nsteps - 1), kb = sc / NTAP, tap = sc - kb * NTAP;
-#pragma unroll
-        for (int m = 0; m < MTW; ++m) {
-            const bool ok = s < nsteps && mt0 + m < k.MT;
-            const u32x4* wp = wbase + tap * tap_stride + (int64_t)(mt0 + m < k.MT ? mt0 + m : 0) * mt_stride + (int64_t)kb * 3 * 64;
-            const uint32_t mk = ok ? 0xffffffffu : 0u;
-#pragma unroll
-            for (int li = 0; li < 3; ++li) {
-                const u32x4 w = wp[li * 64];
-                dst[m][li] = u32x4{w[0] & mk, w[1] & mk, w[2] & mk, w[3] & mk};
-            }
-        }
-    };
-    float xn[8][NSUB], mkn[NSUB];
-    u32x4 wn[MTW][3];
-    load_x(0, xn, mkn);
-    load_w(0, wn);
-    for (int s = 0; s < nsteps; ++s) {
-        u32x4 xl[NSUB][3], wc[MTW][3];
-#pragma unroll
-        for (int t = 0; t < NSUB; ++t) {
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = xn[e][t] * mkn[t];
-            split8(v, xl[t][0], xl[t][1], xl[t][2]);
-        }
-#pragma unroll
-        for (int m = 0; m < MTW; ++m)
-#pragma unroll
-            for (int li = 0; li < 3; ++li) wc[m][li] = wn[m][li];
-        load_x(s + 1, xn, mkn);          // past the end: clamped, never used
-        load_w(s + 1, wn);
-#pragma unroll
-        for (int m = 0; m < MTW; ++m)
-#pragma unroll
-            for (int t = 0; t < NSUB; ++t) mac6(wc[m], xl[t], acc[m][t], alo[m][t]);
-    }
-    // epilogue: out = relu?(acc + bias) + res1 + res2, plane bases uniform, one lane offset
-    const float lo = k.relu ? 0.f : -3.402823466e38f;
-    const uint32_t loff = (uint32_t)(4 * kh) * (uint32_t)Lo + (uint32_t)pc;
-    float* outb = k.out + (int64_t)b * k.Cout * Lo;
-    const float* r1b = k.res1 ? k.res1 + (int64_t)(b / k.res1_rep) * k.Cout * Lo : nullptr;      // one residual row per res1_rep output rows
-    const float* r2b = k.res2 ? k.res2 + (int64_t)b * k.Cout * Lo : nullptr;
-#pragma unroll
-    for (int m = 0; m < MTW; ++m) {
-        if (mt0 + m >= k.MT) continue;
-        const int rb = (mt0 + m) * 32;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float bv[4], rv[4][NSUB];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int urow = rb + 8 * g + i;
-                const int lrow = min(urow + 4 * kh, k.Cout - 1);
-                bv[i] = k.bias ? k.bias[lrow] : 0.f;
-                rv[i][0] = rv[i][1] = 0.f;
-                const uint32_t ro = (uint32_t)lrow * (uint32_t)Lo + (uint32_t)pc;
-                if (r1b) { const float2 q = *reinterpret_cast<const float2*>(r1b + ro); rv[i][0] += q.x; rv[i][1] += q.y; }
-                if (r2b) { const float2 q = *reinterpret_cast<const float2*>(r2b + ro); rv[i][0] += q.x; rv[i][1] += q.y; }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 4 * g + i, urow = rb + 8 * g + i;
-                const float o0 = fmaxf(acc[m][0][r] + alo[m][0][r] + bv[i], lo) + rv[i][0];
-                const float o1 = fmaxf(acc[m][1][r] + alo[m][1][r] + bv[i], lo) + rv[i][1];
-                if (live && urow + 4 * kh < k.Cout) *reinterpret_cast<float2*>(outb + (int64_t)urow * Lo + loff) = make_float2(o0, o1);
-            }
-        }
-    }
-}
-
-}  // namespace
-
-static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                            float* out, int B, int Cin, int H, int W, int Cout, int KH, int stride, int dil, int relu, int res1_rep, void* stream,
-                            const char* what) {
-    BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "%s: null tensor or res1_rep < 1", what);
-    BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", what);
-    BEM_REQUIRE((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1),
-                "%s: supported forms are 3x3 s1 (dilation 1 / 2, padding = dilation) and 3x3 s2 p1", what);
-    const int pad = dil;                                        // "same" padding of the dilated 3x3; 1 for the others
-    const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-    BEM_REQUIRE(Ho > 0 && Wo > 0 && Wo % 2 == 0 && Cin % 8 == 0 && H * W >= 2, "%s: needs an even output width and Cin %% 8 == 0 (got Wo=%d Cin=%d)", what, Wo, Cin);
-    BEM_REQUIRE(((uintptr_t)Wp & 15) == 0 && (((uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 7) == 0,
-                "%s: alignment (packed weights 16 bytes, out / residuals 8 bytes)", what);
-    BEM_REQUIRE((int64_t)Cout * Ho * Wo < (1ll << 30) && (int64_t)Cin * H * W < (1ll << 30), "%s: plane set too large for 32-bit lane offsets", what);
-    if (B == 0) return BEM_OK;
-    CvX k;
-    k.x = x; k.x_bs = x_bstride; k.Wp = reinterpret_cast<const u32x4*>(Wp); k.bias = bias; k.res1 = res1; k.res2 = res2; k.out = out;
-    k.Cin = Cin; k.H = H; k.W = W; k.Ho = Ho; k.Wo = Wo; k.Cout = Cout; k.KB = cdiv(Cin, 16); k.MT = cdiv(Cout, 32); k.relu = relu; k.pad = pad; k.dil = dil; k.res1_rep = res1_rep;
-    const int mtw = k.MT == 1 ? 1 : 2;
-    dim3 grid(cdiv(Ho * Wo, 256), cdiv(k.MT, mtw), B);
-    hipStream_t s = (hipStream_t)stream;
-    if (KH == 3 && stride == 1) {
-        if (mtw == 1) conv_taps_x6_kernel<1, 3, 3, 1><<<grid, 256, 0, s>>>(k);
-        else conv_taps_x6_kernel<2, 3, 3, 1><<<grid, 256, 0, s>>>(k);
-    } else {
-        if (mtw == 1) conv_taps_x6_kernel<1, 3, 3, 2><<<grid, 256, 0, s>>>(k);
-        else conv_taps_x6_kernel<2, 3, 3, 2><<<grid, 256, 0, s>>>(k);
-    }
-    return bem_check_launch(what);
-}
-
-extern "C" int bem_conv4x4s2_fast_supported(int Cin, int H, int W);
-extern "C" int bem_conv3x3_rows_supported(int Cin, int H, int W);
-int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2, float* out,
-                     int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream);      // conv_rows_x6.hip
-static bool rows_aligned(const float* x, int64_t x_bstride, const float* out, const float* res1, const float* res2) {
-    return x && out && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 15) == 0 && x_bstride % 4 == 0;
-}
-
-extern "C" int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                                  const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream) {
-    // the row form (conv_rows_x6.hip) where the shape allows; nine shifted taps otherwise
-    if (Cin > 0 && bem_conv3x3_rows_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2))
-        return conv_rows_launch(3, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, res1_rep, stream);
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, 3, 1, 1, relu, res1_rep, stream, "conv3x3_x6");
-}
-
-
-extern "C" int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                                    const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream) {
-    // the row form (conv_rows_x6.hip); shapes outside it (bem_conv4x4s2_fast_supported == 0) belong to bem_conv2d_mfma_f32
-    BEM_REQUIRE(Cin > 0 && bem_conv4x4s2_fast_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2),
-                "conv4x4s2_x6: needs W = 2 Wo with Wo a power of two <= 64, even H, Cin %% 8 == 0 and 16-byte aligned tensors");
-    return conv_rows_launch(4, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, 1, stream);
-}
-
-extern "C" int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                                    float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
-                                    void* stream) {
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, K, stride, dilation, relu, res1_rep, stream, "conv_taps_x6");
 }

@@ -4,7 +4,7 @@
 // As separate kernels (LayerNorm + in_proj GEMM, depthwise conv + SiLU, x_proj GEMM) the C-channel tensor t = in_proj(LN(x)) is written and read
 // once and xc is read a second time: 5.5 passes of C . P . 4 bytes where x in, xc out and the narrow xd out (2.5 passes) are what is needed.
 //
-// Mapping (one workgroup = 4 waves = one 4 x 32 pixel tile of one image; the tile machinery of gdmlp_x6.hip):
+// Mapping (one workgroup = 4 waves = one 4 x 32 pixel tile of one image; tile and LayerNorm prologue: x6_tile.h):
 //   * the tile's 6 x 34 halo is 204 pixels = 7 MFMA pixel blocks of 32; wave w owns blocks w and w + 4, LayerNorm-ed and split into three
 //     bf16 limbs in registers.
 //   * phase A  t (C rows x 204 halo pixels) = W_in xn on the bf16 matrix cores (six exact limb products) + b_in, zero outside the image (the
@@ -17,7 +17,7 @@
 // Weights are read per wave from L2 in operand order (27 KB per workgroup at C = 40).  Requires C <= 48, C % 8 == 0 (two channel halves of
 // whole groups of four), Mx <= 32.
 #include "bem_common.h"
-#include "x6_common.h"
+#include "x6_tile.h"
 
 namespace {
 
@@ -30,29 +30,21 @@ struct SfX {
     int C, Mx, H, W, tx;
 };
 
-constexpr int SF_TH = 4, SF_TW = 32, SF_HW = SF_TW + 2;
-constexpr int SF_NPH = (SF_TH + 2) * SF_HW;          // 204 halo pixels
-constexpr int SF_NPB = (SF_NPH + 31) / 32;           // 7 blocks
-constexpr int SF_TS = 208;                           // row stride of T (>= 205: the clamp slot of the unused lanes of block 6)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // KBM: k-blocks of 16 channels; CR: channel rows kept in LDS (C <= CR <= 16 KBM, CR % 4 == 0) -- 40 for the bench's width, so that two
 // workgroups fit a CU next to the staged in_proj operands
 template <int KBM, int CR>
 __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
     constexpr int MTI = (CR + 31) / 32;              // row blocks of in_proj
     constexpr int GS = CR + 4;                       // dwords per pixel row of G (conflict-free 16-byte accesses)
-    __shared__ __attribute__((aligned(16))) float T[CR * SF_TS];                       // [channel][halo pixel]
+    __shared__ __attribute__((aligned(16))) float T[CR * XT_TS];                       // [channel][halo pixel]
     __shared__ __attribute__((aligned(16))) float G[128 * GS + 8];                     // [tile pixel][channel]; phase C reads up to channel CM - 1
     __shared__ __attribute__((aligned(16))) u32x4 Wil[MTI * KBM * 3 * 64];             // in_proj operands [mt][kb][limb][lane], by LDS-DMA
     __shared__ __attribute__((aligned(16))) float DWl[CR * 12];                        // depthwise taps [channel][9 taps, bias, 2 pad]
     __shared__ float Bil[32 * MTI];                                                          // in_proj bias (zeros without one / past C)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kh = lane >> 5, n = lane & 31;
     const int b = blockIdx.z;
-    const int tile = xcd_tile(blockIdx.x, gridDim.x);
-    const int tyi = tile / k.tx, txi = tile - tyi * k.tx;
-    const int y0 = tyi * SF_TH, x0 = txi * SF_TW;
+    int y0, x0;
+    tile_origin(k.tx, y0, x0);
     const int L = k.H * k.W;
     const float* xb = k.x + (int64_t)b * k.C * L;
 
@@ -92,11 +84,11 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
             }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int hp = min((wave + 4 * i) * 32 + n, SF_TS - 1);
+            const int hp = min((wave + 4 * i) * 32 + n, XT_TS - 1);
             hpo[i] = hp;
-            const int hy = hp / SF_HW, hx = hp - hy * SF_HW;
+            const int hy = hp / XT_HW, hx = hp - hy * XT_HW;
             const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const bool in = hp < SF_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < SF_NPB;
+            const bool in = hp < XT_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < XT_NPB;
             msk[i] = in ? 1.f : 0.f;
             const int off = min(max(gy, 0), k.H - 1) * k.W + min(max(gx, 0), k.W - 1);
             float xr[KBM][8];
@@ -141,28 +133,21 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
     // ---- phase A: t = W_in xn + b_in over the halo, masked, into T
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        if (wave + 4 * i < SF_NPB) {                                                   // wave-uniform
+        if (wave + 4 * i < XT_NPB) {                                                   // wave-uniform
 #pragma unroll
             for (int mt = 0; mt < MTI; ++mt) {
-                f32x16 hi, lo;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) hi[r] = lo[r] = 0.f;
+                f32x16 hi = zero16(), lo = zero16();
 #pragma unroll
                 for (int kb = 0; kb < KBM; ++kb) {
                     const u32x4* wp = Wil + (mt * KBM + kb) * 192 + lane;
-                    const uint32_t on = kb < KB ? 0xffffffffu : 0u;
                     u32x4 wl[3];
-#pragma unroll
-                    for (int li = 0; li < 3; ++li) {
-                        const u32x4 w = wp[li * 64];
-                        wl[li] = u32x4{w[0] & on, w[1] & on, w[2] & on, w[3] & on};
-                    }
+                    load_w3_masked(wp, kb < KB ? 0xffffffffu : 0u, wl);
                     mac6(wl, xl[i][kb], hi, lo);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    if (row < CR) T[row * SF_TS + hpo[i]] = (hi[r] + lo[r] + Bil[row]) * msk[i];
+                    const int row = acc_row(r, kh, 32 * mt);
+                    if (row < CR) T[row * XT_TS + hpo[i]] = (hi[r] + lo[r] + Bil[row]) * msk[i];
                 }
             }
         }
@@ -174,12 +159,7 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
 #pragma unroll
     for (int kb = 0; kb < KBM; ++kb) {
         const u32x4* wp = k.Wpx + (int64_t)min(kb, KB - 1) * 192 + lane;
-        const uint32_t on = kb < KB ? 0xffffffffu : 0u;
-#pragma unroll
-        for (int li = 0; li < 3; ++li) {
-            const u32x4 w = wp[li * 64];
-            wx[kb][li] = u32x4{w[0] & on, w[1] & on, w[2] & on, w[3] & on};
-        }
+        load_w3_masked(wp, kb < KB ? 0xffffffffu : 0u, wx[kb]);
     }
     // ---- phase B: depthwise 3x3 + SiLU for tile row `wave`; lane = column n, channel half kh, groups of four channels
     const int oy = y0 + wave, ox = x0 + n;
@@ -194,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int c = kh * chalf + g0 + j;
-            const float* tp = T + c * SF_TS + wave * SF_HW + n;                        // halo (wave, n) = window origin of tile pixel (wave, n)
+            const float* tp = T + c * XT_TS + wave * XT_HW + n;                        // halo (wave, n) = window origin of tile pixel (wave, n)
             const f32x4* wv = reinterpret_cast<const f32x4*>(DWl + c * 12);
             const f32x4 w0 = wv[0], w1 = wv[1], w2 = wv[2];
             const float wq[9] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3], w2[0]};
@@ -202,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
 #pragma unroll
             for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
-                for (int tx = 0; tx < 3; ++tx) a = fmaf(wq[3 * ty + tx], tp[ty * SF_HW + tx], a);
+                for (int tx = 0; tx < 3; ++tx) a = fmaf(wq[3 * ty + tx], tp[ty * XT_HW + tx], a);
             o[j] = bem_silu(a);
             if (opix) xcb[(int64_t)c * L] = o[j];
         }
@@ -212,9 +192,7 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
 
     // ---- phase C: xd = W_x xc for the same 32 pixels (data crosses the two half-waves of this wave only)
     {
-        f32x16 hi, lo;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hi[r] = lo[r] = 0.f;
+        f32x16 hi = zero16(), lo = zero16();
 #pragma unroll
         for (int kb = 0; kb < KBM; ++kb) {
             const float* gq = gp + 16 * kb + 8 * kh;
@@ -228,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void ss2d_front_x6_kernel(SfX k) {
             float* xdb = k.xd + (int64_t)b * k.Mx * L + po;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int row = acc_row(r, kh);
                 if (row < k.Mx) xdb[(int64_t)row * L] = hi[r] + lo[r];
             }
         }
@@ -250,8 +228,8 @@ extern "C" int bem_ss2d_front_x6_f32(const float* x, const float* ln_w, const fl
     SfX k;
     k.x = x; k.ln_w = ln_w; k.ln_b = ln_b; k.ln_eps = ln_eps;
     k.Wpi = reinterpret_cast<const u32x4*>(Wp_in); k.bi = bias_in; k.dww = dww; k.dwb = dwb; k.Wpx = reinterpret_cast<const u32x4*>(Wp_x);
-    k.xc = xc; k.xd = xd; k.C = C; k.Mx = Mx; k.H = H; k.W = W; k.tx = cdiv(W, SF_TW);
-    dim3 grid(k.tx * cdiv(H, SF_TH), 1, B);
+    k.xc = xc; k.xd = xd; k.C = C; k.Mx = Mx; k.H = H; k.W = W; k.tx = cdiv(W, XT_TW);
+    dim3 grid(k.tx * cdiv(H, XT_TH), 1, B);
     hipStream_t s = (hipStream_t)stream;
     const int KB = cdiv(C, 16);
     if (KB == 1) ss2d_front_x6_kernel<1, 16><<<grid, 256, 0, s>>>(k);

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x6_kernel(WxK k) {
             const int gc = (nt0 + t) * 32 + n;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int gm = (mt0 + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int gm = acc_row(r, kh, (mt0 + m) * 32);
                 if (gm < k.M && gc < k.K) slot[(int64_t)gm * k.K + gc] = acc[m][t][r] + alo[m][t][r];
             }
         }

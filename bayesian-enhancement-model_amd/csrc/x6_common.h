@@ -1,5 +1,6 @@
-// Shared device helpers of the x6 (3-limb bf16) matrix-core kernels: operand typedefs, the exact limb split, the six-product MAC
-// and the XCD-aware tile order.  Included by pw_gemm_x6.hip, gdmlp_x6.hip, conv_rows_x6.hip and ss2d_front_x6.hip; see the header comment of pw_gemm_x6.hip.
+// Shared device helpers of the x6 (3-limb bf16) matrix-core kernels: operand typedefs, the exact limb split, the six-product MAC,
+// the accumulator layout and the XCD-aware tile order.  Included by pw_gemm_x6.hip, pack.hip, conv_x6.hip, upfuse_x6.hip, wgrad_x6.hip and (through
+// x6_tile.h) gdmlp_x6.hip and ss2d_front_x6.hip; see the header comment of pw_gemm_x6.hip.
 #pragma once
 #include "bem_common.h"
 
@@ -40,6 +41,16 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& h, u32x4& m, 
     }
 }
 
+// D layout of the 32x32 MFMA: register r of a lane in half kh = lane >> 5 holds output row acc_row(r, kh) of the tile, column lane & 31.
+// base = first row of the tile, added first: the sum keeps the association it had where it was written out (and with it the machine code)
+__device__ __forceinline__ int acc_row(int r, int kh, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * kh; }
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = 0.f;
+    return z;
+}
+
 __device__ __forceinline__ f32x16 mfma16(const u32x4& a, const u32x4& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -54,6 +65,16 @@ __device__ __forceinline__ void mac6(const u32x4 (&w)[3], const u32x4 (&x)[3], f
     lo = mfma16(w[0], x[1], lo);
     lo = mfma16(w[1], x[0], lo);
     hi = mfma16(w[0], x[0], hi);
+}
+
+// the three limbs of one packed operand block (16-byte vectors wp[0], wp[64], wp[128]) under a uniform all-ones / zero mask: blocks past the
+// matrix re-read a valid one and are switched off
+__device__ __forceinline__ void load_w3_masked(const u32x4* wp, uint32_t on, u32x4 (&dst)[3]) {
+#pragma unroll
+    for (int li = 0; li < 3; ++li) {
+        const u32x4 w = wp[li * 64];
+        dst[li] = u32x4{w[0] & on, w[1] & on, w[2] & on, w[3] & on};
+    }
 }
 
 // one 1 KiB piece global -> LDS: lane l moves the 16 bytes at sbase + voff (voff = 16 l) to lds_dst + 16 l.  sbase is wave-uniform (an

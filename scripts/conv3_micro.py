@@ -1,4 +1,4 @@
-"""The 3x3 convs of the eval step at the bench shapes on the row-form x6 kernel (conv_rows_x6.hip).
+"""The 3x3 convs of the eval step at the bench shapes on the row-form x6 kernel (conv_x6.hip).
    python scripts/conv3_micro.py [reps]"""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesian-enhancement-model_amd"))

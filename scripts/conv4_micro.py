@@ -1,4 +1,4 @@
-"""The two 4x4 stride-2 down-sampling convs of the Stage-II net at the bench shapes on the coalesced-row x6 kernel (conv_rows_x6.hip).
+"""The two 4x4 stride-2 down-sampling convs of the Stage-II net at the bench shapes on the coalesced-row x6 kernel (conv_x6.hip).
    python scripts/conv4_micro.py [reps]"""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bayesian-enhancement-model_amd"))

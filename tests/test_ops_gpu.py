@@ -629,11 +629,12 @@ def test_pw_gemm_x6_generic_epilogue_full_size(ops):
 
 @pytest.mark.parametrize("cfg", [(2, 40, 160, 16, 64, True), (4, 40, 160, 128, 128, True), (2, 24, 32, 13, 45, True), (1, 7, 16, 8, 32, False),
                                  (3, 48, 96, 5, 3, True), (1, 16, 64, 33, 70, True), (2, 80, 320, 64, 64, True), (1, 64, 48, 9, 37, False),
-                                 (2, 72, 16, 4, 32, True), (1, 33, 16, 2, 31, True)])
+                                 (2, 72, 16, 4, 32, True), (1, 33, 16, 2, 31, True), (1, 40, 160, 5, 33, True)])
 def test_gdmlp_x6_vs_chain_and_float64(ops, cfg):
     """bem_gdmlp_x6_f32 (the whole gdMlp branch: LayerNorm + project_in + depthwise 3x3 + GELU gate + project_out + residual, the
     2Hd- and Hd-channel tensors only in LDS) against the three-kernel chain and against torch in float64 (vmamba.py:116-133,1330-1333):
-    image borders inside and across the 4 x 32 tiles, ragged planes, C not a multiple of 16 / 32, no biases, both bench shapes."""
+    image borders inside and across the 4 x 32 tiles, ragged planes (5 x 33: a one-pixel tile column under a partial tile row), C not a
+    multiple of 16 / 32, no biases, both bench shapes."""
     B, C, Hd, H, W, bias = cfg
     g = torch.Generator().manual_seed(C * Hd + H)
     x = torch.randn(B, C, H, W, generator=g) * 2 + 0.3
@@ -818,7 +819,7 @@ def test_mc_mean(ops):
 @pytest.mark.parametrize("cfg", [(2, 40, 80, 128, 128, False), (1, 80, 160, 64, 64, False), (2, 8, 7, 4, 4, False), (1, 24, 33, 6, 16, True),
                                  (3, 16, 40, 2, 128, False), (1, 40, 96, 10, 32, True), (1, 48, 64, 34, 8, False)])
 def test_conv4x4s2_coalesced_rows(ops, cfg):
-    """The 4x4 stride-2 pad-1 down-sampling conv on the coalesced-row x6 kernel (conv4_x6.hip; DecompDualBranchDDWavelet_arch.py:40-41):
+    """The 4x4 stride-2 pad-1 down-sampling conv on the coalesced-row x6 kernel (conv_x6.hip; DecompDualBranchDDWavelet_arch.py:40-41):
     both bench shapes (40 -> 80 at 128x128, 80 -> 160 at 64x64), one / two / three row blocks of output channels incl. an odd count,
     half-filled last k-block (Cin % 16 == 8), output rows of 2 .. 64 pixels (1 .. 32 lanes per row: every DPP neighbour / padding case),
     odd output heights, a partly empty last wave, relu, a channel-slice input; against F.conv2d in float64 with the f32 run as yardstick."""
@@ -844,7 +845,7 @@ def test_conv4x4s2_coalesced_rows(ops, cfg):
 @pytest.mark.parametrize("cfg", [(2, 32, 32, 128, 128, True), (1, 32, 40, 128, 128, False), (2, 40, 16, 64, 64, True), (1, 8, 7, 5, 4, True),
                                  (3, 24, 33, 3, 8, False), (1, 16, 80, 9, 32, True), (1, 48, 32, 1, 16, False), (1, 32, 32, 37, 128, True)])
 def test_conv3x3_row_form(ops, cfg):
-    """3x3 stride-1 pad-1 convs on the row-form x6 kernel (conv_rows_x6.hip; QD/model4.py:181-200, DecompDualBranchDDWavelet_arch.py:190):
+    """3x3 stride-1 pad-1 convs on the row-form x6 kernel (conv_x6.hip; QD/model4.py:181-200, DecompDualBranchDDWavelet_arch.py:190):
     the decomposition net's 32 -> 32 at 128x128, first_conv 32 -> 40 and proj 40 -> 16, rows of 4 .. 128 pixels (1 .. 32 lanes per row),
     heights that leave the last wave partly empty, one / two / three row blocks of output channels, half-filled last k-block, relu and
     both residual inputs, a channel-slice input; against F.conv2d in float64 with the f32 run as yardstick."""
@@ -871,11 +872,11 @@ def test_conv3x3_row_form(ops, cfg):
 
 
 @pytest.mark.parametrize("cfg", [(2, 40, 3, 16, 64, True), (4, 40, 3, 128, 128, False), (2, 24, 2, 13, 45, True), (1, 8, 1, 8, 32, False),
-                                 (3, 48, 3, 5, 3, True), (1, 16, 6, 33, 70, True), (1, 32, 2, 4, 32, False)])
+                                 (3, 48, 3, 5, 3, True), (1, 16, 6, 33, 70, True), (1, 32, 2, 4, 32, False), (1, 40, 3, 5, 33, True)])
 def test_ss2d_front_x6_vs_chain_and_float64(ops, cfg):
     """bem_ss2d_front_x6_f32 (LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel, the in_proj output only in LDS) against the
-    three-kernel chain and against torch in float64 (vmamba.py:700-716,1326): image borders inside and across the 4 x 32 tiles, ragged planes,
-    C not a multiple of 16, with / without biases, the bench's level-0 shape."""
+    three-kernel chain and against torch in float64 (vmamba.py:700-716,1326): image borders inside and across the 4 x 32 tiles, ragged planes
+    (5 x 33: a one-pixel tile column under a partial tile row), C not a multiple of 16, with / without biases, the bench's level-0 shape."""
     B, C, R, H, W, bias = cfg
     Mx = 4 * (R + 2)
     g = torch.Generator().manual_seed(C * Mx + H)

@@ -152,7 +152,7 @@ def test_bnn_sample_every_element(ops, nsets):
 def unpack_x6(Wp, M, K):
     """(nsets, packed(M, K)) x6 operand -> natural (nsets, M, K) float32, exactly: 16-byte vector ((set MT + mt) KB + kb) 3 64 + limb 64
     + lane holds, for row mt 32 + (lane & 31), the eight k = kb 16 + (lane >> 5) 8 + e as bf16 pairs (even e in the low half); the
-    three limbs of a value add up to it without rounding (csrc/x6_common.h split8, csrc/pw_gemm_x6.hip pack_x6_item)."""
+    three limbs of a value add up to it without rounding (csrc/x6_common.h split8, csrc/pack.hip pack_x6_item)."""
     ns, MT, KB = Wp.shape[0], (M + 31) // 32, (K + 15) // 16
     u = Wp.contiguous().view(torch.int32).view(ns, MT, KB, 3, 2, 32, 4)
     v = torch.stack([(u << 16).view(torch.float32), (u & -65536).view(torch.float32)], -1).double().sum(3)     # (ns, MT, KB, kh, row, q, j)
