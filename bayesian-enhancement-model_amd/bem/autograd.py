@@ -14,14 +14,11 @@ of the flat buffer of ``bem.train.FlatParams``); the Functions return ``None`` f
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from . import ops
 from .native import BemNativeError
-from .native import check, lib
 
 
 def grad_of(p: torch.Tensor) -> torch.Tensor:
@@ -229,14 +226,6 @@ class Conv2dFn(Function):
 # ------------------------------------------------------------------------------------------------------------------
 # VSSBlock (vmamba.py:1319-1334) as one node
 # ------------------------------------------------------------------------------------------------------------------
-def _transpose_into(src, dst, dst_c0):
-    """dst[:, dst_c0 : dst_c0 + C] (B,*,H,W) = planes of src (B,C,W,H) transposed."""
-    B, C, Ws, Hs = src.shape
-    L = Ws * Hs
-    check(lib().bem_transpose_planes_f32(ctypes.c_void_p(src.data_ptr()), C * L, ctypes.c_void_p(dst.data_ptr() + 4 * dst_c0 * L),
-                                         dst.shape[1] * L, B, C, Ws, Hs, ops._stream()), "transpose_planes(into)")
-
-
 class VSSBlockFn(Function):
     @staticmethod
     def forward(ctx, x, blk, *params):
@@ -291,7 +280,7 @@ class VSSBlockFn(Function):
         # x_dbl gradient back in the stacked row order of the forward GEMM: [dir 0 | dir 2 | dir 1 | dir 3], row-major pixels
         dxd = torch.empty(B, 4 * M, H, W, device=x.device, dtype=x.dtype)
         ops.copy_channels(dxd0.view(B, 2 * M, H, W), dxd, 0)
-        _transpose_into(dxd1.view(B, 2 * M, W, H), dxd, 2 * M)
+        ops.transpose_planes_into(dxd1.view(B, 2 * M, W, H), dxd, 2 * M)
         ops.pw_wgrad_(dxd, xc, grad_of(op.x_proj_weight), blk_rows=M, perm=(0, 2, 1, 3))
         xw = op.x_proj_weight
         wallT = _pack(op, "wallT", [xw], lambda: torch.cat([xw.detach()[0], xw.detach()[2], xw.detach()[1], xw.detach()[3]], 0).t())

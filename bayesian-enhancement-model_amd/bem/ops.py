@@ -7,6 +7,9 @@ from __future__ import annotations
 
 import ctypes
 import os
+from inspect import signature as _signature
+from functools import wraps as _wraps
+from math import prod as _prod
 from typing import Optional
 
 import torch
@@ -34,6 +37,105 @@ def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32, optional=Fal
         raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
+
+
+# --------------------------------------------------------------------------- launch timing ----
+# bench.py asks for ONE op's launches to be bracketed by HIP events on the launch stream (torch's
+# current stream is the stream every wrapper launches on), together with that launch's algorithmic
+# bytes / flops.  Disabled (one None test and one Python frame per bracketed op) outside bench.py.
+_PROF = None
+# profile key -> (op wrapper it belongs to, roofline bound, kernel symbol reported to bench.py, predicate on the call)
+_KEYS = {
+    # the register-resident x6 GEMM for K <= 48 (level-0 in_proj / project_in / x_proj and the small Stage-I layers):
+    # every launch of the (vectorised, single-input or concat) instance, whatever M and L
+    "pw_x6_res<3,2,1>": ("pw_gemm", "hbm", "pw_x6_res_kernel<3, 2, 1, false, true>",
+                         lambda K, M, ln, L, mode: K <= 48 and L % 2 == 0 and mode != 1),
+    # the streaming x6 GEMM with two M-tiles per pass (project_out / out_proj / fuse 1x1 at K > 48 without LayerNorm):
+    # the kernel with the largest share of the step in profiles/r01_bench_kernel_stats.csv
+    "pw_x6_stream<2>": ("pw_gemm", "hbm", "pw_x6_stream_kernel<2, 2, false, true, false>",
+                        lambda K, M, ln, L, mode: K > 48 and not ln and M > 32 and L % 2 == 0 and mode != 1),
+    "pw_gemm": ("pw_gemm", "mfma", "pw_gemm* (all variants)", lambda K, M, ln, L, mode: True),
+    # the whole gdMlp branch in one kernel: x in, out out -- 8 bytes per element of x are its algorithmic bytes
+    # (HBM: 42 us at level 0) -- but its two GEMMs (2Hd x C and C x Hd per pixel) evaluated as six bf16 limb products are 242 GFLOP on the
+    # matrix cores (97 us at the dense bf16 peak): the matrix pipe is the roofline that bounds it.  flops = 6 x the f32 GEMM flops
+    # (what the x6 scheme must issue for the output pixels; halo and padding MFMAs are waste, not work).
+    "gdmlp_x6<3>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<3, 2, 2, false>", lambda C: 32 < C <= 48),
+    "gdmlp_x6<5>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<5, 3, 1, false>", lambda C: 64 < C <= 80),
+    "conv2d": ("conv2d", "mfma", "conv2d_kernel", None),
+    "dwconv3x3": ("dwconv3x3", "hbm", "dwconv3x3_kernel", None),
+    "ss2d_scan": ("ss2d_scan", "hbm", "ss2d_scan_kernel", None),
+    "transpose_planes": ("transpose_planes", "hbm", "transpose_planes_kernel", None),
+    # a decoder level's up + fuse as one kernel: f in, skip in, out out are its algorithmic bytes
+    "up_fuse": ("up_fuse", "hbm", "upfuse_x6_kernel<2>", None),
+    # training step (bench.py --config train)
+    "pw_wgrad": ("pw_wgrad_", "hbm", "wgrad_x6_kernel<2, 2> + wgrad_x6_reduce_kernel (1x1 weight gradients; wgrad_kernel<*> for L % 32 != 0)", None),
+    "conv_wgrad": ("conv_wgrad_", "mfma", "wgrad_kernel<*> (dense conv weight gradients)", None),
+    "ss2d_scan_bwd": ("ss2d_scan_bwd", "hbm", "ss2d_scan_bwd_kernel", None),
+    "dwact_bwd": ("dwact_bwd", "hbm", "dwact_bwd_kernel", None),
+    "ln_bwd": ("ln_bwd", "hbm", "ln_bwd_kernel", None),
+}
+
+
+def profile_start(key: str):
+    global _PROF
+    if key not in _KEYS:
+        raise ValueError(f"profile_start: unknown key {key}; choose from {sorted(_KEYS)}")
+    op, bound, symbol, pred = _KEYS[key]
+    _PROF = {"kernel": op, "symbol": symbol, "bound": bound, "pred": pred, "events": [], "bytes": 0.0, "flops": 0.0}
+
+
+def profile_stop():
+    global _PROF
+    p, _PROF = _PROF, None
+    if p is None:
+        return None
+    torch.cuda.synchronize()
+    ms = sum(s.elapsed_time(e) for s, e in p["events"])
+    return {"kernel": p["symbol"], "bound": p["bound"], "launches": len(p["events"]), "ms": ms,
+            "bytes": p["bytes"], "flops": p["flops"]}
+
+
+def _bracket(cost, sees=None):
+    """Makes an op one that a profile key (_KEYS) can time.  ``cost`` and ``sees`` are handed the call's arguments by the op's own
+    parameter names, defaults filled in, and name the ones they read (``**_`` takes the rest): cost returns the (algorithmic bytes,
+    flops) of the call, sees the tuple handed to the key's predicate (keys without a predicate count every call)."""
+    def deco(fn):
+        name, sig = fn.__name__, _signature(fn)
+        if sees is None and any(op == name and pred is not None for op, _, _, pred in _KEYS.values()):
+            raise TypeError(f"_bracket: a key of {name} has a predicate, so the op needs ``sees``")
+
+        @_wraps(fn)
+        def op(*a, **kw):
+            p = _PROF
+            if p is None or p["kernel"] != name:
+                return fn(*a, **kw)
+            args = sig.bind(*a, **kw)
+            args.apply_defaults()
+            if p["pred"] is not None and not p["pred"](*sees(**args.arguments)):
+                return fn(*a, **kw)
+            nb, nf = cost(**args.arguments)
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            out = fn(*a, **kw)
+            e.record()
+            p["bytes"] += nb
+            p["flops"] += nf
+            p["events"].append((s, e))
+            return out
+        return op
+    return deco
+
+
+_GRID_MAX = 65535        # the y and z extent of a launch grid: planes, candidates (x 3 channels) or images go there
+
+
+def _pslice(t, c0):
+    """Channel c0 of a contiguous float32 (B, Ct, *spatial) tensor as a pointer, and the tensor's batch stride in elements."""
+    Ct = t.shape[1]
+    if not 0 <= c0 <= Ct:
+        raise ValueError(f"channel offset {c0} outside a tensor of {Ct} channels")
+    L = _prod(t.shape[2:])
+    return ctypes.c_void_p(t.data_ptr() + 4 * c0 * L), Ct * L
 
 
 # --------------------------------------------------------------------------- operator seam ----
@@ -101,61 +203,63 @@ def cross_merge(ys):
 
 
 # --------------------------------------------------------------------------- fused SS2D -------
-def _xd_bstrides(name, xd0, xd1, B, rows, L):
-    """Batch strides of the x_dbl operands of the scans: (B,2,rows,L) float32, contiguous or channel slices of a wider buffer."""
+def ss2d_scan_n_supported(N):
+    return bool(lib().bem_ss2d_scan_n_supported(int(N)))
+
+
+def _scan_operands(op, n_from_A, acts, xd0, xd1, dtw, dtb, A, Ds, grads=None):
+    """The operand checks of every SS2D scan wrapper; returns (B, C, L, R, N, batch stride of xd0, of xd1).
+    acts: (name, tensor) pairs, all (B,C,L) (x0, x1 and, backward, dy0, dy1).  xd0 / xd1 (B,2,R+2N,L): contiguous, or channel slices
+    of a wider (B,*,L) buffer, whose batch stride is taken from the view.  n_from_A: A is (4C, N) and gives the d_state; otherwise A
+    holds 4C elements and N = 1.  grads: the accumulators (dAlog, dDs, ddtw, ddtb) of a backward."""
+    params = (("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds))
+    if grads is not None:
+        params += tuple(zip(("dAlog", "dDs", "ddtw", "ddtb"), grads))
+    for n, t in acts + params:
+        _chk(t, n)
+    x = acts[0][1]
+    B, C, L = x.shape
+    R, N = dtw.shape[2], 1
+    if n_from_A:
+        if A.dim() != 2 or A.shape[0] != 4 * C:
+            raise ValueError(f"{op}: A {tuple(A.shape)} is not (4C, N)")
+        N = A.shape[1]
+        if not ss2d_scan_n_supported(N):
+            raise NotImplementedError(f"{op}: d_state {N} outside 1..16")
+    rows = R + 2 * N
+    if any(t.shape != x.shape for _, t in acts) or xd0.shape != (B, 2, rows, L) or xd1.shape != xd0.shape:
+        raise ValueError(f"{op}: activation shapes: {[tuple(t.shape) for _, t in acts]} xd {tuple(xd0.shape)}/{tuple(xd1.shape)} R={R} N={N}")
+    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C * N or Ds.numel() != 4 * C:
+        raise ValueError(f"{op}: parameter shapes")
+    if grads is not None and [g.numel() for g in grads] != [4 * C * N, 4 * C, 4 * C * R, 4 * C]:
+        raise ValueError(f"{op}: gradient accumulator sizes")
     bs = []
     for n, t in (("xd0", xd0), ("xd1", xd1)):
         if not t.is_cuda or t.dtype != torch.float32:
             raise native.BemNativeError(f"{n} must be a float32 CUDA/HIP tensor")
         if t.stride()[1:] != (rows * L, L, 1) or (B > 1 and (t.stride(0) < 2 * rows * L or (L % 4 == 0 and t.stride(0) % 4))):
-            raise ValueError(f"{name}: {n}: only the batch stride may differ from a contiguous (B,2,R+2N,L) tensor")
+            raise ValueError(f"{op}: {n}: only the batch stride may differ from a contiguous (B,2,R+2N,L) tensor")
         bs.append(t.stride(0) if B > 1 else 0)
-    return bs
+    return B, C, L, R, N, bs[0], bs[1]
 
 
+@_bracket(lambda x0, xd0, **_: (4.0 * (2 * x0.numel() + 2 * xd0.numel() + 2 * x0.numel()), 0.0))
 def ss2d_scan(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
     """xd0 / xd1 (B,2,R+2,L): contiguous, or channel slices of a wider (B,*,L) buffer (batch stride taken from the view)."""
-    for n, t in (("x0", x0), ("x1", x1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
-        _chk(t, n)
-    B, C, L = x0.shape
-    R = dtw.shape[2]
-    if x1.shape != x0.shape or xd0.shape != (B, 2, R + 2, L) or xd1.shape != xd0.shape:
-        raise ValueError(f"ss2d_scan shapes: x {tuple(x0.shape)}/{tuple(x1.shape)} xd {tuple(xd0.shape)}/{tuple(xd1.shape)} R={R}")
-    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C:
-        raise ValueError("ss2d_scan parameter shapes")
-    bs = _xd_bstrides("ss2d_scan", xd0, xd1, B, R + 2, L)
-    y0 = torch.empty_like(x0)
-    y1 = torch.empty_like(x0)
+    B, C, L, R, _, bs0, bs1 = _scan_operands("ss2d_scan", False, (("x0", x0), ("x1", x1)), xd0, xd1, dtw, dtb, A, Ds)
+    y0, y1 = torch.empty_like(x0), torch.empty_like(x0)
     check(lib().bem_ss2d_scan_strided_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1),
-                                          B, C, L, R, bs[0], bs[1], _stream()), "ss2d_scan")
+                                          B, C, L, R, bs0, bs1, _stream()), "ss2d_scan")
     return y0, y1
-
-
-def ss2d_scan_n_supported(N):
-    return bool(lib().bem_ss2d_scan_n_supported(int(N)))
 
 
 def ss2d_scan_n(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
     """d_state N form of ss2d_scan (bem_ss2d_scan_n_f32): xd0 / xd1 (B,2,R+2N,L) with rows [dt | B_0..B_{N-1} | C_0..C_{N-1}]
     (contiguous or batch-strided channel slices), A (4C, N) = -exp(A_logs)."""
-    for n, t in (("x0", x0), ("x1", x1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
-        _chk(t, n)
-    B, C, L = x0.shape
-    R = dtw.shape[2]
-    if A.dim() != 2 or A.shape[0] != 4 * C:
-        raise ValueError(f"ss2d_scan_n: A {tuple(A.shape)} is not (4C, N)")
-    N = A.shape[1]
-    if not ss2d_scan_n_supported(N):
-        raise NotImplementedError(f"ss2d_scan_n: d_state {N} outside 1..16")
-    if x1.shape != x0.shape or xd0.shape != (B, 2, R + 2 * N, L) or xd1.shape != xd0.shape:
-        raise ValueError(f"ss2d_scan_n shapes: x {tuple(x0.shape)}/{tuple(x1.shape)} xd {tuple(xd0.shape)}/{tuple(xd1.shape)} R={R} N={N}")
-    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or Ds.numel() != 4 * C:
-        raise ValueError("ss2d_scan_n parameter shapes")
-    bs = _xd_bstrides("ss2d_scan_n", xd0, xd1, B, R + 2 * N, L)
-    y0 = torch.empty_like(x0)
-    y1 = torch.empty_like(x0)
+    B, C, L, R, N, bs0, bs1 = _scan_operands("ss2d_scan_n", True, (("x0", x0), ("x1", x1)), xd0, xd1, dtw, dtb, A, Ds)
+    y0, y1 = torch.empty_like(x0), torch.empty_like(x0)
     check(lib().bem_ss2d_scan_n_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1),
-                                    B, C, L, R, N, bs[0], bs[1], _stream()), "ss2d_scan_n")
+                                    B, C, L, R, N, bs0, bs1, _stream()), "ss2d_scan_n")
     return y0, y1
 
 
@@ -166,31 +270,46 @@ def ss2d_scan_rm_supported(H, W, R):
 def ss2d_scan_rm(x, xd0, xd1, dtw, dtb, A, Ds):
     """Row-major form: x (B,C,H,W); xd0 (B,2,R+2,L) row-major order, xd1 (B,2,R+2,L) transposed pixel order (either may be
     a batch-strided channel slice); returns y0, y1 both (B,C,H,W) row-major."""
-    for n, t in (("x", x), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
+    for n, t in (("x", x), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):      # a wrong tensor is reported before an unsupported plane
         _chk(t, n)
     B, C, H, W = x.shape
-    L, R = H * W, dtw.shape[2]
-    if not ss2d_scan_rm_supported(H, W, R):
-        raise ValueError(f"ss2d_scan_rm: plane {H}x{W} / dt_rank {R} not supported")
-    if xd0.shape != (B, 2, R + 2, L) or xd1.shape != xd0.shape or dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C:
-        raise ValueError("ss2d_scan_rm: shapes")
-    bs = _xd_bstrides("ss2d_scan_rm", xd0, xd1, B, R + 2, L)
+    if not ss2d_scan_rm_supported(H, W, dtw.shape[2]):
+        raise ValueError(f"ss2d_scan_rm: plane {H}x{W} / dt_rank {dtw.shape[2]} not supported")
+    _, _, _, R, _, bs0, bs1 = _scan_operands("ss2d_scan_rm", False, (("x", x.view(B, C, H * W)),), xd0, xd1, dtw, dtb, A, Ds)
     y0, y1 = torch.empty_like(x), torch.empty_like(x)
-    check(lib().bem_ss2d_scan_rm_f32(_p(x), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1), B, C, H, W, R, bs[0], bs[1], _stream()),
+    check(lib().bem_ss2d_scan_rm_f32(_p(x), _p(xd0), _p(xd1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y0), _p(y1), B, C, H, W, R, bs0, bs1, _stream()),
           "ss2d_scan_rm")
     return y0, y1
 
 
+def _transpose(src, src_c0, C, dst=None, dst_c0=0):
+    """dst[:, dst_c0:dst_c0+C] (B,*,W,H) = the planes of src[:, src_c0:src_c0+C] (B,*,H,W) transposed, in one launch (its B C planes
+    go into gridDim.z).  C None: every channel from src_c0 on; dst None: a new (B,C,W,H) tensor.  Returns dst."""
+    _chk(src, "src")
+    B, Cs, H, W = src.shape
+    C = Cs - src_c0 if C is None else C
+    if C < 0 or src_c0 < 0 or src_c0 + C > Cs:
+        raise ValueError(f"transpose_planes: channels [{src_c0}, {src_c0 + C}) of a source with {Cs}")
+    if B * C > _GRID_MAX:
+        raise ValueError(f"transpose_planes: at most {_GRID_MAX} planes per launch, got {B * C}")
+    if dst is None:
+        dst = torch.empty(B, C, W, H, device=src.device, dtype=src.dtype)
+    _chk(dst, "dst")
+    if dst.dim() != 4 or dst.shape[0] != B or tuple(dst.shape[2:]) != (W, H) or dst_c0 < 0 or dst_c0 + C > dst.shape[1]:
+        raise ValueError(f"transpose_planes: {C} transposed planes of src {tuple(src.shape)} do not fit dst {tuple(dst.shape)} at channel {dst_c0}")
+    (sp, sbs), (dp, dbs) = _pslice(src, src_c0), _pslice(dst, dst_c0)
+    check(lib().bem_transpose_planes_f32(sp, sbs, dp, dbs, B, C, H, W, _stream()), "transpose_planes")
+    return dst
+
+
 def transpose_plane_slice(x, c0, C):
     """x (B,Ct,H,W) contiguous -> transposed planes of channels [c0, c0+C): (B,C,W,H) contiguous."""
-    _chk(x, "x")
-    B, Ct, H, W = x.shape
-    if c0 < 0 or c0 + C > Ct or B * C > 65535:
-        raise ValueError("transpose_plane_slice: channel range / plane count")
-    out = torch.empty(B, C, W, H, device=x.device, dtype=x.dtype)
-    check(lib().bem_transpose_planes_f32(ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W), Ct * H * W, _p(out), C * H * W, B, C, H, W, _stream()),   # (nbatch, planes per batch)
-          "transpose_planes")
-    return out
+    return _transpose(x, c0, C)
+
+
+def transpose_planes_into(src, dst, dst_c0):
+    """dst[:, dst_c0:dst_c0+C] = src.transpose(2, 3) for src (B,C,H,W) and dst (B,*,W,H), both contiguous; dst's other channels stay."""
+    return _transpose(src, 0, None, dst, dst_c0)
 
 
 # --------------------------------------------------------------------------- pointwise GEMM ---
@@ -270,6 +389,18 @@ def pack_pw_weight(W, x6=True):
     return out
 
 
+def _pw_gemm_sees(x1, M, x2, in_mode, ln, **_):
+    return x1.shape[1] + (x2.shape[1] if in_mode == 2 else 0), M, ln is not None, x1[0, 0].numel(), in_mode
+
+
+def _pw_gemm_cost(x1, Wp, M, x2, in_mode, res, **_):
+    B, L = x1.shape[0], x1[0, 0].numel()
+    C2 = 0 if x2 is None else x2.shape[1]
+    K = x1.shape[1] + (C2 if in_mode == 2 else 0)
+    return 4.0 * B * L * (x1.shape[1] + C2 + M + (M if res is not None else 0)) + 4.0 * Wp.numel(), 2.0 * M * K * L * B
+
+
+@_bracket(_pw_gemm_cost, _pw_gemm_sees)
 def pw_gemm(x1, Wp, M, *, x2=None, in_mode=0, ln=None, ln_eps=1e-5, bias=None, res=None, prelu=None,
             convT_Win: int = 0, out=None):
     """x1 (B,C1,*spatial); Wp packed (1|B, packed(M,K)); returns (B,M,*spatial) (or (B,M/4,2H,2W) for convT)."""
@@ -343,6 +474,11 @@ class UpFuseWeights:
         self.Wc, self.Wf2, self.bias, self.cin = Wc, Wf2, bias, int(cin)
 
 
+def _up_fuse_cost(f, skip, folded, **_):
+    return 4.0 * (f.numel() + 2 * skip.numel() + folded.Wc.numel() + folded.Wf2.numel()), 2.0 * skip.numel() * (f.shape[1] + skip.shape[1])
+
+
+@_bracket(_up_fuse_cost)
 def up_fuse(f, skip, folded: UpFuseWeights):
     """fuse(cat(up(f), skip)) of a decoder level as one kernel: f (B,Cin,h,w), skip (B,Cin/2,2h,2w) -> (B,Cin/2,2h,2w)."""
     _chk(f, "f"); _chk(skip, "skip"); _chk(folded.Wc, "Wc"); _chk(folded.Wf2, "Wf2"); _chk(folded.bias, "bias")
@@ -428,6 +564,12 @@ def dw_gate_params10(dww, dwb, Hd):
     return torch.cat([w, b], 1).contiguous()
 
 
+def _gdmlp_x6_cost(x, Hd, **_):
+    B, C, H, W = x.shape
+    return 8.0 * x.numel(), 6.0 * 2.0 * B * H * W * (2 * Hd * C + Hd * C)
+
+
+@_bracket(_gdmlp_x6_cost, lambda x, **_: (x.shape[1],))
 def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, Hd):
     """x + project_out(GELU(h1) * h2) + b_o with [h1; h2] = dw3x3(project_in(LayerNorm2d(x))) in ONE kernel (bem_gdmlp_x6_f32).
     Wp_gate = pack_pw_weight(W_i[gate_interleave(Hd)], x6=True), bias_gate = b_i[gate_interleave(Hd)] (zeros without a bias);
@@ -444,13 +586,17 @@ def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, 
         raise ValueError("gdmlp_x6: parameter shapes")
     _chk_packed1("gdmlp_x6", (("Wp_gate", Wp_gate, 2 * Hd, C), ("Wp_out", Wp_out, C, Hd)))
     out = torch.empty_like(x)
-    s = _timed("gdmlp_x6", 8.0 * x.numel(), 6.0 * 2.0 * B * H * W * (2 * Hd * C + Hd * C)) if _PROF is not None and _PROF["kernel"] == "gdmlp_x6" and _PROF["pred"](C) else None
     check(lib().bem_gdmlp_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_gate), _p(bias_gate), _p(dw10), _p(Wp_out),
                                  _p(bias_out), _p(out), B, C, Hd, H, W, _stream()), "gdmlp_x6")
-    _timed_end(s)
     return out
 
 
+def _dwconv3x3_cost(x, mode, **_):
+    B, Cin, H, W = x.shape
+    return 4.0 * B * H * W * (Cin + (Cin // 2 if mode == 2 else Cin)), 18.0 * B * Cin * H * W
+
+
+@_bracket(_dwconv3x3_cost)
 def dwconv3x3(x, w, bias=None, mode=0):
     """mode 0 plain, 1 SiLU, 2 gdMlp gate (x has 2*Cout channels), 3 PostSmooth.  w (Cw,1,3,3) or (B,Cw,1,3,3)."""
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias", optional=True)
@@ -499,6 +645,19 @@ class ConvWeight:
         return self._f32
 
 
+def _conv_out_hw(H, W, KH, KW, stride, pad, dilation=1):
+    return (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+
+
+def _conv2d_cost(x, w, stride, pad, res1, res2, dilation, **_):
+    B, _, H, W = x.shape
+    Co, Ci, KH, KW = (w.w if isinstance(w, ConvWeight) else w).shape
+    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad, dilation)
+    nres = (res1 is not None) + (res2 is not None)
+    return 4.0 * B * (Ci * H * W + Co * Ho * Wo * (1 + nres)) + 4.0 * Co * Ci * KH * KW, 2.0 * B * Co * Ci * KH * KW * Ho * Wo
+
+
+@_bracket(_conv2d_cost)
 def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
     """Dense conv.  ``cin_slice=(c0, Cin)`` convolves channels [c0, c0+Cin) of a wider contiguous x.
     ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
@@ -518,11 +677,12 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
             raise ValueError("conv2d: channel slice out of range")
     elif Ct != Cin:
         raise ValueError(f"conv2d: input has {Ct} channels, weight expects {Cin}")
-    Ho, Wo = (H + 2 * pad - dilation * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (KW - 1) - 1) // stride + 1
+    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad, dilation)
     out = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=x.dtype)
     res1_rep = int(res1_rep)
     if res1_rep < 1 or (res1_rep != 1 and res1 is None):
         raise ValueError("conv2d: res1_rep must be >= 1 and needs res1")
+    xp, xbs = _pslice(x, c0)
     res_shapes = (("res1", res1, (B // res1_rep if B % res1_rep == 0 else -1,) + tuple(out.shape[1:])), ("res2", res2, tuple(out.shape)))
     if dilation != 1 or (KH, KW, stride) == (3, 3, 2):
         if (KH, KW) != (3, 3) or pad != dilation or Wo % 2 or Cin % 8 or (c0 * H * W) % 2:
@@ -530,8 +690,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         for n, r, shp in res_shapes:
             if r is not None and tuple(r.shape) != shp:
                 raise ValueError(f"conv2d: {n} shape")
-        xp_ = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
-        check(lib().bem_conv_taps_x6_f32(xp_, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
+        check(lib().bem_conv_taps_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
                                          dilation, int(relu), res1_rep, _stream()), "conv_taps_x6")
         return out
     for n, r, shp in res_shapes:
@@ -539,24 +698,23 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
             raise ValueError(f"conv2d: {n} shape")
     if bias is not None and bias.shape != (Cout,):
         raise ValueError("conv2d: bias shape")
-    xp = ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W)
     if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
         # nine shifted 1x1 taps on the bf16-limb GEMM machinery (conv_x6.hip)
-        check(lib().bem_conv3x3_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv3x3_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
         return out
     conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
-        and (Ct * H * W) % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
+        and xbs % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
     if conv4_fast:
         # the coalesced-row form (conv_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
-        check(lib().bem_conv4x4s2_x6_f32(xp, Ct * H * W, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv4x4s2_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                          Cout, int(relu), _stream()), "conv4x4s2_x6")
         return out
     if USE_CONV_MFMA and Cout <= 160 and ((KH, KW, stride) in ((3, 3, 1), (4, 4, 2))):
-        check(lib().bem_conv2d_mfma_f32(xp, Ct * H * W, _p(cw.f32()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
+        check(lib().bem_conv2d_mfma_f32(xp, xbs, _p(cw.f32()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                         Cout, KH, KW, stride, pad, int(relu), res1_rep, _stream()), "conv2d_mfma")
         return out
-    check(lib().bem_conv2d_f32(xp, Ct * H * W, _p(w), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW,
+    check(lib().bem_conv2d_f32(xp, xbs, _p(w), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW,
                                stride, pad, int(relu), res1_rep, _stream()), "conv2d")
     return out
 
@@ -569,7 +727,7 @@ def quat_dwt(x, c0=0):
     if c0 + 3 > Ct or H % 2 or W % 2:
         raise ValueError("quat_dwt: needs 3 channels and even H, W")
     out = torch.empty(B, 32, H // 2, W // 2, device=x.device, dtype=x.dtype)
-    check(lib().bem_quat_dwt_f32(ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W), Ct * H * W, _p(out), B, H, W, _stream()), "quat_dwt")
+    check(lib().bem_quat_dwt_f32(*_pslice(x, c0), _p(out), B, H, W, _stream()), "quat_dwt")
     return out
 
 
@@ -665,61 +823,46 @@ def attn_fold(f1, f2, attn_w, fuse_w, fuse_b):
 
 
 # --------------------------------------------------------------------------- layout helpers ---
+@_bracket(lambda x, **_: (8.0 * x.numel(), 0.0))
 def transpose_planes(x):
     """(B,C,H,W) -> (B,C,W,H), contiguous."""
     _chk(x, "x")
     B, C, H, W = x.shape
     out = torch.empty(B, C, W, H, device=x.device, dtype=x.dtype)
     n = B * C
-    # plane count goes into gridDim.z (<= 65535): split large batches
-    step = 65535
-    xf, of = x.view(n, H * W), out.view(n, H * W)
-    for s in range(0, n, step):
-        m = min(step, n - s)
-        check(lib().bem_transpose_planes_f32(_p(xf[s:]), 0, _p(of[s:]), 0, 1, m, H, W, _stream()), "transpose_planes")
+    xf, of = x.view(1, n, H, W), out.view(1, n, W, H)
+    for s in range(0, n, _GRID_MAX):            # large batches: one launch per _GRID_MAX planes
+        _transpose(xf, s, min(_GRID_MAX, n - s), of, s)
     return out
+
+
+def _channels(op, fn, src, dst, dst_c0, src_c0, C, rep=None):
+    """The body of copy_channels, copy_channels_rep and add_channels: ``op`` names the wrapper in messages, ``fn`` is its library function."""
+    _chk(src, "src"); _chk(dst, "dst")
+    Cs = src.shape[1]
+    C = Cs - src_c0 if C is None else C
+    L = _prod(src.shape[2:])
+    Bd = src.shape[0] * (1 if rep is None else int(rep))
+    if dst.shape[0] != Bd or _prod(dst.shape[2:]) != L or C < 0 or dst_c0 + C > dst.shape[1] or src_c0 + C > Cs:
+        raise ValueError(f"{op}: shapes")
+    rep_arg = () if rep is None else (int(rep),)
+    check(fn(*_pslice(src, src_c0), *_pslice(dst, dst_c0), Bd, C, L, *rep_arg, _stream()), op)
+    return dst
 
 
 def copy_channels(src, dst, dst_c0, src_c0=0, C=None):
     """dst[:, dst_c0:dst_c0+C] = src[:, src_c0:src_c0+C] (same spatial size)."""
-    _chk(src, "src"); _chk(dst, "dst")
-    B, Cs = src.shape[0], src.shape[1]
-    C = Cs - src_c0 if C is None else C
-    L = src[0, 0].numel()
-    if dst.shape[0] != B or dst[0, 0].numel() != L or dst_c0 + C > dst.shape[1] or src_c0 + C > Cs:
-        raise ValueError("copy_channels: shapes")
-    check(lib().bem_copy_channels_f32(ctypes.c_void_p(src.data_ptr() + 4 * src_c0 * L), Cs * L,
-                                      ctypes.c_void_p(dst.data_ptr() + 4 * dst_c0 * L), dst.shape[1] * L, B, C, L,
-                                      _stream()), "copy_channels")
-    return dst
+    return _channels("copy_channels", lib().bem_copy_channels_f32, src, dst, dst_c0, src_c0, C)
 
 
 def copy_channels_rep(src, dst, dst_c0, rep, src_c0=0, C=None):
     """dst[b, dst_c0:dst_c0+C] = src[b // rep, src_c0:src_c0+C]  (dst has rep times the rows of src)."""
-    _chk(src, "src"); _chk(dst, "dst")
-    Bs, Cs = src.shape[0], src.shape[1]
-    C = Cs - src_c0 if C is None else C
-    L = src[0, 0].numel()
-    if dst.shape[0] != Bs * rep or dst[0, 0].numel() != L or dst_c0 + C > dst.shape[1] or src_c0 + C > Cs:
-        raise ValueError("copy_channels_rep: shapes")
-    check(lib().bem_copy_channels_rep_f32(ctypes.c_void_p(src.data_ptr() + 4 * src_c0 * L), Cs * L,
-                                          ctypes.c_void_p(dst.data_ptr() + 4 * dst_c0 * L), dst.shape[1] * L, Bs * rep, C, L, int(rep),
-                                          _stream()), "copy_channels_rep")
-    return dst
+    return _channels("copy_channels_rep", lib().bem_copy_channels_rep_f32, src, dst, dst_c0, src_c0, C, rep)
 
 
 def add_channels(src, dst, dst_c0, src_c0=0, C=None):
     """dst[:, dst_c0:dst_c0+C] += src[:, src_c0:src_c0+C] (same spatial size)."""
-    _chk(src, "src"); _chk(dst, "dst")
-    B, Cs = src.shape[0], src.shape[1]
-    C = Cs - src_c0 if C is None else C
-    L = src[0, 0].numel()
-    if dst.shape[0] != B or dst[0, 0].numel() != L or dst_c0 + C > dst.shape[1] or src_c0 + C > Cs:
-        raise ValueError("add_channels: shapes")
-    check(lib().bem_add_channels_f32(ctypes.c_void_p(src.data_ptr() + 4 * src_c0 * L), Cs * L,
-                                     ctypes.c_void_p(dst.data_ptr() + 4 * dst_c0 * L), dst.shape[1] * L, B, C, L,
-                                     _stream()), "add_channels")
-    return dst
+    return _channels("add_channels", lib().bem_add_channels_f32, src, dst, dst_c0, src_c0, C)
 
 
 def bilinear_up(src, s, dst=None, dst_c0=0):
@@ -731,9 +874,7 @@ def bilinear_up(src, s, dst=None, dst_c0=0):
     _chk(dst, "dst")
     if dst.shape[0] != B or dst.shape[2] != H * s or dst.shape[3] != W * s or dst_c0 + C > dst.shape[1]:
         raise ValueError("bilinear_up: dst shape")
-    Lo = H * s * W * s
-    check(lib().bem_bilinear_up_f32(_p(src), C * H * W, ctypes.c_void_p(dst.data_ptr() + 4 * dst_c0 * Lo),
-                                    dst.shape[1] * Lo, B, C, H, W, s, _stream()), "bilinear_up")
+    check(lib().bem_bilinear_up_f32(_p(src), C * H * W, *_pslice(dst, dst_c0), B, C, H, W, s, _stream()), "bilinear_up")
     return dst
 
 
@@ -1073,9 +1214,6 @@ def se_gate_bwd(mean, w1, w2, y, dy, dw1, dw2):
     dmean = torch.empty_like(mean)
     check(lib().bem_se_gate_bwd_f32(_p(mean), _p(w1), _p(w2), _p(y), _p(dy), _p(dmean), _p(dw1), _p(dw2), B, C, Cr, _stream()), "se_gate_bwd")
     return dmean
-
-
-_GRID_MAX = 65535        # the y and z extent of a launch grid: the selection tail puts candidates (x 3 channels) or images there
 
 
 def _spi(op, Bn, samples_per_image):
@@ -1465,6 +1603,11 @@ def add(a, b, alpha=1.0):
     return out
 
 
+def _ln_bwd_cost(x1, x2, dres, want_n, **_):
+    return 4.0 * x1.numel() * (3 + (x2 is not None) + (dres is not None) + bool(want_n)), 0.0
+
+
+@_bracket(_ln_bwd_cost)
 def ln_bwd(x1, dn, gamma, beta, eps, dgamma, dbeta, x2=None, dres=None, want_n=True):
     """LayerNorm2d backward over channels of x = x1 (+ x2): returns (dx, n = LN(x) | None); dgamma / dbeta accumulated."""
     for n, t in (("x1", x1), ("dn", dn), ("gamma", gamma), ("beta", beta), ("dgamma", dgamma), ("dbeta", dbeta)):
@@ -1492,6 +1635,7 @@ def ln_fwd(x1, gamma, beta, eps, x2=None):
     return out
 
 
+@_bracket(lambda t, dout, **_: (4.0 * (2 * t.numel() + dout.numel()), 40.0 * t.numel()))
 def dwact_bwd(t, w, bias, dout, dw, dbias, mode):
     """Backward of dwconv3x3(mode) through the activation: returns dpre (like t); dw (Cw,1,3,3) / dbias accumulated."""
     _chk(t, "t"); _chk(w, "w"); _chk(bias, "bias", optional=True); _chk(dout, "dout"); _chk(dw, "dw"); _chk(dbias, "dbias", optional=True)
@@ -1513,6 +1657,14 @@ WGRAD_X6_MIN_PIXELS = 16384
 _WGX_WS = {}                                               # per-device scratch of the x6 weight-gradient kernel (stream-ordered reuse)
 
 
+def _pw_wgrad_cost(dy, x1, x2, M, **_):
+    B, L = x1.shape[0], x1[0, 0].numel()
+    M = dy.shape[1] if M is None else M
+    K = x1.shape[1] + (0 if x2 is None else x2.shape[1])
+    return 4.0 * B * L * (M + K) + 4.0 * M * K, 2.0 * M * K * B * L
+
+
+@_bracket(_pw_wgrad_cost)
 def pw_wgrad_(dy, x1, dw, x2=None, dbias=None, blk_rows=0, perm=(0, 1, 2, 3), dy_bstride=0, M=None):
     """dw (M, C1 + C2) += dy . cat(x1, x2)^T over batch and pixels; dbias (M) += row sums of dy.
     dy may be a channel slice of a wider tensor (pass M and dy_bstride)."""
@@ -1549,6 +1701,12 @@ def pw_wgrad_(dy, x1, dw, x2=None, dbias=None, blk_rows=0, perm=(0, 1, 2, 3), dy
     return dw
 
 
+def _conv_wgrad_cost(dy, x, dw, **_):
+    Cout, Cin, KH, KW = dw.shape
+    return 4.0 * (dy.numel() + x.shape[0] * Cin * x.shape[2] * x.shape[3]) + 4.0 * dw.numel(), 2.0 * dy.numel() * Cin * KH * KW
+
+
+@_bracket(_conv_wgrad_cost)
 def conv_wgrad_(dy, x, dw, dbias=None, stride=1, pad=1, cin_slice=None):
     """dw (Cout,Cin,KH,KW) += weight gradient of conv2d(x, w, stride, pad); dbias (Cout) += sum dy."""
     _chk(dy, "dy"); _chk(x, "x"); _chk(dw, "dw"); _chk(dbias, "dbias", optional=True)
@@ -1561,10 +1719,9 @@ def conv_wgrad_(dy, x, dw, dbias=None, stride=1, pad=1, cin_slice=None):
             raise ValueError("conv_wgrad: channel slice")
     elif Ct != Cin:
         raise ValueError("conv_wgrad: channels")
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    if tuple(dy.shape) != (B, Cout, Ho, Wo) or (dbias is not None and dbias.numel() != Cout):
+    if tuple(dy.shape) != (B, Cout) + _conv_out_hw(H, W, KH, KW, stride, pad) or (dbias is not None and dbias.numel() != Cout):
         raise ValueError("conv_wgrad: dy / dbias shapes")
-    check(lib().bem_conv_wgrad_f32(_p(dy), ctypes.c_void_p(x.data_ptr() + 4 * c0 * H * W), Ct * H * W, _p(dw), _p(dbias), B, Cin, H, W, Cout,
+    check(lib().bem_conv_wgrad_f32(_p(dy), *_pslice(x, c0), _p(dw), _p(dbias), B, Cin, H, W, Cout,
                                    KH, KW, stride, pad, _stream()), "conv_wgrad")
     return dw
 
@@ -1634,25 +1791,15 @@ def fusion_head_bwd_(o1, o2, dout, w1=None, b1=None, w2=None, dw1=None, db1=None
     return do1, do2
 
 
+@_bracket(lambda x0, xd0, **_: (4.0 * (6 * x0.numel() + 4 * xd0.numel()), 0.0))
 def ss2d_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw, ddtb):
     """Backward of ss2d_scan: returns (dx0, dx1, dxd0, dxd1); parameter gradients accumulated into dAlog (4C), dDs (4C),
     ddtw (4,C,R), ddtb (4,C)."""
-    for n, t in (("x0", x0), ("x1", x1), ("dy0", dy0), ("dy1", dy1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds), ("dAlog", dAlog),
-                 ("dDs", dDs), ("ddtw", ddtw), ("ddtb", ddtb)):
-        _chk(t, n)
-    B, C, L = x0.shape
-    R = dtw.shape[2]
-    if x1.shape != x0.shape or dy0.shape != x0.shape or dy1.shape != x0.shape or xd0.shape != (B, 2, R + 2, L) or xd1.shape != xd0.shape:
-        raise ValueError("ss2d_scan_bwd: activation shapes")
-    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C or dAlog.numel() != 4 * C or dDs.numel() != 4 * C \
-            or ddtw.numel() != 4 * C * R or ddtb.numel() != 4 * C:
-        raise ValueError("ss2d_scan_bwd: parameter shapes")
-    bs = _xd_bstrides("ss2d_scan_bwd", xd0, xd1, B, R + 2, L)
-    dx0, dx1 = torch.empty_like(x0), torch.empty_like(x0)
-    dxd0 = torch.empty(B, 2, R + 2, L, device=x0.device, dtype=x0.dtype)
-    dxd1 = torch.empty(B, 2, R + 2, L, device=x0.device, dtype=x0.dtype)
+    B, C, L, R, _, bs0, bs1 = _scan_operands("ss2d_scan_bwd", False, (("x0", x0), ("x1", x1), ("dy0", dy0), ("dy1", dy1)), xd0, xd1,
+                                             dtw, dtb, A, Ds, (dAlog, dDs, ddtw, ddtb))
+    dx0, dx1, dxd0, dxd1 = torch.empty_like(x0), torch.empty_like(x0), xd0.new_empty(xd0.shape), xd0.new_empty(xd0.shape)
     check(lib().bem_ss2d_scan_bwd_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dy0), _p(dy1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(dx0), _p(dx1),
-                                      _p(dxd0), _p(dxd1), _p(dAlog), _p(dDs), _p(ddtw), _p(ddtb), B, C, L, R, bs[0], bs[1], _stream()),
+                                      _p(dxd0), _p(dxd1), _p(dAlog), _p(dDs), _p(ddtw), _p(ddtb), B, C, L, R, bs0, bs1, _stream()),
           "ss2d_scan_bwd")
     return dx0, dx1, dxd0, dxd1
 
@@ -1660,30 +1807,13 @@ def ss2d_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw,
 def ss2d_scan_n_bwd(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dAlog, dDs, ddtw, ddtb):
     """Backward of ss2d_scan_n: returns (dx0, dx1, dxd0, dxd1), dxd* (B,2,R+2N,L); parameter gradients accumulated into dAlog (4C, N),
     dDs (4C), ddtw (4,C,R), ddtb (4,C)."""
-    for n, t in (("x0", x0), ("x1", x1), ("dy0", dy0), ("dy1", dy1), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds), ("dAlog", dAlog),
-                 ("dDs", dDs), ("ddtw", ddtw), ("ddtb", ddtb)):
-        _chk(t, n)
-    B, C, L = x0.shape
-    R = dtw.shape[2]
-    if A.dim() != 2 or A.shape[0] != 4 * C:
-        raise ValueError(f"ss2d_scan_n_bwd: A {tuple(A.shape)} is not (4C, N)")
-    N = A.shape[1]
-    if not ss2d_scan_n_supported(N):
-        raise NotImplementedError(f"ss2d_scan_n_bwd: d_state {N} outside 1..16")
-    if x1.shape != x0.shape or dy0.shape != x0.shape or dy1.shape != x0.shape or xd0.shape != (B, 2, R + 2 * N, L) or xd1.shape != xd0.shape:
-        raise ValueError("ss2d_scan_n_bwd: activation shapes")
-    if dtw.shape != (4, C, R) or dtb.shape != (4, C) or Ds.numel() != 4 * C or dAlog.numel() != 4 * C * N or dDs.numel() != 4 * C \
-            or ddtw.numel() != 4 * C * R or ddtb.numel() != 4 * C:
-        raise ValueError("ss2d_scan_n_bwd: parameter shapes")
-    bs = _xd_bstrides("ss2d_scan_n_bwd", xd0, xd1, B, R + 2 * N, L)
-    dx0, dx1 = torch.empty_like(x0), torch.empty_like(x0)
-    dxd0 = torch.empty(B, 2, R + 2 * N, L, device=x0.device, dtype=x0.dtype)
-    dxd1 = torch.empty(B, 2, R + 2 * N, L, device=x0.device, dtype=x0.dtype)
-    nws = int(lib().bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N))
-    ws = torch.empty(max(nws, 1), device=x0.device, dtype=torch.float32)
+    B, C, L, R, N, bs0, bs1 = _scan_operands("ss2d_scan_n_bwd", True, (("x0", x0), ("x1", x1), ("dy0", dy0), ("dy1", dy1)), xd0, xd1,
+                                             dtw, dtb, A, Ds, (dAlog, dDs, ddtw, ddtb))
+    dx0, dx1, dxd0, dxd1 = torch.empty_like(x0), torch.empty_like(x0), xd0.new_empty(xd0.shape), xd0.new_empty(xd0.shape)
+    ws = torch.empty(max(int(lib().bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N)), 1), device=x0.device, dtype=torch.float32)
     check(lib().bem_ss2d_scan_n_bwd_f32(_p(x0), _p(x1), _p(xd0), _p(xd1), _p(dy0), _p(dy1), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(dx0), _p(dx1),
                                         _p(dxd0), _p(dxd1), _p(dAlog), _p(dDs), _p(ddtw), _p(ddtb), _p(ws), ws.numel(), B, C, L, R, N,
-                                        bs[0], bs[1], _stream()), "ss2d_scan_n_bwd")
+                                        bs0, bs1, _stream()), "ss2d_scan_n_bwd")
     return dx0, dx1, dxd0, dxd1
 
 
@@ -1705,187 +1835,3 @@ def adamw_step_(p, g, m, v, lr, betas, eps, weight_decay, step, max_norm=0.0, su
         raise ValueError("adamw_step: buffer sizes differ")
     check(lib().bem_adamw_step_f32(_p(p), _p(g), _p(m), _p(v), n, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                    int(step), float(max_norm), _p(sumsq), _p(norm_out), _p(hyper), _stream()), "adamw_step")
-
-
-# --------------------------------------------------------------------------- launch timing ----
-# bench.py asks for ONE op's launches to be bracketed by HIP events on the launch stream (torch's
-# current stream is the stream every wrapper launches on), together with that launch's algorithmic
-# bytes / flops.  Disabled (zero overhead beyond a None check) outside bench.py.
-_PROF = None
-# profile key -> (op wrapper it belongs to, roofline bound, kernel symbol reported to bench.py, predicate on the call)
-_KEYS = {
-    # the register-resident x6 GEMM for K <= 48 (level-0 in_proj / project_in / x_proj and the small Stage-I layers):
-    # every launch of the (vectorised, single-input or concat) instance, whatever M and L
-    "pw_x6_res<3,2,1>": ("pw_gemm", "hbm", "pw_x6_res_kernel<3, 2, 1, false, true>",
-                         lambda K, M, ln, L, mode: K <= 48 and L % 2 == 0 and mode != 1),
-    # the streaming x6 GEMM with two M-tiles per pass (project_out / out_proj / fuse 1x1 at K > 48 without LayerNorm):
-    # the kernel with the largest share of the step in profiles/r01_bench_kernel_stats.csv
-    "pw_x6_stream<2>": ("pw_gemm", "hbm", "pw_x6_stream_kernel<2, 2, false, true, false>",
-                        lambda K, M, ln, L, mode: K > 48 and not ln and M > 32 and L % 2 == 0 and mode != 1),
-    "pw_gemm": ("pw_gemm", "mfma", "pw_gemm* (all variants)", lambda K, M, ln, L, mode: True),
-    # the whole gdMlp branch in one kernel: x in, out out -- 8 bytes per element of x are its algorithmic bytes
-    # (HBM: 42 us at level 0) -- but its two GEMMs (2Hd x C and C x Hd per pixel) evaluated as six bf16 limb products are 242 GFLOP on the
-    # matrix cores (97 us at the dense bf16 peak): the matrix pipe is the roofline that bounds it.  flops = 6 x the f32 GEMM flops
-    # (what the x6 scheme must issue for the output pixels; halo and padding MFMAs are waste, not work).
-    "gdmlp_x6<3>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<3, 2, 2, false>", lambda C: 32 < C <= 48),
-    "gdmlp_x6<5>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<5, 3, 1, false>", lambda C: 64 < C <= 80),
-    "conv2d": ("conv2d", "mfma", "conv2d_kernel", None),
-    "dwconv3x3": ("dwconv3x3", "hbm", "dwconv3x3_kernel", None),
-    "ss2d_scan": ("ss2d_scan", "hbm", "ss2d_scan_kernel", None),
-    "transpose_planes": ("transpose_planes", "hbm", "transpose_planes_kernel", None),
-    # a decoder level's up + fuse as one kernel: f in, skip in, out out are its algorithmic bytes
-    "up_fuse": ("up_fuse", "hbm", "upfuse_x6_kernel<2>", None),
-    # training step (bench.py --config train)
-    "pw_wgrad": ("pw_wgrad_", "hbm", "wgrad_x6_kernel<2, 2> + wgrad_x6_reduce_kernel (1x1 weight gradients; wgrad_kernel<*> for L % 32 != 0)", None),
-    "conv_wgrad": ("conv_wgrad_", "mfma", "wgrad_kernel<*> (dense conv weight gradients)", None),
-    "ss2d_scan_bwd": ("ss2d_scan_bwd", "hbm", "ss2d_scan_bwd_kernel", None),
-    "dwact_bwd": ("dwact_bwd", "hbm", "dwact_bwd_kernel", None),
-    "ln_bwd": ("ln_bwd", "hbm", "ln_bwd_kernel", None),
-}
-
-
-def profile_start(key: str):
-    global _PROF
-    if key not in _KEYS:
-        raise ValueError(f"profile_start: unknown key {key}; choose from {sorted(_KEYS)}")
-    op, bound, symbol, pred = _KEYS[key]
-    _PROF = {"kernel": op, "symbol": symbol, "bound": bound, "pred": pred, "events": [], "bytes": 0.0, "flops": 0.0}
-
-
-def profile_stop():
-    global _PROF
-    p, _PROF = _PROF, None
-    if p is None:
-        return None
-    torch.cuda.synchronize()
-    ms = sum(s.elapsed_time(e) for s, e in p["events"])
-    return {"kernel": p["symbol"], "bound": p["bound"], "launches": len(p["events"]), "ms": ms,
-            "bytes": p["bytes"], "flops": p["flops"]}
-
-
-def _timed(name, nbytes, nflops):
-    """Decorator-free helper: returns (start_event or None); caller records the end with _timed_end."""
-    if _PROF is None or _PROF["kernel"] != name:
-        return None
-    s = torch.cuda.Event(enable_timing=True)
-    s.record()
-    _PROF["bytes"] += nbytes
-    _PROF["flops"] += nflops
-    return s
-
-
-def _timed_end(s):
-    if s is not None:
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        _PROF["events"].append((s, e))
-
-
-def _wrap_profiled():
-    """Wrap the four hot ops with event brackets + algorithmic byte/flop accounting."""
-    global pw_gemm, conv2d, dwconv3x3, ss2d_scan, transpose_planes
-    _pw, _cv, _dw, _ss, _tp = pw_gemm, conv2d, dwconv3x3, ss2d_scan, transpose_planes
-
-    def pw_gemm_p(x1, Wp, M, **kw):
-        if _PROF is None:
-            return _pw(x1, Wp, M, **kw)
-        B, C1 = x1.shape[0], x1.shape[1]
-        L = x1[0, 0].numel()
-        x2, mode = kw.get("x2"), kw.get("in_mode", 0)
-        K = C1 + (x2.shape[1] if mode == 2 else 0)
-        cin = C1 + (x2.shape[1] if x2 is not None else 0)
-        nb = 4.0 * B * L * (cin + M + (M if kw.get("res") is not None else 0)) + 4.0 * Wp.numel()
-        if _PROF["kernel"] == "pw_gemm" and not _PROF["pred"](K, M, kw.get("ln") is not None, L, mode):
-            return _pw(x1, Wp, M, **kw)
-        s = _timed("pw_gemm", nb, 2.0 * M * K * L * B)
-        out = _pw(x1, Wp, M, **kw)
-        _timed_end(s)
-        return out
-
-    def conv2d_p(x, w, bias=None, stride=1, pad=1, **kw):
-        if _PROF is None:
-            return _cv(x, w, bias, stride, pad, **kw)
-        B, _, H, W = x.shape
-        wn = w.w if isinstance(w, ConvWeight) else w
-        Co, Ci, KH, KW = wn.shape
-        Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-        nres = (kw.get("res1") is not None) + (kw.get("res2") is not None)
-        s = _timed("conv2d", 4.0 * B * (Ci * H * W + Co * Ho * Wo * (1 + nres)) + 4.0 * wn.numel(), 2.0 * B * Co * Ci * KH * KW * Ho * Wo)
-        out = _cv(x, w, bias, stride, pad, **kw)
-        _timed_end(s)
-        return out
-
-    def dwconv3x3_p(x, w, bias=None, mode=0):
-        if _PROF is None:
-            return _dw(x, w, bias, mode)
-        B, Cin, H, W = x.shape
-        Cout = Cin // 2 if mode == 2 else Cin
-        s = _timed("dwconv3x3", 4.0 * B * H * W * (Cin + Cout), 18.0 * B * Cin * H * W)
-        out = _dw(x, w, bias, mode)
-        _timed_end(s)
-        return out
-
-    def ss2d_scan_p(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
-        if _PROF is None:
-            return _ss(x0, x1, xd0, xd1, dtw, dtb, A, Ds)
-        s = _timed("ss2d_scan", 4.0 * (2 * x0.numel() + 2 * xd0.numel() + 2 * x0.numel()), 0.0)
-        out = _ss(x0, x1, xd0, xd1, dtw, dtb, A, Ds)
-        _timed_end(s)
-        return out
-
-    def transpose_planes_p(x):
-        if _PROF is None:
-            return _tp(x)
-        s = _timed("transpose_planes", 8.0 * x.numel(), 0.0)
-        out = _tp(x)
-        _timed_end(s)
-        return out
-
-    pw_gemm, conv2d, dwconv3x3, ss2d_scan, transpose_planes = pw_gemm_p, conv2d_p, dwconv3x3_p, ss2d_scan_p, transpose_planes_p
-
-    # backward ops: (algorithmic bytes, flops) of one launch from the call's arguments
-    def numel(t):
-        return 0 if t is None else t.numel()
-
-    def wrap(name, cost):
-        inner = globals()[name]
-
-        def wrapped(*a, **kw):
-            if _PROF is None or _PROF["kernel"] != name:
-                return inner(*a, **kw)
-            nb, nf = cost(*a, **kw)
-            s = _timed(name, nb, nf)
-            out = inner(*a, **kw)
-            _timed_end(s)
-            return out
-        wrapped.__doc__ = inner.__doc__
-        globals()[name] = wrapped
-
-    def c_pw_wgrad(dy, x1, dw, x2=None, dbias=None, blk_rows=0, perm=None, dy_bstride=0, M=None):
-        B, L = x1.shape[0], x1[0, 0].numel()
-        M = dy.shape[1] if M is None else M
-        K = x1.shape[1] + (0 if x2 is None else x2.shape[1])
-        return 4.0 * B * L * (M + K) + 4.0 * M * K, 2.0 * M * K * B * L
-
-    def c_conv_wgrad(dy, x, dw, dbias=None, stride=1, pad=1, cin_slice=None):
-        Cout, Cin, KH, KW = dw.shape
-        return 4.0 * (dy.numel() + x.shape[0] * Cin * x.shape[2] * x.shape[3]) + 4.0 * dw.numel(), 2.0 * dy.numel() * Cin * KH * KW
-
-    def c_scan_bwd(x0, x1, xd0, xd1, dy0, dy1, *a, **kw):
-        return 4.0 * (6 * x0.numel() + 4 * xd0.numel()), 0.0
-
-    def c_dwact(t, w, bias, dout, dw, dbias, mode):
-        return 4.0 * (2 * t.numel() + dout.numel()), 40.0 * t.numel()
-
-    def c_ln(x1, dn, gamma, beta, eps, dgamma, dbeta, x2=None, dres=None, want_n=True):
-        return 4.0 * x1.numel() * (3 + (x2 is not None) + (dres is not None) + bool(want_n)), 0.0
-
-    def c_up_fuse(f, skip, folded):
-        Co = skip.shape[1]
-        return 4.0 * (f.numel() + 2 * skip.numel() + folded.Wc.numel() + folded.Wf2.numel()), 2.0 * skip.numel() * (f.shape[1] + Co)
-
-    for nm, fn in (("up_fuse", c_up_fuse), ("pw_wgrad_", c_pw_wgrad), ("conv_wgrad_", c_conv_wgrad), ("ss2d_scan_bwd", c_scan_bwd), ("dwact_bwd", c_dwact), ("ln_bwd", c_ln)):
-        wrap(nm, fn)
-
-
-_wrap_profiled()

@@ -557,13 +557,27 @@ def test_pw_gemm_x6_accuracy(ops, cfg):
     assert abs(d.mean().item()) < 0.1 * e32, ("bias", d.mean().item(), e32)
 
 
-def test_transpose_plane_slice_and_strided_scan_inputs(ops):
+def test_transpose_plane_slice_and_strided_scan_inputs(ops, monkeypatch):
     """transpose of a channel slice (batch-strided source) and bem_ss2d_scan_strided: x_dbl given as channel slices of a
     wider buffer must give the same result as contiguous copies."""
     g = torch.Generator().manual_seed(77)
     x = torch.randn(3, 7, 5, 9, generator=g)
     t = ops.transpose_plane_slice(dev(x), 2, 4)
     assert torch.equal(t.cpu(), x[:, 2:6].transpose(2, 3).contiguous())
+    # transpose_planes_into: the planes land in channels [2, 5) of a wider destination, whose other channels stay as they were
+    xs, before = torch.randn(2, 3, 5, 7, generator=g), torch.randn(2, 6, 7, 5, generator=g)
+    dst = dev(before)
+    assert ops.transpose_planes_into(dev(xs), dst, 2) is dst
+    assert torch.equal(dst[:, 2:5].cpu(), xs.transpose(2, 3)) and torch.equal(dst[:, :2].cpu(), before[:, :2]) and torch.equal(dst[:, 5:].cpu(), before[:, 5:])
+    launched = []
+    with monkeypatch.context() as m:                     # a rejected call launches nothing
+        m.setattr(ops.lib(), "bem_transpose_planes_f32", lambda *a: launched.append(a) or 1)
+        for bad_dst, c0 in ((dst, 4), (dst, -1), (dev(torch.zeros(2, 6, 5, 7)), 2), (dev(torch.zeros(1, 6, 7, 5)), 2)):
+            with pytest.raises(ValueError):              # 4 + 3 > 6 channels; a negative offset; planes not transposed; another batch
+                ops.transpose_planes_into(dev(xs), bad_dst, c0)
+        with pytest.raises(ValueError):
+            ops.transpose_plane_slice(dev(x), 5, 3)      # channels [5, 8) of 7
+    assert launched == [] and torch.equal(dst[:, :2].cpu(), before[:, :2]) and torch.equal(dst[:, 5:].cpu(), before[:, 5:])
     B, C, H, W, R = 2, 8, 16, 16, 3
     L = H * W
     x0, x1 = torch.randn(B, C, L, generator=g), torch.randn(B, C, L, generator=g)
