@@ -107,7 +107,8 @@ __device__ __forceinline__ float dpp_from_next_lane(float v) {   // lane l <- la
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
-template <bool DPPHALO>
+// VW (grouped form): the weights are per-lane loads and pass through a VALU copy before the packed FMAs pair them up
+template <bool DPPHALO, bool VW = false>
 __device__ __forceinline__ void dw_block_fast(const float* __restrict__ plane, int H, int W, int y0, int x0,
                                               const float* __restrict__ w9, float (&acc)[RB][4]) {
     float4 c[RB + 2];
@@ -124,7 +125,7 @@ __device__ __forceinline__ void dw_block_fast(const float* __restrict__ plane, i
     }
     float wk[9];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) wk[i] = w9[i];
+    for (int i = 0; i < 9; ++i) wk[i] = VW ? valu_copy(w9[i]) : w9[i];
     const float mt = y0 > 0 ? 1.f : 0.f, mb = y0 + RB < H ? 1.f : 0.f;
     const float ml = x0 > 0 ? 1.f : 0.f, mr = x0 + 4 < W ? 1.f : 0.f;
 #pragma unroll
@@ -132,8 +133,12 @@ __device__ __forceinline__ void dw_block_fast(const float* __restrict__ plane, i
         float4 q = c[ry + 1];
         if (ry == -1) { q.x *= mt; q.y *= mt; q.z *= mt; q.w *= mt; }
         if (ry == RB) { q.x *= mb; q.y *= mb; q.z *= mb; q.w *= mb; }
-        const float v[6] = {(DPPHALO ? dpp_from_prev_lane(q.w) : hl[ry + 1] * ((ry == -1) ? mt : (ry == RB) ? mb : 1.f)) * ml, q.x, q.y, q.z, q.w,
-                            (DPPHALO ? dpp_from_next_lane(q.x) : hr[ry + 1] * ((ry == -1) ? mt : (ry == RB) ? mb : 1.f)) * mr};
+        float v[6] = {(DPPHALO ? dpp_from_prev_lane(q.w) : hl[ry + 1] * ((ry == -1) ? mt : (ry == RB) ? mb : 1.f)) * ml, q.x, q.y, q.z, q.w,
+                      (DPPHALO ? dpp_from_next_lane(q.x) : hr[ry + 1] * ((ry == -1) ? mt : (ry == RB) ? mb : 1.f)) * mr};
+        if (VW && DPPHALO) {            // the neighbouring lane may belong to another channel: its value is dropped, not multiplied by zero
+            v[0] = x0 > 0 ? v[0] : 0.f;
+            v[5] = x0 + 4 < W ? v[5] : 0.f;
+        }
 #pragma unroll
         for (int oy = 0; oy < RB; ++oy) {
             const int dy = ry - oy;
@@ -145,31 +150,47 @@ __device__ __forceinline__ void dw_block_fast(const float* __restrict__ plane, i
     }
 }
 
-template <int MODE, bool DPPHALO>
+//
+// GROUP (small planes, HB * W4 <= 16 threads: the 4x4 ... 16x16 maps of Stage I): a workgroup takes CG = 256 / (HB * W4) consecutive
+// channels (mode 2: gate pairs), thread i -> channel-in-group i / (HB * W4), then (row block, column quad) as in the one-plane form; grid
+// (1, ceil(Cout / CG), B).  A channel boundary is a row boundary, so ml / mr already stop the DPP halo shifts there.  No lane leaves: lanes
+// past the last channel (or past CG planes, where HB * W4 does not divide 256) work on a clamped channel and only their stores are masked,
+// so every DPP source lane is active.  Weights and bias are per-lane loads (the channel varies inside a wave); the arithmetic per output
+// is the same expression in the same order as in the one-plane form.
+template <int MODE, bool DPPHALO, bool GROUP>
 __global__ __launch_bounds__(256) void dwconv3x3_fast_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              int64_t w_bs, const float* __restrict__ bias, int64_t b_bs,
                                                              float* __restrict__ out, int Cout, int H, int W) {
     const int W4 = W >> 2, HB = H / RB;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= HB * W4) return;           // whole rows per wavefront: the lanes that leave are past the last row
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c = blockIdx.y;
+    bool live = true;
+    if (GROUP) {
+        const int per = HB * W4, cg = 256 / per, ci = (int)threadIdx.x / per;
+        i = (int)threadIdx.x - ci * per;
+        c = blockIdx.y * cg + ci;
+        live = ci < cg && c < Cout;
+        c = min(c, Cout - 1);
+    } else if (i >= HB * W4) return;    // whole rows per wavefront: the lanes that leave are past the last row
     const int yb = i / W4, y0 = yb * RB, x0 = (i - yb * W4) * 4;
-    const int c = blockIdx.y, b = blockIdx.z;
+    const int b = blockIdx.z;
     const int Cin = (MODE == 2) ? 2 * Cout : Cout;
     const int64_t HW = (int64_t)H * W;
     const float* wb = w + (int64_t)b * w_bs;
     // bias through an always-valid pointer and a multiplicative mask (no branch around the load)
     const float* bb = bias ? bias + (int64_t)b * b_bs : wb;
     const float bm = bias ? 1.f : 0.f;
-    const float b0 = bb[bias ? c : 0] * bm;
-    const float b1 = (MODE == 2) ? bb[bias ? c + Cout : 0] * bm : 0.f;
+    float b0 = bb[bias ? c : 0] * bm;
+    float b1 = (MODE == 2) ? bb[bias ? c + Cout : 0] * bm : 0.f;
+    if (GROUP) { b0 = valu_copy(b0); b1 = valu_copy(b1); }
     const float* pl = x + ((int64_t)b * Cin + c) * HW;
     float a0[RB][4], a1[RB][4];
 #pragma unroll
     for (int r = 0; r < RB; ++r)
 #pragma unroll
         for (int j = 0; j < 4; ++j) a0[r][j] = a1[r][j] = 0.f;
-    dw_block_fast<DPPHALO>(pl, H, W, y0, x0, wb + (int64_t)c * 9, a0);
-    if (MODE == 2) dw_block_fast<DPPHALO>(x + ((int64_t)b * Cin + c + Cout) * HW, H, W, y0, x0, wb + (int64_t)(c + Cout) * 9, a1);
+    dw_block_fast<DPPHALO, GROUP>(pl, H, W, y0, x0, wb + (int64_t)c * 9, a0);
+    if (MODE == 2) dw_block_fast<DPPHALO, GROUP>(x + ((int64_t)b * Cin + c + Cout) * HW, H, W, y0, x0, wb + (int64_t)(c + Cout) * 9, a1);
     float4 self[RB];
     if (MODE == 3) {
 #pragma unroll
@@ -187,7 +208,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fast_kernel(const float* __rest
             else if (MODE == 3) o[j] = sv[j] + fmaxf(v, 0.f);
             else o[j] = v;
         }
-        *reinterpret_cast<float4*>(out + ((int64_t)b * Cout + c) * HW + (int64_t)(y0 + r) * W + x0) = make_float4(o[0], o[1], o[2], o[3]);
+        if (!GROUP || live) *reinterpret_cast<float4*>(out + ((int64_t)b * Cout + c) * HW + (int64_t)(y0 + r) * W + x0) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
@@ -563,8 +584,18 @@ extern "C" int bem_dwconv3x3_f32(const float* x, const float* w, int64_t w_bstri
     // covers whole image rows (64 % (W / 4) == 0: every plane of a 256x256 image), else from two more clamped loads per row
     const bool fast = W % 4 == 0 && H % RB == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
     const bool dpp = fast && 64 % (W / 4) == 0;
-#define BEM_DW(MODE) do { if (dpp) dwconv3x3_fast_kernel<MODE, true><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); \
-                          else dwconv3x3_fast_kernel<MODE, false><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); } while (0)
+    // small planes (HB * W4 <= 16 threads: 16x16 and below, Stage I): 256 / (HB * W4) channels per workgroup instead of one plane on a few lanes
+    // of 256.  B = 64, per-sample weights (scripts/small_plane_micro.py; ~11 us is the launch floor of that measurement): level-2 gate conv (4x4,
+    // 640 pairs, 40 960 workgroups of one live lane -> 192 full ones) 52.2 -> 11.3 us, level 1 (8x8, 320 pairs) 28.2 -> 11.2 us, level 0 (16x16,
+    // 160 pairs) 16.7 -> 11.5 us.  Not beyond: at 32x32 (64 threads per plane, Stage II's level 2) a one-plane workgroup already runs a full
+    // wave with its weights in scalar registers, and four planes per workgroup with per-lane weight loads took 135 us against 104 us (640 pairs)
+    const int per = (H / RB) * (W / 4);
+    const bool group = fast && per <= 16;
+    if (group) grid = dim3(1, cdiv(Cout, 256 / per), B);
+#define BEM_DW(MODE) do { if (group && dpp) dwconv3x3_fast_kernel<MODE, true, true><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); \
+                          else if (group) dwconv3x3_fast_kernel<MODE, false, true><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); \
+                          else if (dpp) dwconv3x3_fast_kernel<MODE, true, false><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); \
+                          else dwconv3x3_fast_kernel<MODE, false, false><<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W); } while (0)
     if (!fast) dwconv3x3_kernel<<<grid, 256, 0, s>>>(x, w, w_bstride, bias, bias_bstride, out, Cout, H, W, mode);
     else if (mode == 0) BEM_DW(0);
     else if (mode == 1) BEM_DW(1);

@@ -21,7 +21,10 @@
 //   * D layout: column = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (acc_row, x6_common.h).
 //   * "resident" kernel: the wave's whole input tile (all K channels, already normalised and split) stays in
 //     registers while the wave walks over every M-tile, so x is read once and LayerNorm evaluated once;
-//     "stream" kernel (no LayerNorm, any K): x is streamed k-block by k-block, one block ahead of the MFMAs.
+//     "stream" kernel (any K; LayerNorm by two more sweeps over x): x is streamed k-block by k-block, ahead of the MFMAs.
+//   * "small" kernel (planes of at most 128 pixels, Stage I's 4x4 and 8x8 maps): the k-blocks of a pixel-wave are shared among the four
+//     (two) waves of the workgroup, each requests its slice of the weight stream up front, and the partial sums meet in LDS in a fixed
+//     order (pw_x6_small_kernel below).  The three forms above give each wave its own pixels, so on such a plane one wave works alone.
 #include "bem_common.h"
 #include "x6_common.h"
 #include <algorithm>
@@ -593,6 +596,163 @@ for (int m = 0; m < MTW; ++m)
     x6_epilogue<MTW, NSUB, VEC>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
 }
 
+// ------------------------------------------------------------------------------------------------
+// small planes: L <= 128 (the 4x4 ... 8x8 maps of Stage I), any K, optional LayerNorm.  grid (1, MT, B): one M-tile per workgroup.
+// In the forms above a plane this small leaves one wave of four with pixels, and that wave walks K with one k-block of weights in flight:
+// the time follows the k-block count at one memory latency each (~1.1 us), whatever the flops.  Here the plane's PW = 4 / KS pixel-waves
+// each share their k-blocks among KS waves: wave w has pixel group w / KS and k-slice w % KS, slice s covers k-blocks
+// [s q, min(KB, (s + 1) q)), q = ceil(KB / KS) (a slice may be empty and then adds zeros), and a wave requests its slice BEM_X6_SMALL_D
+// k-blocks at a time, weights and x together, before the first MFMA of the chunk: one exposed latency per chunk instead of one per k-block
+// (K <= 192 at KS = 4: one in all).  Each wave sums its own hi + lo; slices 1 .. KS - 1 park their accumulators in LDS, one barrier, slice 0
+// adds them in the fixed order 1, 2, 3 (bit-reproducible from launch to launch) and runs the common epilogue.  No wave leaves before the
+// last barrier.  LayerNorm (32-pixel waves and q <= BEM_X6_SMALL_D only, so that a slice is one chunk held in registers): the slices' partial
+// sums, then partial centred squares, meet in LDS (two more barriers, summed in slice order by every wave alike).
+// ------------------------------------------------------------------------------------------------
+// k-blocks per chunk: with the accumulators of one M-tile this stays inside the 256 registers of two workgroups per CU
+constexpr int BEM_X6_SMALL_D = 3;
+template <int KS, int NSUB, bool SUM, bool VEC, bool LN>
+__global__ __launch_bounds__(256, 2) void pw_x6_small_kernel(PwX k) {
+    constexpr int PW = 4 / KS, D = BEM_X6_SMALL_D, MAXK = 16 * 4 * D;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kh = lane >> 5, n = lane & 31;
+    const int pg = wave / KS, ks = wave % KS;
+    const int b = blockIdx.z, mt0 = blockIdx.y;
+    __shared__ __attribute__((aligned(16))) float s_bias[BEM_X6_MAXM];
+    __shared__ float s_ln[LN ? 2 * MAXK : 2];
+    __shared__ float s_stat[LN ? 2 * 4 * NSUB * 64 : 2];
+    __shared__ float s_part[PW * (KS - 1) * NSUB * 16 * 64];
+    stage_bias(k, b, s_bias);
+    if (LN) {
+        for (int i = threadIdx.x; i < k.KB * 16; i += 256) {     // zero scale / shift on the padded channels
+            s_ln[i] = i < k.K ? k.ln_w[i] : 0.f;
+            s_ln[MAXK + i] = i < k.K ? k.ln_b[i] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int p = pg * (32 * NSUB) + NSUB * n;
+    bool keep[NSUB];
+#pragma unroll
+    for (int t = 0; t < NSUB; ++t) keep[t] = p + t < k.L;
+    const int pc = VEC ? (keep[0] ? p : 0) : p;
+    const int q = (k.KB + KS - 1) / KS, kb0 = ks * q, kb1 = min(k.KB, kb0 + q);
+    const u32x4* wbase = k.Wp + (int64_t)b * k.w_bstride + (int64_t)mt0 * k.KB * 3 * 64 + lane;
+    f32x16 acc[1][NSUB], alo[NSUB];
+#pragma unroll
+    for (int t = 0; t < NSUB; ++t) acc[0][t] = alo[t] = zero16();
+    int kc = kb0;
+#pragma nounroll
+    do {                                // once even for an empty slice: clamped loads, nothing accumulated, every barrier reached
+        u32x4 wv[D][3];
+        float xv[D][8][NSUB];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {   // k-blocks past the slice re-read a valid block: weights masked to zero, x not used
+            load_w3_masked(wbase + (int64_t)min(kc + d, k.KB - 1) * 3 * 64, kc + d < kb1 ? 0xffffffffu : 0u, wv[d]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ldx<NSUB, SUM, VEC>(k, b, 16 * (kc + d) + 8 * kh + e, pc, keep, xv[d][e]);   // channels >= K come back as zeros
+        }
+        float mean[NSUB], rstd[NSUB];
+        if (LN) {
+            const float inv = 1.f / (float)k.K;
+            float* st = s_stat + lane;
+#pragma unroll
+            for (int t = 0; t < NSUB; ++t) {
+                float sm = 0.f;
+#pragma unroll
+                for (int d = 0; d < D; ++d)
+                    if (kc + d < kb1) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) sm += xv[d][e][t];
+                    }
+                sm += __shfl_xor(sm, 32, 64);
+                st[((pg * KS + ks) * NSUB + t) * 64] = sm;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < NSUB; ++t) {
+                float sm = 0.f;
+#pragma unroll
+                for (int j = 0; j < KS; ++j) sm += valu_copy(st[((pg * KS + j) * NSUB + t) * 64]);
+                mean[t] = sm * inv;
+                float sq = 0.f;
+#pragma unroll
+                for (int d = 0; d < D; ++d)
+                    if (kc + d < kb1) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const float dv = (16 * (kc + d) + 8 * kh + e < k.K) ? xv[d][e][t] - mean[t] : 0.f;     // padded channels do not count
+                            sq = fmaf(dv, dv, sq);
+                        }
+                    }
+                sq += __shfl_xor(sq, 32, 64);
+                st[(4 * NSUB + (pg * KS + ks) * NSUB + t) * 64] = sq;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < NSUB; ++t) {
+                float sq = 0.f;
+#pragma unroll
+                for (int j = 0; j < KS; ++j) sq += valu_copy(st[(4 * NSUB + (pg * KS + j) * NSUB + t) * 64]);
+                rstd[t] = 1.f / sqrtf(sq * inv + k.ln_eps);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (kc + d < kb1) {
+                u32x4 xl[NSUB][3];
+#pragma unroll
+                for (int t = 0; t < NSUB; ++t) {
+                    float v[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        v[e] = xv[d][e][t];
+                        const int ch = min(16 * (kc + d) + 8 * kh + e, MAXK - 1);
+                        if (LN) v[e] = (v[e] - mean[t]) * rstd[t] * valu_copy(s_ln[ch]) + valu_copy(s_ln[MAXK + ch]);
+                    }
+                    split8(v, xl[t][0], xl[t][1], xl[t][2]);
+                }
+#pragma unroll
+                for (int t = 0; t < NSUB; ++t) mac6(wv[d], xl[t], acc[0][t], alo[t]);
+            }
+        }
+        kc += D;
+    } while (kc < kb1);
+#pragma unroll
+    for (int t = 0; t < NSUB; ++t) acc[0][t] += alo[t];
+    float4 bq[1][4];
+    x6_load_bias<1>(k, b, mt0, kh, bq);
+    float* sp = s_part + (int64_t)(pg * (KS - 1) * NSUB) * 1024 + lane;
+    if (ks != 0) {
+#pragma unroll
+        for (int t = 0; t < NSUB; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sp[(((ks - 1) * NSUB + t) * 16 + r) * 64] = acc[0][t][r];
+    }
+    __syncthreads();
+    if (ks != 0) return;
+#pragma unroll
+    for (int j = 1; j < KS; ++j)        // fixed order 1, 2, 3
+#pragma unroll
+        for (int t = 0; t < NSUB; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[0][t][r] += valu_copy(sp[(((j - 1) * NSUB + t) * 16 + r) * 64]);
+    x6_epilogue<1, NSUB, VEC>(k, b, mt0, p, keep, kh, s_bias, bq, acc);
+}
+
+template <int KS, int NSUB>
+void launch_small(const PwX& k, dim3 grid, hipStream_t s, bool sum, bool vec, bool ln) {
+#define BEM_X6_SMALL(SUM, VEC)                                                              \
+    do {                                                                                    \
+        if constexpr (NSUB == 1) {                                                          \
+            if (ln) { pw_x6_small_kernel<KS, NSUB, SUM, VEC, true><<<grid, 256, 0, s>>>(k); break; }   \
+        }                                                                                   \
+        pw_x6_small_kernel<KS, NSUB, SUM, VEC, false><<<grid, 256, 0, s>>>(k);              \
+    } while (0)
+    if (NSUB == 2 && vec && !sum) BEM_X6_SMALL(false, NSUB == 2);       // 32-pixel waves: the scalar-pixel forms, as in BEM_X6_RES(10, 1, *)
+    else if (NSUB == 2 && vec) BEM_X6_SMALL(true, NSUB == 2);
+    else if (!sum) BEM_X6_SMALL(false, false);
+    else BEM_X6_SMALL(true, false);
+#undef BEM_X6_SMALL
+}
+
 }  // namespace
 
 extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
@@ -625,8 +785,9 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
 #define BEM_X6_RES(KBM, NSUB, MTW)                                                                       \
     do {                                                                                                 \
         dim3 grid(cdiv(a->L, 128 * NSUB), 1, a->B);                                                      \
-        /* few pixels (Stage I: 4x4 ... 16x16 maps), many output rows: slice M over grid.y so that the weight stream of  \
-           one sample is pulled by several workgroups (each repeats the cheap LayerNorm of the same pixels) */            \
+        /* few pixels (Stage I's 16x16 maps; 8x8 with LayerNorm, 4x4 and 8x8 at K <= 48: the rest of the 4x4 and 8x8 maps    \
+           takes pw_x6_small_kernel), many output rows: slice M over grid.y so that the weight stream of one sample is     \
+           pulled by several workgroups (each repeats the cheap LayerNorm of the same pixels) */                           \
         const int64_t wv = (int64_t)a->B * cdiv(a->L, 32 * NSUB);                                        \
         const int groups = cdiv(k.MT, MTW);                                                              \
         const int ny = wv >= 2048 ? 1 : (int)std::min<int64_t>(groups, cdiv64(2048, wv));                \
@@ -638,6 +799,25 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
         else pw_x6_res_kernel<KBM, NSUB, MTW, true, false><<<grid, 256, 0, s>>>(k);                            \
         return bem_check_launch("pw_x6_res");                                                            \
     } while (0)
+    // small planes (grid.x would be 1 below and the plane fills at most two pixel-waves): K split over the waves of the workgroup
+    // (pw_x6_small_kernel), 4-way for L <= 64, 2-way for L <= 128, 32-pixel waves for L <= 32.  Kept on the forms below, measured with
+    // scripts/small_plane_micro.py (B = 64, per-sample weights; parent -> small form):
+    //   * K <= 48 (KB <= 3): the one working wave of the resident form already has every k-block in flight at once;
+    //   * LayerNorm on 64-pixel waves: level-1 project_in (K 80 -> M 640, 8x8) 27.8 -> 33.1 us -- 20 workgroups per sample that each repeat
+    //     the statistics behind two more barriers at 240 registers; in_proj / out_proj there (3 M-tiles) 13.1 -> 12.8 / 14.4 -> 13.7 us, inside
+    //     the launch floor of the measurement.  With 32-pixel waves (4x4: K 160 -> 1280 48.7 -> 36.6 us, out_proj 22.8 -> 13.8 us) it is taken
+    //     where a wave's slice is one chunk (K <= 192).
+    // Without LayerNorm: level-2 project_out (K 640) 52.1 -> 21.5 us, level-1 (K 320) 26.7 -> 13.4 us, the 4x4 up-sampling GEMM 25.3 -> 13.6 us.
+    if (a->L <= 128 && k.KB > 3) {
+        const int ks = a->L <= 64 ? 4 : 2;
+        if (!ln || (a->L <= 32 && cdiv(k.KB, ks) <= BEM_X6_SMALL_D)) {
+            const dim3 grid(1, k.MT, a->B);
+            if (a->L <= 32) launch_small<4, 1>(k, grid, s, sum, vec, ln);
+            else if (ks == 4) launch_small<4, 2>(k, grid, s, sum, vec, ln);
+            else launch_small<2, 2>(k, grid, s, sum, vec, ln);
+            return bem_check_launch("pw_x6_small");
+        }
+    }
     // one M-tile at a time where a wave holds two sub-tiles: the accumulator pairs double the register cost of an M-tile
     if (k.KB <= 3) BEM_X6_RES(3, 2, 1);
     if (ln && k.KB <= 5) BEM_X6_RES(5, 2, 1);
