@@ -30,6 +30,14 @@ static inline int bem_check_launch(const char* what) {
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Give every XCD a contiguous run of work items (the pixel
+// tiles of a plane in the x6 kernels, the channel rows of one (orientation, image) in the scans), so that what one L2 collects
+// (and later writes back) is adjacent in memory and shared operands are fetched into one L2 only.
+__device__ __forceinline__ int xcd_tile(int x, int nx) {
+    const int per = nx >> 3, rem = nx & 7, xcd = x & 7, idx = x >> 3;
+    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
+}
+
 // Hardware transcendental forms (v_exp_f32 / v_log_f32, ~1 ulp): the scan evaluates three of them per
 // element and direction, and the libm-accurate versions made that kernel instruction-bound.
 __device__ __forceinline__ float bem_fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }

@@ -8,7 +8,6 @@
 // 6 steps), waves exchange their aggregates through LDS and a running carry links successive chunks.
 // The reverse directions use the mirrored lane / wave / element order of the same code.
 #include "scan_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -221,33 +220,6 @@ __global__ __launch_bounds__(NT) void selective_scan_bwd_kernel(
 // Fused SS2D scan (N = 1): grid (C, B, 2 orientations).  Each workgroup owns one (b, c) sequence of
 // one orientation and runs its forward direction (k = o) and reverse direction (k = o + 2).
 // ------------------------------------------------------------------------------------------------
-template <int E>
-__device__ __forceinline__ void ss2d_coeffs(const float* __restrict__ xd /* (R+2, L) of one direction */,
-                                            const float* __restrict__ wdt /* (R) */, float dtb, float Ak,
-                                            const float (&x)[E], int64_t t0, int L, int R, bool vec,
-                                            float (&a)[E], float (&b)[E], float (&cv)[E]) {
-    float dt[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) dt[e] = 0.f;
-    for (int r = 0; r < R; ++r) {
-        float v[E];
-        load_row<E>(xd + (int64_t)r * L, t0, L, vec, v);
-        const float w = wdt[r];
-#pragma unroll
-        for (int e = 0; e < E; ++e) dt[e] = fmaf(w, v[e], dt[e]);
-    }
-    float Bv[E];
-    load_row<E>(xd + (int64_t)R * L, t0, L, vec, Bv);
-    load_row<E>(xd + (int64_t)(R + 1) * L, t0, L, vec, cv);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const bool ok = t0 + e < L;
-        const float dl = bem_softplus(dt[e] + dtb);
-        a[e] = ok ? bem_fexp(dl * Ak) : 1.f;
-        b[e] = ok ? dl * Bv[e] * x[e] : 0.f;
-    }
-}
-
 template <int NT, int E>
 __global__ __launch_bounds__(NT) void ss2d_scan_kernel(
     const float* __restrict__ x0, const float* __restrict__ x1, const float* __restrict__ xd0,
@@ -255,21 +227,13 @@ __global__ __launch_bounds__(NT) void ss2d_scan_kernel(
     const float* __restrict__ A, const float* __restrict__ Ds, float* __restrict__ y0,
     float* __restrict__ y1, int Bn, int C, int L, int R, int64_t xbs0, int64_t xbs1) {
     __shared__ float agg[2 * (NT / BEM_WAVE)];
-    // XCD-aware order: workgroup ids are dealt round-robin to the 8 XCDs, so give each XCD a contiguous range of
-    // (orientation, image, channel) work items -- the C channel rows of one (o, b) share its 2*(R+2) x_dbl planes in that XCD's L2.
-    const int total = gridDim.x, lin = blockIdx.x;
-    const int per = total / 8, rem = total % 8, xcd = lin % 8, idx = lin / 8;
-    const int wi = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    const int c = wi % C, b = (wi / C) % Bn, o = wi / (C * Bn);
+    // XCD-aware order: the C channel rows of one (o, b) share its 2*(R+2) x_dbl planes in one XCD's L2
+    const Ss2dItem it = ss2d_item(xcd_tile(blockIdx.x, gridDim.x), C, Bn);
+    const int c = it.u, b = it.b, o = it.o;
     const float* xr = (o ? x1 : x0) + ((int64_t)b * C + c) * L;
     const float* xd = (o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0);
     float* yr = (o ? y1 : y0) + ((int64_t)b * C + c) * L;
-    const int kf = o, kr = o + 2;
-    const float* wf = dtw + ((int64_t)kf * C + c) * R;
-    const float* wr = dtw + ((int64_t)kr * C + c) * R;
-    const float bf = dtb[kf * C + c], br = dtb[kr * C + c];
-    const float Af = A[kf * C + c], Ar = A[kr * C + c];
-    const float Df = Ds[kf * C + c], Dr = Ds[kr * C + c];
+    const Ss2dDir pf = ss2d_dir(dtw, dtb, A, Ds, o, C, c, R), pr = ss2d_dir(dtw, dtb, A, Ds, o + 2, C, c, R);
     const bool vec = (L % 4 == 0);
     constexpr int CH = NT * E;
     const int nchunks = (L + CH - 1) / CH;
@@ -281,10 +245,10 @@ __global__ __launch_bounds__(NT) void ss2d_scan_kernel(
         const int64_t t0 = (int64_t)j * CH + (int64_t)threadIdx.x * E;
         float x[E], a[E], bb[E], cv[E], h[E];
         load_row<E>(xr, t0, L, vec, x);
-        ss2d_coeffs<E>(xd, wf, bf, Af, x, t0, L, R, vec, a, bb, cv);
+        ss2d_coeffs<E>(xd, pf.wdt, pf.dtb, *pf.A, x, t0, L, R, vec, a, bb, cv);
         block_scan_affine<NT, E, false>(a, bb, h, carry, agg);
 #pragma unroll
-        for (int e = 0; e < E; ++e) yacc[e] = fmaf(cv[e], h[e], Df * x[e]);
+        for (int e = 0; e < E; ++e) yacc[e] = fmaf(cv[e], h[e], pf.D * x[e]);
         if (!single) store_row<E>(yr, t0, L, vec, yacc);
     }
     // reverse direction, chunks descending; adds onto the forward result
@@ -293,11 +257,11 @@ __global__ __launch_bounds__(NT) void ss2d_scan_kernel(
         const int64_t t0 = (int64_t)j * CH + (int64_t)threadIdx.x * E;
         float x[E], a[E], bb[E], cv[E], h[E], yv[E];
         load_row<E>(xr, t0, L, vec, x);
-        ss2d_coeffs<E>(xd + (int64_t)(R + 2) * L, wr, br, Ar, x, t0, L, R, vec, a, bb, cv);
+        ss2d_coeffs<E>(xd + (int64_t)(R + 2) * L, pr.wdt, pr.dtb, *pr.A, x, t0, L, R, vec, a, bb, cv);
         block_scan_affine<NT, E, true>(a, bb, h, carry, agg);
         if (!single) load_row<E>(yr, t0, L, vec, yacc);   // this thread's own earlier stores
 #pragma unroll
-        for (int e = 0; e < E; ++e) yv[e] = yacc[e] + fmaf(cv[e], h[e], Dr * x[e]);
+        for (int e = 0; e < E; ++e) yv[e] = yacc[e] + fmaf(cv[e], h[e], pr.D * x[e]);
         store_row<E>(yr, t0, L, vec, yv);
     }
 }
@@ -315,23 +279,18 @@ __device__ __forceinline__ void ss2d_coeffs_full(const float* __restrict__ xd, c
 #pragma unroll
     for (int r = 0; r < (RT ? RT : R); ++r) {
         const float w = wdt[r];
+        float v[E];
+        load4<E>(xd + (int64_t)r * L + t0, v);
 #pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(xd + (int64_t)r * L + t0 + i);
-            a[i] = fmaf(w, q.x, a[i]); a[i + 1] = fmaf(w, q.y, a[i + 1]);
-            a[i + 2] = fmaf(w, q.z, a[i + 2]); a[i + 3] = fmaf(w, q.w, a[i + 3]);
-        }
+        for (int e = 0; e < E; ++e) a[e] = fmaf(w, v[e], a[e]);
     }
+    float bv[E];
+    load4<E>(xd + (int64_t)R * L + t0, bv);
 #pragma unroll
-    for (int i = 0; i < E; i += 4) {
-        const float4 q = *reinterpret_cast<const float4*>(xd + (int64_t)R * L + t0 + i);
-        const float bv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float dl = bem_softplus(a[i + j]);
-            a[i + j] = bem_fexp(dl * Ak);
-            b[i + j] = dl * bv[j] * x[i + j];
-        }
+    for (int e = 0; e < E; ++e) {
+        const float dl = bem_softplus(a[e]);
+        a[e] = bem_fexp(dl * Ak);
+        b[e] = dl * bv[e] * x[e];
     }
 }
 
@@ -344,61 +303,44 @@ __global__ __launch_bounds__(NT) void ss2d_scan_full_kernel(
     __shared__ float agg[2 * (NT / BEM_WAVE)];
     constexpr int L = NT * E;
     const int R = RT ? RT : Rr;
-    const int total = gridDim.x, lin = blockIdx.x;      // XCD-aware order, as in ss2d_scan_kernel
-    const int per = total / 8, rem = total % 8, xcd = lin % 8, idx = lin / 8;
-    const int wi = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    const int c = wi % C, b = (wi / C) % Bn, o = wi / (C * Bn);
+    const Ss2dItem it = ss2d_item(xcd_tile(blockIdx.x, gridDim.x), C, Bn);      // XCD-aware order, as in ss2d_scan_kernel
+    const int c = it.u, b = it.b, o = it.o;
     const float* xr = (o ? x1 : x0) + ((int64_t)b * C + c) * L;
     const float* xd = (o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0);
     float* yr = (o ? y1 : y0) + ((int64_t)b * C + c) * L;
-    const int kf = o, kr = o + 2;
     const int t0 = threadIdx.x * E;
     float x[E], y[E];
-#pragma unroll
-    for (int i = 0; i < E; i += 4) {
-        const float4 q = *reinterpret_cast<const float4*>(xr + t0 + i);
-        x[i] = q.x; x[i + 1] = q.y; x[i + 2] = q.z; x[i + 3] = q.w;
-    }
+    load4<E>(xr + t0, x);
     {
         float a[E], bb[E];
-        ss2d_coeffs_full<E, RT>(xd, dtw + ((int64_t)kf * C + c) * R, dtb[kf * C + c], A[kf * C + c], x, t0, L, R, a, bb);
+        const Ss2dDir p = ss2d_dir(dtw, dtb, A, Ds, o, C, c, R);
+        ss2d_coeffs_full<E, RT>(xd, p.wdt, p.dtb, *p.A, x, t0, L, R, a, bb);
         float carry = 0.f;
         float hh = block_scan_enter<NT, E, false>(a, bb, carry, agg);
-        const float Df = Ds[kf * C + c];
-        const float* cp = xd + (int64_t)(R + 1) * L + t0;
+        float cv[E];
+        load4<E>(xd + (int64_t)(R + 1) * L + t0, cv);
 #pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(cp + i);
-            const float cv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                hh = a[i + j] * hh + bb[i + j];
-                y[i + j] = fmaf(cv[j], hh, Df * x[i + j]);
-            }
+        for (int e = 0; e < E; ++e) {
+            hh = a[e] * hh + bb[e];
+            y[e] = fmaf(cv[e], hh, p.D * x[e]);
         }
     }
     {
         float a[E], bb[E];
         const float* xdr = xd + (int64_t)(R + 2) * L;
-        ss2d_coeffs_full<E, RT>(xdr, dtw + ((int64_t)kr * C + c) * R, dtb[kr * C + c], A[kr * C + c], x, t0, L, R, a, bb);
+        const Ss2dDir p = ss2d_dir(dtw, dtb, A, Ds, o + 2, C, c, R);
+        ss2d_coeffs_full<E, RT>(xdr, p.wdt, p.dtb, *p.A, x, t0, L, R, a, bb);
         float carry = 0.f;
         float hh = block_scan_enter<NT, E, true>(a, bb, carry, agg);
-        const float Dr = Ds[kr * C + c];
-        const float* cp = xdr + (int64_t)(R + 1) * L + t0;
+        float cv[E];
+        load4<E>(xdr + (int64_t)(R + 1) * L + t0, cv);
 #pragma unroll
-        for (int i = E - 4; i >= 0; i -= 4) {
-            const float4 q = *reinterpret_cast<const float4*>(cp + i);
-            const float cv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 3; j >= 0; --j) {
-                hh = a[i + j] * hh + bb[i + j];
-                y[i + j] += fmaf(cv[j], hh, Dr * x[i + j]);
-            }
+        for (int e = E - 1; e >= 0; --e) {
+            hh = a[e] * hh + bb[e];
+            y[e] += fmaf(cv[e], hh, p.D * x[e]);
         }
     }
-#pragma unroll
-    for (int i = 0; i < E; i += 4)
-        *reinterpret_cast<float4*>(yr + t0 + i) = make_float4(y[i], y[i + 1], y[i + 2], y[i + 3]);
+    store4<E>(yr + t0, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -425,14 +367,11 @@ __global__ __launch_bounds__(NT, MINW) void ss2d_scan_rows_kernel(
     __shared__ float agg[NSLOT][2 * NW];
     extern __shared__ float plane_sm[];                  // TR: CB planes, Himg rows of (Wimg + 1) floats
     const int G = (C + CB - 1) / CB;
-    const int total = gridDim.x, lin = blockIdx.x;      // XCD-aware order: the channel groups of one (o, b) share an L2
-    const int per = total / 8, rem = total % 8, xcd = lin % 8, idx = lin / 8;
-    const int wi = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    const int g = wi % G, b = (wi / G) % Bn, o = ORI < 0 ? wi / (G * Bn) : ORI;
+    const Ss2dItem it = ss2d_item(xcd_tile(blockIdx.x, gridDim.x), G, Bn);      // XCD-aware order: the channel groups of one (o, b) share an L2
+    const int g = it.u, b = it.b, o = ORI < 0 ? it.o : ORI;
     const float* xb = (o ? x1 : x0) + (int64_t)b * C * L;
     const float* xdb = (o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0);
     float* yb = (o ? y1 : y0) + (int64_t)b * C * L;
-    const int lane = threadIdx.x & (BEM_WAVE - 1), wave = threadIdx.x / BEM_WAVE;
     const bool via_lds = TR && o == 1;                   // uniform per workgroup (a compile-time constant when ORI >= 0)
     // LDS plane layout: element (row, col) at (row >> 2) * (4 pitch + 1) + (row & 3) * pitch + col, pitch = W + 1.  A lane reads
     // 4 consecutive rows of one column (rows 4n .. 4n + 3): the extra +1 per group of 4 rows makes the lane stride
@@ -492,14 +431,14 @@ __global__ __launch_bounds__(NT, MINW) void ss2d_scan_rows_kernel(
                     const float4 xq = *reinterpret_cast<const float4*>(xb + (int64_t)c * L + pos);
                     xv[0] = xq.x; xv[1] = xq.y; xv[2] = xq.z; xv[3] = xq.w;
                 }
-                const float* wd = dtw + ((int64_t)kd * C + c) * R;
-                const float bias = dtb[kd * C + c], Ak = A[kd * C + c], Dk = Ds[kd * C + c];
+                const Ss2dDir p = ss2d_dir(dtw, dtb, A, Ds, kd, C, c, R);
+                const float Ak = *p.A;
                 float a[4], bb[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = bias;
+                for (int e = 0; e < 4; ++e) a[e] = p.dtb;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const float w = wd[r];
+                    const float w = p.wdt[r];
                     a[0] = fmaf(w, dq[r].x, a[0]); a[1] = fmaf(w, dq[r].y, a[1]);
                     a[2] = fmaf(w, dq[r].z, a[2]); a[3] = fmaf(w, dq[r].w, a[3]);
                 }
@@ -507,11 +446,8 @@ __global__ __launch_bounds__(NT, MINW) void ss2d_scan_rows_kernel(
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int e = dir ? 3 - i : i;
-                    // softplus and exp(dt * A) share the base-2 logarithm: lg = log2(1 + e^z) (z log2 e beyond the threshold),
-                    // dt = lg ln 2, exp(dt A) = 2^(A lg)
-                    const float z = a[e];
-                    const float lg = z <= 20.f ? __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(z * 1.44269504088896340736f)) : z * 1.44269504088896340736f;
-                    const float dl = lg * 0.69314718055994530942f;
+                    const float lg = softplus_log2(a[e]);      // softplus and exp(dt A) share the base-2 logarithm
+                    const float dl = lg * BEM_LN2;
                     a[e] = __builtin_amdgcn_exp2f(lg * Ak);
                     bb[e] = dl * Bv[e] * xv[e];
                     S = fmaf(a[e], S, bb[e]);
@@ -520,35 +456,9 @@ __global__ __launch_bounds__(NT, MINW) void ss2d_scan_rows_kernel(
                 float Pe, Se;
                 if (dir) wave_scan_affine<true>(P, S, Pe, Se);
                 else wave_scan_affine<false>(P, S, Pe, Se);
-                float hw = carry[ch];
-                if (NW > 1) {
-                    float* ag = agg[slot];
-                    if (lane == (dir ? 0 : BEM_WAVE - 1)) { ag[2 * wave] = P; ag[2 * wave + 1] = S; }
-                    __syncthreads();
-                    // compose the NW wave aggregates in scan order with a 16-lane DPP row scan (lane l < NW holds wave l of
-                    // that order) instead of every thread walking all NW pairs: ~30 instructions instead of 5 NW
-                    static_assert(NW <= 16, "the cross-wave scan uses one DPP row");
-                    const int sl = min(lane, NW - 1), src = dir ? NW - 1 - sl : sl;      // always a valid pair; lanes >= NW hold the identity
-                    const float Pl = ag[2 * src], Sl = ag[2 * src + 1];
-                    float Pw = lane < NW ? Pl : 1.f, Sw = lane < NW ? Sl : 0.f;
-#define BEM_ROW_STEP(DPP) asm volatile("s_nop 1\n\tv_fmac_f32_dpp %0, %0, %1 " DPP "\n\tv_mul_f32_dpp %1, %1, %1 " DPP : "+v"(Sw), "+v"(Pw))
-                    BEM_ROW_STEP("row_shr:1 row_mask:0xf bank_mask:0xf"); BEM_ROW_STEP("row_shr:2 row_mask:0xf bank_mask:0xf");
-                    if (NW > 4) BEM_ROW_STEP("row_shr:4 row_mask:0xf bank_mask:0xf");
-                    if (NW > 8) BEM_ROW_STEP("row_shr:8 row_mask:0xf bank_mask:0xf");
-#undef BEM_ROW_STEP
-                    const int rw = dir ? NW - 1 - wave : wave;                 // this wave's place in scan order (uniform)
-                    const float Pt = lane_bcast(Pw, NW - 1), St = lane_bcast(Sw, NW - 1);
-                    const float Px = lane_bcast(Pw, rw > 0 ? rw - 1 : 0), Sx = lane_bcast(Sw, rw > 0 ? rw - 1 : 0);
-                    const float c0 = carry[ch];
-                    hw = rw > 0 ? fmaf(Px, c0, Sx) : c0;
-                    carry[ch] = fmaf(Pt, c0, St);
-                    // the slot is rewritten NSLOT channel steps later; the barriers of the steps in between order that
-                    // write after every read above
-                    slot = (slot + 1 == NSLOT) ? 0 : slot + 1;
-                } else {
-                    const float Pt = lane_bcast(P, dir ? 0 : BEM_WAVE - 1), St = lane_bcast(S, dir ? 0 : BEM_WAVE - 1);
-                    carry[ch] = fmaf(Pt, hw, St);
-                }
+                // the slot is rewritten NSLOT channel steps later; the barriers of the steps in between order that write after every read
+                const float hw = dir ? cross_wave_affine<NW, true>(P, S, agg[slot], carry[ch]) : cross_wave_affine<NW, false>(P, S, agg[slot], carry[ch]);
+                slot = (slot + 1 == NSLOT) ? 0 : slot + 1;
                 float hh = fmaf(Pe, hw, Se);
                 if (LATE_C) {
                     const float4 cq = *reinterpret_cast<const float4*>(xd + (int64_t)(R + 1) * L + pos);
@@ -559,7 +469,7 @@ __global__ __launch_bounds__(NT, MINW) void ss2d_scan_rows_kernel(
                 for (int i = 0; i < 4; ++i) {
                     const int e = dir ? 3 - i : i;
                     hh = fmaf(a[e], hh, bb[e]);
-                    yv[e] = fmaf(Cv[e], hh, Dk * xv[e]);
+                    yv[e] = fmaf(Cv[e], hh, p.D * xv[e]);
                 }
                 if (ORI == 1 && TR) {
                     // the orientation-1-only launch of the row-major form keeps nothing in registers across the two directions
@@ -631,78 +541,46 @@ __global__ __launch_bounds__(NT) void ss2d_scan_chunks_kernel(
     __shared__ float agg[2 * (NT / BEM_WAVE)];
     constexpr int CH = NT * E;
     const int R = RT ? RT : Rr;
-    const int total = gridDim.x, lin = blockIdx.x;      // XCD-aware order, as in ss2d_scan_kernel
-    const int per = total / 8, rem = total % 8, xcd = lin % 8, idx = lin / 8;
-    const int wi = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    const int c = wi % C, b = (wi / C) % Bn, o = wi / (C * Bn);
+    const Ss2dItem it = ss2d_item(xcd_tile(blockIdx.x, gridDim.x), C, Bn);      // XCD-aware order, as in ss2d_scan_kernel
+    const int c = it.u, b = it.b, o = it.o;
     const float* xr = (o ? x1 : x0) + ((int64_t)b * C + c) * L;
     const float* xd = (o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0);
     const float* xdr = xd + (int64_t)(R + 2) * L;
     float* yr = (o ? y1 : y0) + ((int64_t)b * C + c) * L;
-    const int kf = o, kr = o + 2;
-    const float* wf = dtw + ((int64_t)kf * C + c) * R;
-    const float* wr = dtw + ((int64_t)kr * C + c) * R;
-    const float bf = dtb[kf * C + c], br = dtb[kr * C + c];
-    const float Af = A[kf * C + c], Ar = A[kr * C + c];
-    const float Df = Ds[kf * C + c], Dr = Ds[kr * C + c];
+    const Ss2dDir pf = ss2d_dir(dtw, dtb, A, Ds, o, C, c, R), pr = ss2d_dir(dtw, dtb, A, Ds, o + 2, C, c, R);
     const int nchunks = L / CH;
     float carry = 0.f;
     for (int j = 0; j < nchunks; ++j) {
         const int t0 = j * CH + threadIdx.x * E;
         float x[E], a[E], bb[E], y[E];
-#pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(xr + t0 + i);
-            x[i] = q.x; x[i + 1] = q.y; x[i + 2] = q.z; x[i + 3] = q.w;
-        }
-        float4 cq[E / 4];
-#pragma unroll
-        for (int i = 0; i < E; i += 4) cq[i / 4] = *reinterpret_cast<const float4*>(xd + (int64_t)(R + 1) * L + t0 + i);
-        ss2d_coeffs_full<E, RT>(xd, wf, bf, Af, x, t0, L, R, a, bb);
+        load4<E>(xr + t0, x);
+        float cv[E];
+        load4<E>(xd + (int64_t)(R + 1) * L + t0, cv);
+        ss2d_coeffs_full<E, RT>(xd, pf.wdt, pf.dtb, *pf.A, x, t0, L, R, a, bb);
         float hh = block_scan_enter<NT, E, false>(a, bb, carry, agg);
 #pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            const float cv[4] = {cq[i / 4].x, cq[i / 4].y, cq[i / 4].z, cq[i / 4].w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                hh = a[i + k] * hh + bb[i + k];
-                y[i + k] = fmaf(cv[k], hh, Df * x[i + k]);
-            }
+        for (int e = 0; e < E; ++e) {
+            hh = a[e] * hh + bb[e];
+            y[e] = fmaf(cv[e], hh, pf.D * x[e]);
         }
-#pragma unroll
-        for (int i = 0; i < E; i += 4)
-            *reinterpret_cast<float4*>(yr + t0 + i) = make_float4(y[i], y[i + 1], y[i + 2], y[i + 3]);
+        store4<E>(yr + t0, y);
     }
     carry = 0.f;
     for (int j = nchunks - 1; j >= 0; --j) {
         const int t0 = j * CH + threadIdx.x * E;
         float x[E], a[E], bb[E], y[E];
-#pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(xr + t0 + i);
-            x[i] = q.x; x[i + 1] = q.y; x[i + 2] = q.z; x[i + 3] = q.w;
-        }
-        float4 cq[E / 4], yq[E / 4];
-#pragma unroll
-        for (int i = 0; i < E; i += 4) {
-            cq[i / 4] = *reinterpret_cast<const float4*>(xdr + (int64_t)(R + 1) * L + t0 + i);
-            yq[i / 4] = *reinterpret_cast<const float4*>(yr + t0 + i);       // this thread's own earlier stores
-        }
-        ss2d_coeffs_full<E, RT>(xdr, wr, br, Ar, x, t0, L, R, a, bb);
+        load4<E>(xr + t0, x);
+        float cv[E];
+        load4<E>(xdr + (int64_t)(R + 1) * L + t0, cv);
+        load4<E>(yr + t0, y);                                // this thread's own earlier stores
+        ss2d_coeffs_full<E, RT>(xdr, pr.wdt, pr.dtb, *pr.A, x, t0, L, R, a, bb);
         float hh = block_scan_enter<NT, E, true>(a, bb, carry, agg);
 #pragma unroll
-        for (int i = E - 4; i >= 0; i -= 4) {
-            const float cv[4] = {cq[i / 4].x, cq[i / 4].y, cq[i / 4].z, cq[i / 4].w};
-            const float yv[4] = {yq[i / 4].x, yq[i / 4].y, yq[i / 4].z, yq[i / 4].w};
-#pragma unroll
-            for (int k = 3; k >= 0; --k) {
-                hh = a[i + k] * hh + bb[i + k];
-                y[i + k] = yv[k] + fmaf(cv[k], hh, Dr * x[i + k]);
-            }
+        for (int e = E - 1; e >= 0; --e) {
+            hh = a[e] * hh + bb[e];
+            y[e] += fmaf(cv[e], hh, pr.D * x[e]);
         }
-#pragma unroll
-        for (int i = 0; i < E; i += 4)
-            *reinterpret_cast<float4*>(yr + t0 + i) = make_float4(y[i], y[i + 1], y[i + 2], y[i + 3]);
+        store4<E>(yr + t0, y);
     }
 }
 
@@ -786,21 +664,21 @@ extern "C" int bem_selective_scan_fwd_in16(const void* u, const void* delta, con
 extern "C" int bem_ss2d_scan_strided_f32(const float* x0, const float* x1, const float* xd0, const float* xd1,
                                          const float* dtw, const float* dtb, const float* A, const float* Ds, float* y0,
                                          float* y1, int B, int C, int L, int R, int64_t xd0_bstride, int64_t xd1_bstride, void* stream) {
-    const int64_t xbs0 = xd0_bstride ? xd0_bstride : (int64_t)2 * (R + 2) * L, xbs1 = xd1_bstride ? xd1_bstride : (int64_t)2 * (R + 2) * L;
-    BEM_REQUIRE(xbs0 >= (int64_t)2 * (R + 2) * L && xbs1 >= (int64_t)2 * (R + 2) * L && (L % 4 != 0 || (xbs0 % 4 == 0 && xbs1 % 4 == 0)), "ss2d_scan: x_dbl batch strides");
-    BEM_REQUIRE(x0 && x1 && xd0 && xd1 && dtw && dtb && A && Ds && y0 && y1, "ss2d_scan: null tensor");
-    BEM_REQUIRE(B >= 0 && C > 0 && L >= 0 && R >= 1 && (int64_t)B * C * 2 < (1ll << 31), "ss2d_scan: bad shape B=%d C=%d L=%d R=%d", B, C, L, R);
+    Ss2dArgs a{};
+    a.x0 = x0; a.x1 = x1; a.xd0 = xd0; a.xd1 = xd1; a.dtw = dtw; a.dtb = dtb; a.A = A; a.Ds = Ds;
+    a.y0 = y0; a.y1 = y1;
+    a.B = B; a.C = C; a.L = L; a.R = R; a.s = (hipStream_t)stream;
+    // unaligned tensors are served (by the general kernel): alignment only selects the kernel below
+    if (const int rc = ss2d_operands_ok("ss2d_scan", a, false, false, INT_MAX, C, R + 2, xd0_bstride, xd1_bstride)) return rc;
     if (B == 0 || L == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
     const int grid = C * B * 2;
-#define BEM_SS2D(NT, E) ss2d_scan_kernel<NT, E><<<grid, NT, 0, s>>>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, xbs0, xbs1)
-#define BEM_SS2D_FULL_R(NT, E, RT) ss2d_scan_full_kernel<NT, E, RT><<<grid, NT, 0, s>>>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, R, xbs0, xbs1)
-#define BEM_SS2D_FULL(NT, E) BEM_SS2D_FULL_R(NT, E, 0)      // runtime dt_rank: unrolling its plane loads measured slower (register pressure)
-#define BEM_SS2D_CHUNKS(RT) ss2d_scan_chunks_kernel<256, 8, RT><<<grid, 256, 0, s>>>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, xbs0, xbs1)
+#define BEM_SS2D(NT, E) ss2d_scan_kernel<NT, E><<<grid, NT, 0, a.s>>>(SS2D_FWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1)
+#define BEM_SS2D_FULL(NT, E) ss2d_scan_full_kernel<NT, E, 0><<<grid, NT, 0, a.s>>>(SS2D_FWD_OPERANDS(a), B, C, R, a.xbs0, a.xbs1)   // runtime dt_rank: unrolling its plane loads measured slower (register pressure)
+#define BEM_SS2D_CHUNKS(RT) ss2d_scan_chunks_kernel<256, 8, RT><<<grid, 256, 0, a.s>>>(SS2D_FWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1)
     const bool al = (((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)xd0 | (uintptr_t)xd1 | (uintptr_t)y0 | (uintptr_t)y1) & 15) == 0;
     // channel-blocked whole-row forms for the plane sizes and dt_ranks of a 256x256 image (n_feat 40: C = 40 / 80 / 160)
-#define BEM_SS2D_ROWS(NT, T, CB, RT, MW) do { ss2d_scan_rows_kernel<NT, T, CB, RT, MW, false><<<((C + CB - 1) / CB) * B * 2, NT, 0, s>>>( \
-        x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, xbs0, xbs1, 0); return bem_check_launch("ss2d_scan"); } while (0)
+#define BEM_SS2D_ROWS(NT, T, CB, RT, MW) do { ss2d_scan_rows_kernel<NT, T, CB, RT, MW, false><<<((C + CB - 1) / CB) * B * 2, NT, 0, a.s>>>( \
+        SS2D_FWD_OPERANDS(a), B, C, a.xbs0, a.xbs1, 0); return bem_check_launch("ss2d_scan"); } while (0)
     // the tilings that won the round-1 / round-2 sweeps (the other 14 instantiations went with their A/B switch in round 3)
     if (al) {
         if (L == 1024 && R == 10) BEM_SS2D_ROWS(256, 1, 4, 10, 5);
@@ -821,7 +699,6 @@ extern "C" int bem_ss2d_scan_strided_f32(const float* x0, const float* x1, const
     else BEM_SS2D(256, 8);
 #undef BEM_SS2D
 #undef BEM_SS2D_FULL
-#undef BEM_SS2D_FULL_R
 #undef BEM_SS2D_CHUNKS
     return bem_check_launch("ss2d_scan");
 }
@@ -886,40 +763,30 @@ extern "C" int bem_ss2d_scan_rm_supported(int H, int W, int R) {
 // the workgroup's own output plane instead of 16 registers, and neither variant needs scratch at the 64-register budget
 // (the combined L = 16384 kernel spilled 44 bytes per lane: 1.6x its output bytes in HBM writes).
 template <int NT, int T, int CB, int RT, int MW, int ORI>
-static int launch_rows_tr(const float* x, const float* xd0, const float* xd1, const float* dtw, const float* dtb, const float* A,
-                          const float* Ds, float* y0, float* y1, int B, int C, int H, int W, int64_t xbs0, int64_t xbs1, hipStream_t s) {
+static int launch_rows_tr(const Ss2dArgs& a, int H, int W) {
     const size_t lds = ORI == 0 ? 0 : (size_t)CB * (H / 4) * (4 * (W + 1) + 1) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ss2d_scan_rows_kernel<NT, T, CB, RT, MW, true, ORI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        attr_set = true;
-    }
-    const int groups = ((C + CB - 1) / CB) * B;
-    ss2d_scan_rows_kernel<NT, T, CB, RT, MW, true, ORI><<<ORI < 0 ? 2 * groups : groups, NT, lds, s>>>(x, x, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C,
-                                                                                                        xbs0, xbs1, H);
+    set_max_dynamic_lds<&ss2d_scan_rows_kernel<NT, T, CB, RT, MW, true, ORI>>(72 * 1024);
+    const int groups = ((a.C + CB - 1) / CB) * a.B;
+    ss2d_scan_rows_kernel<NT, T, CB, RT, MW, true, ORI><<<ORI < 0 ? 2 * groups : groups, NT, lds, a.s>>>(SS2D_FWD_OPERANDS(a), a.B, a.C, a.xbs0, a.xbs1, H);
     return bem_check_launch("ss2d_scan_rm");
 }
 
 extern "C" int bem_ss2d_scan_rm_f32(const float* x, const float* xd0, const float* xd1, const float* dtw, const float* dtb,
                                     const float* A, const float* Ds, float* y0, float* y1, int B, int C, int H, int W, int R,
                                     int64_t xd0_bstride, int64_t xd1_bstride, void* stream) {
-    BEM_REQUIRE(x && xd0 && xd1 && dtw && dtb && A && Ds && y0 && y1, "ss2d_scan_rm: null tensor");
-    BEM_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && R >= 1 && (int64_t)B * C * 2 < (1ll << 31), "ss2d_scan_rm: bad shape");
+    BEM_REQUIRE(H > 0 && W > 0, "ss2d_scan_rm: bad shape");
     BEM_REQUIRE(bem_ss2d_scan_rm_supported(H, W, R), "ss2d_scan_rm: unsupported plane %dx%d / dt_rank %d", H, W, R);
-    const int L = H * W;
-    const int64_t xbs0 = xd0_bstride ? xd0_bstride : (int64_t)2 * (R + 2) * L, xbs1 = xd1_bstride ? xd1_bstride : (int64_t)2 * (R + 2) * L;
-    BEM_REQUIRE(xbs0 >= (int64_t)2 * (R + 2) * L && xbs1 >= (int64_t)2 * (R + 2) * L && xbs0 % 4 == 0 && xbs1 % 4 == 0, "ss2d_scan_rm: x_dbl batch strides");
-    BEM_REQUIRE((((uintptr_t)x | (uintptr_t)xd0 | (uintptr_t)xd1 | (uintptr_t)y0 | (uintptr_t)y1) & 15) == 0, "ss2d_scan_rm: 16-byte alignment");
+    Ss2dArgs a{};
+    a.x0 = x; a.x1 = x; a.xd0 = xd0; a.xd1 = xd1; a.dtw = dtw; a.dtb = dtb; a.A = A; a.Ds = Ds;
+    a.y0 = y0; a.y1 = y1;
+    a.B = B; a.C = C; a.L = H * W; a.R = R; a.s = (hipStream_t)stream;
+    if (const int rc = ss2d_operands_ok("ss2d_scan_rm", a, false, true, INT_MAX, C, R + 2, xd0_bstride, xd1_bstride)) return rc;
     if (B == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-#define BEM_TR(NT, T, CB, RT, MW, ORI) launch_rows_tr<NT, T, CB, RT, MW, ORI>(x, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, H, W, xbs0, xbs1, s)
-    if (L == 16384) {
+    if (a.L == 16384) {
         // two single-orientation launches: 2 x 172 us, no scratch; the combined kernel needs both orientations' state at once and spilled (372 us)
-        const int rc = BEM_TR(1024, 4, 1, 3, 8, 0);
-        return rc ? rc : BEM_TR(1024, 4, 1, 3, 8, 1);
+        const int rc = launch_rows_tr<1024, 4, 1, 3, 8, 0>(a, H, W);
+        return rc ? rc : launch_rows_tr<1024, 4, 1, 3, 8, 1>(a, H, W);
     }
-    if (L == 4096) return BEM_TR(512, 2, 2, 5, 6, -1);       // combined: 143 us against 152 us for the best split
-    return BEM_TR(256, 1, 4, 10, 5, -1);
-#undef BEM_TR
+    if (a.L == 4096) return launch_rows_tr<512, 2, 2, 5, 6, -1>(a, H, W);       // combined: 143 us against 152 us for the best split
+    return launch_rows_tr<256, 1, 4, 10, 5, -1>(a, H, W);
 }

@@ -23,13 +23,15 @@ constexpr int SB_MAXCH = 128;
 
 template <int NT, int E, bool REV>
 __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const float* __restrict__ dyr, const float* __restrict__ xd,
-                                             float* __restrict__ dxd, float* __restrict__ dxr, const float* __restrict__ wdt, float dtb,
-                                             float Ak, float Dk, int L, int R, bool first, float* agg, float* red, float* cs, float* nb,
-                                             float* accw, float* dAlog_p, float* dDs_p, float* ddtb_p, float* ddtw_p) {
+                                             float* __restrict__ dxd, float* __restrict__ dxr, const Ss2dDir p, int L, int R, bool first,
+                                             float* agg, float* red, float* cs, float* nb, float* accw, float* __restrict__ dAlog,
+                                             float* __restrict__ dDs, float* __restrict__ ddtb, float* __restrict__ ddtw) {
     constexpr int CH = NT * E, NW = NT / BEM_WAVE;
     const int nchunks = (L + CH - 1) / CH;
     const bool vec = (L % 4 == 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* wdt = p.wdt;
+    const float Ak = *p.A;
     // ---- pass 1: state entering every chunk, in scan order ----
     float carry = 0.f;
     for (int jj = 0; jj < nchunks; ++jj) {
@@ -38,28 +40,8 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
         if (threadIdx.x == 0) cs[j] = carry;
         float x[E], a[E], bb[E], cv[E], h[E];
         load_row<E>(xr, t0, L, vec, x);
-        float dts[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) dts[e] = 0.f;
-        for (int r = 0; r < R; ++r) {
-            float v[E];
-            load_row<E>(xd + (int64_t)r * L, t0, L, vec, v);
-            const float w = wdt[r];
-#pragma unroll
-            for (int e = 0; e < E; ++e) dts[e] = fmaf(w, v[e], dts[e]);
-        }
-        float Bv[E];
-        load_row<E>(xd + (int64_t)R * L, t0, L, vec, Bv);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const bool ok = t0 + e < L;
-            const float dl = bem_softplus(dts[e] + dtb);
-            a[e] = ok ? bem_fexp(dl * Ak) : 1.f;
-            bb[e] = ok ? dl * Bv[e] * x[e] : 0.f;
-            cv[e] = 0.f;
-        }
+        ss2d_coeffs<E>(xd, wdt, p.dtb, Ak, x, t0, L, R, vec, a, bb, cv);
         block_scan_affine<NT, E, REV>(a, bb, h, carry, agg);
-        (void)cv;
     }
     if (threadIdx.x < 16) accw[threadIdx.x] = 0.f;
     if (threadIdx.x == 0) nb[NW + 1] = 1.f;          // a of the first element (scan order) of the chunk processed before: none yet
@@ -69,27 +51,10 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
     for (int jj = nchunks - 1; jj >= 0; --jj) {
         const int j = REV ? nchunks - 1 - jj : jj;
         const int64_t t0 = (int64_t)j * CH + (int64_t)threadIdx.x * E;
-        float x[E], dy[E], dts[E], dl[E], a[E], bb[E], Bv[E], Cv[E], h[E], ar[E], br[E], dh[E], dz[E];
+        float x[E], dy[E], z[E], dl[E], a[E], bb[E], Bv[E], Cv[E], h[E], ar[E], br[E], dh[E], dz[E];
         load_row<E>(xr, t0, L, vec, x);
         load_row<E>(dyr, t0, L, vec, dy);
-#pragma unroll
-        for (int e = 0; e < E; ++e) dts[e] = 0.f;
-        for (int r = 0; r < R; ++r) {
-            float v[E];
-            load_row<E>(xd + (int64_t)r * L, t0, L, vec, v);
-            const float w = wdt[r];
-#pragma unroll
-            for (int e = 0; e < E; ++e) dts[e] = fmaf(w, v[e], dts[e]);
-        }
-        load_row<E>(xd + (int64_t)R * L, t0, L, vec, Bv);
-        load_row<E>(xd + (int64_t)(R + 1) * L, t0, L, vec, Cv);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const bool ok = t0 + e < L;
-            dl[e] = bem_softplus(dts[e] + dtb);
-            a[e] = ok ? bem_fexp(dl[e] * Ak) : 1.f;
-            bb[e] = ok ? dl[e] * Bv[e] * x[e] : 0.f;
-        }
+        ss2d_coeffs<E>(xd, wdt, p.dtb, Ak, x, t0, L, R, vec, a, bb, Bv, Cv, dl, z);
         float cf = cs[j];
         block_scan_affine<NT, E, REV>(a, bb, h, cf, agg);
         // a of the successor (scan order) of each element
@@ -121,10 +86,9 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
             const bool ok = t0 + e < L;
             const float hm = h[e] - bb[e];
             const float dhd = dh[e] * dl[e];
-            dxv[e] = fmaf(dhd, Bv[e], Dk * dy[e]);
+            dxv[e] = fmaf(dhd, Bv[e], p.D * dy[e]);
             const float ddl = dh[e] * fmaf(Bv[e], x[e], Ak * hm);
-            const float z = dts[e] + dtb;
-            const float sg = z <= 20.f ? 1.f / (1.f + bem_fexp(-z)) : 1.f;
+            const float sg = z[e] <= 20.f ? 1.f / (1.f + bem_fexp(-z[e])) : 1.f;
             dz[e] = ok ? ddl * sg : 0.f;
             dBv[e] = dhd * x[e];
             dCv[e] = dy[e] * h[e];
@@ -151,8 +115,7 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
                 s = fmaf(dz[e], v[e], s);
                 if (t0 + e < L) atomicAdd(dxd + (int64_t)r * L + t0 + e, dz[e] * w);
             }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, BEM_WAVE);
+            s = wave_sum(s);
             if (lane == 0) atomicAdd(&accw[r], s);
         }
 #pragma unroll
@@ -167,11 +130,11 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
     accB = block_reduce_sum<NT>(accB, red);
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(dAlog_p, accA * Ak);
-        atomicAdd(dDs_p, accD);
-        atomicAdd(ddtb_p, accB);
+        atomicAdd(dAlog + p.kc, accA * Ak);
+        atomicAdd(dDs + p.kc, accD);
+        atomicAdd(ddtb + p.kc, accB);
     }
-    if (threadIdx.x < R) atomicAdd(ddtw_p + threadIdx.x, accw[threadIdx.x]);
+    if (threadIdx.x < R) atomicAdd(ddtw + (int64_t)p.kc * R + threadIdx.x, accw[threadIdx.x]);
     __syncthreads();
 }
 
@@ -188,23 +151,17 @@ __global__ __launch_bounds__(NT) void ss2d_scan_bwd_kernel(
     __shared__ float cs[SB_MAXCH];
     __shared__ float nb[NW + 2];
     __shared__ float accw[16];
-    const int total = gridDim.x, lin = blockIdx.x;
-    const int per = total / 8, rem = total % 8, xcd = lin % 8, idx = lin / 8;
-    const int wi = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    const int c = wi % C, b = (wi / C) % Bn, o = wi / (C * Bn);
+    const Ss2dItem it = ss2d_item(xcd_tile(blockIdx.x, gridDim.x), C, Bn);
+    const int c = it.u, b = it.b, o = it.o;
     const int64_t row = ((int64_t)b * C + c) * L;
     const float* xr = (o ? x1 : x0) + row;
     const float* dyr = (o ? dy1 : dy0) + row;
     float* dxr = (o ? dx1 : dx0) + row;
     const float* xd = o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0;
     float* dxd = (o ? dxd1 : dxd0) + (int64_t)b * 2 * (R + 2) * L;
-    const int kf = o, kr = o + 2;
-    ss2d_dir_bwd<NT, E, false>(xr, dyr, xd, dxd, dxr, dtw + ((int64_t)kf * C + c) * R, dtb[kf * C + c], A[kf * C + c], Ds[kf * C + c], L, R,
-                               true, agg, red, cs, nb, accw, dAlog + kf * C + c, dDs + kf * C + c, ddtb + kf * C + c,
-                               ddtw + ((int64_t)kf * C + c) * R);
-    ss2d_dir_bwd<NT, E, true>(xr, dyr, xd + (int64_t)(R + 2) * L, dxd + (int64_t)(R + 2) * L, dxr, dtw + ((int64_t)kr * C + c) * R,
-                              dtb[kr * C + c], A[kr * C + c], Ds[kr * C + c], L, R, false, agg, red, cs, nb, accw, dAlog + kr * C + c,
-                              dDs + kr * C + c, ddtb + kr * C + c, ddtw + ((int64_t)kr * C + c) * R);
+    ss2d_dir_bwd<NT, E, false>(xr, dyr, xd, dxd, dxr, ss2d_dir(dtw, dtb, A, Ds, o, C, c, R), L, R, true, agg, red, cs, nb, accw, dAlog, dDs, ddtb, ddtw);
+    ss2d_dir_bwd<NT, E, true>(xr, dyr, xd + (int64_t)(R + 2) * L, dxd + (int64_t)(R + 2) * L, dxr, ss2d_dir(dtw, dtb, A, Ds, o + 2, C, c, R), L, R, false,
+                              agg, red, cs, nb, accw, dAlog, dDs, ddtb, ddtw);
 }
 
 
@@ -226,13 +183,12 @@ __global__ __launch_bounds__(64) void ss2d_scan_bwd_small_kernel(
     __shared__ float accw[16];
     __shared__ float dacc[2 * 18 * 256];
     const int G = (C + CBS - 1) / CBS;
-    const int wi = blockIdx.x;
-    const int g = wi % G, b = (wi / G) % Bn, o = wi / (G * Bn);
+    const Ss2dItem it = ss2d_item(blockIdx.x, G, Bn);
+    const int g = it.u, b = it.b, o = it.o;
     const int nacc = 2 * (R + 2) * L;
     for (int i = threadIdx.x; i < nacc; i += 64) dacc[i] = 0.f;
     __syncthreads();
     const float* xd = o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0;
-    const int kf = o, kr = o + 2;
     for (int ch = 0; ch < CBS; ++ch) {
         const int c = g * CBS + ch;
         if (c >= C) break;                                                   // uniform
@@ -240,12 +196,9 @@ __global__ __launch_bounds__(64) void ss2d_scan_bwd_small_kernel(
         const float* xr = (o ? x1 : x0) + row;
         const float* dyr = (o ? dy1 : dy0) + row;
         float* dxr = (o ? dx1 : dx0) + row;
-        ss2d_dir_bwd<64, 4, false>(xr, dyr, xd, dacc, dxr, dtw + ((int64_t)kf * C + c) * R, dtb[kf * C + c], A[kf * C + c], Ds[kf * C + c], L, R,
-                                   true, agg, red, cs, nb, accw, dAlog + kf * C + c, dDs + kf * C + c, ddtb + kf * C + c,
-                                   ddtw + ((int64_t)kf * C + c) * R);
-        ss2d_dir_bwd<64, 4, true>(xr, dyr, xd + (int64_t)(R + 2) * L, dacc + (R + 2) * L, dxr, dtw + ((int64_t)kr * C + c) * R,
-                                  dtb[kr * C + c], A[kr * C + c], Ds[kr * C + c], L, R, false, agg, red, cs, nb, accw, dAlog + kr * C + c,
-                                  dDs + kr * C + c, ddtb + kr * C + c, ddtw + ((int64_t)kr * C + c) * R);
+        ss2d_dir_bwd<64, 4, false>(xr, dyr, xd, dacc, dxr, ss2d_dir(dtw, dtb, A, Ds, o, C, c, R), L, R, true, agg, red, cs, nb, accw, dAlog, dDs, ddtb, ddtw);
+        ss2d_dir_bwd<64, 4, true>(xr, dyr, xd + (int64_t)(R + 2) * L, dacc + (R + 2) * L, dxr, ss2d_dir(dtw, dtb, A, Ds, o + 2, C, c, R), L, R, false,
+                                  agg, red, cs, nb, accw, dAlog, dDs, ddtb, ddtw);
     }
     __syncthreads();
     float* dxd = (o ? dxd1 : dxd0) + (int64_t)b * 2 * (R + 2) * L;
@@ -263,6 +216,8 @@ __global__ __launch_bounds__(64) void ss2d_scan_bwd_small_kernel(
 //                                  dh_t = C_t dy_t + g_{t+1}: its per-thread map needs only the thread's own a's, so the DPP
 //                                  wavefront scan + one LDS barrier per (tile, channel) is all the communication there is.
 // ------------------------------------------------------------------------------------------------------------------------
+// This kernel keeps its own work-item decode, parameter reads, shared-logarithm lines and wave sums: with the scan_common.h helpers its
+// launches in the Stage-II training step measured 0.7 us (0.2 %) slower, outside the parent's run-to-run spread (profiles/scan_layout_bench.txt).
 template <int NT, int T, int CB, int R>
 __global__ __launch_bounds__(NT) void ss2d_scan_bwd_rows_kernel(
     const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dy0, const float* dy1,
@@ -490,19 +445,12 @@ __global__ __launch_bounds__(NT) void ss2d_scan_bwd_rows_kernel(
 }
 
 template <int NT, int T, int CB, int R>
-static int launch_bwd_rows(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dy0, const float* dy1, const float* dtw,
-                           const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0, float* dxd1, float* dAlog, float* dDs,
-                           float* ddtw, float* ddtb, int B, int C, int64_t xbs0, int64_t xbs1, hipStream_t s) {
-    const int G = (C + CB - 1) / CB;
+static int launch_bwd_rows(const Ss2dArgs& a) {
+    const int G = (a.C + CB - 1) / CB;
     constexpr size_t lds = sizeof(float) * CB * T * NT;
     static_assert(lds + sizeof(float) * (NT * 4 + 64 + (NT / 64) * CB * (3 + R)) <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    if (!attr_set && lds > 48 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ss2d_scan_bwd_rows_kernel<NT, T, CB, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    ss2d_scan_bwd_rows_kernel<NT, T, CB, R><<<G * B * 2, NT, lds, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs,
-                                                                      ddtw, ddtb, B, C, xbs0, xbs1);
+    if (lds > 48 * 1024) set_max_dynamic_lds<&ss2d_scan_bwd_rows_kernel<NT, T, CB, R>>((int)lds);
+    ss2d_scan_bwd_rows_kernel<NT, T, CB, R><<<G * a.B * 2, NT, lds, a.s>>>(SS2D_BWD_OPERANDS(a), a.B, a.C, a.xbs0, a.xbs1);
     return bem_check_launch("ss2d_scan_bwd(rows)");
 }
 
@@ -515,43 +463,38 @@ extern "C" int bem_ss2d_scan_bwd_f32(const float* x0, const float* x1, const flo
                                      const float* dtw, const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0,
                                      float* dxd1, float* dAlog, float* dDs, float* ddtw, float* ddtb, int B, int C, int L, int R,
                                      int64_t xd0_bstride, int64_t xd1_bstride, void* stream) {
-    BEM_REQUIRE(x0 && x1 && xd0 && xd1 && dy0 && dy1 && dtw && dtb && A && Ds && dx0 && dx1 && dxd0 && dxd1 && dAlog && dDs && ddtw && ddtb,
-                "ss2d_scan_bwd: null tensor");
-    BEM_REQUIRE(B >= 0 && C > 0 && L >= 0 && R >= 1 && R <= 16 && (int64_t)B * C * 2 < (1ll << 31), "ss2d_scan_bwd: bad shape B=%d C=%d L=%d R=%d", B, C, L, R);
-    const int64_t xbs0 = xd0_bstride ? xd0_bstride : (int64_t)2 * (R + 2) * L, xbs1 = xd1_bstride ? xd1_bstride : (int64_t)2 * (R + 2) * L;
-    BEM_REQUIRE(xbs0 >= (int64_t)2 * (R + 2) * L && xbs1 >= (int64_t)2 * (R + 2) * L, "ss2d_scan_bwd: x_dbl batch strides");
+    Ss2dArgs a{};
+    a.x0 = x0; a.x1 = x1; a.xd0 = xd0; a.xd1 = xd1; a.dtw = dtw; a.dtb = dtb; a.A = A; a.Ds = Ds;
+    a.dy0 = dy0; a.dy1 = dy1; a.dx0 = dx0; a.dx1 = dx1; a.dxd0 = dxd0; a.dxd1 = dxd1; a.dAlog = dAlog; a.dDs = dDs; a.ddtw = ddtw; a.ddtb = ddtb;
+    a.B = B; a.C = C; a.L = L; a.R = R; a.s = (hipStream_t)stream;
+    if (const int rc = ss2d_operands_ok("ss2d_scan_bwd", a, true, B != 0 && L != 0 /* an empty call returns OK whatever its pointers */, 16, C, R + 2, xd0_bstride, xd1_bstride)) return rc;
     BEM_REQUIRE((int64_t)L <= (int64_t)SB_MAXCH * 1024 * 4, "ss2d_scan_bwd: L too long");
     if (B == 0 || L == 0) return BEM_OK;
-    if (L % 4 == 0)
-        BEM_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)xd0 | (uintptr_t)xd1 | (uintptr_t)dy0 | (uintptr_t)dy1 | (uintptr_t)dx0 | (uintptr_t)dx1) & 15) == 0 &&
-                    xbs0 % 4 == 0 && xbs1 % 4 == 0, "ss2d_scan_bwd: 16-byte alignment");
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = a.s;
     const size_t nd = sizeof(float) * (size_t)B * 2 * (R + 2) * L;
     if (hipMemsetAsync(dxd0, 0, nd, s) != hipSuccess || hipMemsetAsync(dxd1, 0, nd, s) != hipSuccess) return bem_check_launch("ss2d_scan_bwd memset");
     static const bool fast = !(getenv("BEM_SCAN_BWD_ROWS") && atoi(getenv("BEM_SCAN_BWD_ROWS")) == 0);
     if (fast) {
         // whole-row channel-blocked forms for the plane sizes / dt_ranks of the shipped configuration (n_feat 40: R = 3 / 5 / 10)
-#define BEM_BWD_ROWS(NT, T, CB, RR) return launch_bwd_rows<NT, T, CB, RR>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, B, C, xbs0, xbs1, s)
-        if (L == 16384 && R == 3) BEM_BWD_ROWS(512, 8, 4, 3);
-        if (L == 4096 && R == 3) BEM_BWD_ROWS(256, 4, 4, 3);
-        if (L == 4096 && R == 5) BEM_BWD_ROWS(256, 4, 4, 5);
-        if (L == 1024 && R == 5) BEM_BWD_ROWS(256, 1, 4, 5);
-        if (L == 1024 && R == 10) BEM_BWD_ROWS(256, 1, 2, 10);
-        if (L == 256 && R == 10) BEM_BWD_ROWS(64, 1, 2, 10);
-        if (L == 1024 && R == 1) BEM_BWD_ROWS(256, 1, 4, 1);
-        if (L == 1024 && R == 2) BEM_BWD_ROWS(256, 1, 2, 2);
-#undef BEM_BWD_ROWS
+        if (L == 16384 && R == 3) return launch_bwd_rows<512, 8, 4, 3>(a);
+        if (L == 4096 && R == 3) return launch_bwd_rows<256, 4, 4, 3>(a);
+        if (L == 4096 && R == 5) return launch_bwd_rows<256, 4, 4, 5>(a);
+        if (L == 1024 && R == 5) return launch_bwd_rows<256, 1, 4, 5>(a);
+        if (L == 1024 && R == 10) return launch_bwd_rows<256, 1, 2, 10>(a);
+        if (L == 256 && R == 10) return launch_bwd_rows<64, 1, 2, 10>(a);
+        if (L == 1024 && R == 1) return launch_bwd_rows<256, 1, 4, 1>(a);
+        if (L == 1024 && R == 2) return launch_bwd_rows<256, 1, 2, 2>(a);
     }
     const int grid = C * B * 2;
     if (L <= 32)          // 4x4 and 2x2 planes: a workgroup per channel (the atomics are few, the channel loop below would only serialise)
-        ss2d_scan_bwd_kernel<64, 4><<<grid, 64, 0, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, B, C, L, R, xbs0, xbs1);
+        ss2d_scan_bwd_kernel<64, 4><<<grid, 64, 0, s>>>(SS2D_BWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1);
     else if (L <= 256) {  // 8x8 .. 16x16 planes: one wavefront per row, 4 channels per workgroup (181 -> 114 us at L = 64, C = 160, B = 8)
         constexpr int CBS = 4;
-        ss2d_scan_bwd_small_kernel<CBS><<<cdiv(C, CBS) * B * 2, 64, 0, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, B, C, L, R, xbs0, xbs1);
+        ss2d_scan_bwd_small_kernel<CBS><<<cdiv(C, CBS) * B * 2, 64, 0, s>>>(SS2D_BWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1);
     }
     else if (L <= 1024)
-        ss2d_scan_bwd_kernel<256, 4><<<grid, 256, 0, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, B, C, L, R, xbs0, xbs1);
+        ss2d_scan_bwd_kernel<256, 4><<<grid, 256, 0, s>>>(SS2D_BWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1);
     else
-        ss2d_scan_bwd_kernel<1024, 4><<<grid, 1024, 0, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, B, C, L, R, xbs0, xbs1);
+        ss2d_scan_bwd_kernel<1024, 4><<<grid, 1024, 0, s>>>(SS2D_BWD_OPERANDS(a), B, C, L, R, a.xbs0, a.xbs1);
     return bem_check_launch("ss2d_scan_bwd");
 }

@@ -1,6 +1,9 @@
-// Block-wide affine-map scan primitives shared by the forward (scan.hip) and backward (scan_bwd.hip) selective-scan kernels.
+// Shared by the selective-scan kernels (scan.hip, scan_bwd.hip, scan_nstate.hip): block- and wavefront-wide affine-map scan
+// primitives, row loads / stores, the fused-SS2D work-item decode, per-direction parameters and scan coefficients, and the host-side
+// operand check of the bem_ss2d_scan*_f32 entry points.
 #pragma once
 #include "bem_common.h"
+#include <climits>
 
 namespace {
 
@@ -124,6 +127,83 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, int64_t t0, int
     }
 }
 
+// unmasked float4 forms of load_row / store_row (whole tiles, 16-byte aligned rows; also rows of an LDS tile)
+template <int E>
+__device__ __forceinline__ void load4(const float* p, float (&v)[E]) {
+#pragma unroll
+    for (int i = 0; i < E; i += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + i);
+        v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
+    }
+}
+template <int E>
+__device__ __forceinline__ void store4(float* p, const float (&v)[E]) {
+#pragma unroll
+    for (int i = 0; i < E; i += 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fused SS2D scans: a launch covers 2 orientations x Bn images x n units (channels, or groups of CB channels), unit fastest.
+// ------------------------------------------------------------------------------------------------
+struct Ss2dItem { int u, b, o; };       // unit (channel c or channel group g), image, orientation
+__device__ __forceinline__ Ss2dItem ss2d_item(int wi, int n, int Bn) { return {wi % n, (wi / n) % Bn, wi / (n * Bn)}; }
+
+// Parameters of direction k (0 / 1: orientations 0 / 1 in memory order, 2 / 3: the same reversed) and channel c, from dtw (4, C, R),
+// dtb and Ds (4, C) and A (4, C, N); kc = k * C + c also indexes the channel's parameter gradients.
+struct Ss2dDir { const float* wdt; float dtb; const float* A; float D; int kc; };
+__device__ __forceinline__ Ss2dDir ss2d_dir(const float* __restrict__ dtw, const float* __restrict__ dtb, const float* __restrict__ A,
+                                            const float* __restrict__ Ds, int k, int C, int c, int R, int N = 1) {
+    const int kc = k * C + c;
+    return {dtw + (int64_t)kc * R, dtb[kc], A + (int64_t)kc * N, Ds[kc], kc};
+}
+
+// softplus and exp(dt A) on one base-2 logarithm: lg = log2(1 + e^z) (z log2 e beyond softplus' threshold of 20), then
+// dt = lg ln 2, exp(dt A) = 2^(A lg) and sigmoid(z) = 1 - 2^-lg
+constexpr float BEM_LOG2E = 1.44269504088896340736f, BEM_LN2 = 0.69314718055994530942f;
+__device__ __forceinline__ float softplus_log2(float z) {
+    return z <= 20.f ? __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(z * BEM_LOG2E)) : z * BEM_LOG2E;
+}
+
+// Scan coefficients of E positions of one direction (d_state 1): z = dtb + sum_r w_r dt_row_r, dl = softplus(z), a = exp(dl A),
+// b = dl B x; positions past L get the identity (a, b) = (1, 0).  Bv / Cv are the B and C rows.  The backward uses every output, the
+// forward the short form below (outputs that are not used cost nothing).
+template <int E>
+__device__ __forceinline__ void ss2d_coeffs(const float* __restrict__ xd /* (R+2, L) of one direction */, const float* __restrict__ wdt /* (R) */,
+                                            float dtb, float Ak, const float (&x)[E], int64_t t0, int L, int R, bool vec, float (&a)[E],
+                                            float (&b)[E], float (&Bv)[E], float (&Cv)[E], float (&dl)[E], float (&z)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) z[e] = 0.f;
+    for (int r = 0; r < R; ++r) {
+        float v[E];
+        load_row<E>(xd + (int64_t)r * L, t0, L, vec, v);
+        const float w = wdt[r];
+#pragma unroll
+        for (int e = 0; e < E; ++e) z[e] = fmaf(w, v[e], z[e]);
+    }
+    load_row<E>(xd + (int64_t)R * L, t0, L, vec, Bv);
+    load_row<E>(xd + (int64_t)(R + 1) * L, t0, L, vec, Cv);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const bool ok = t0 + e < L;
+        z[e] += dtb;
+        dl[e] = bem_softplus(z[e]);
+        a[e] = ok ? bem_fexp(dl[e] * Ak) : 1.f;
+        b[e] = ok ? dl[e] * Bv[e] * x[e] : 0.f;
+    }
+}
+template <int E>
+__device__ __forceinline__ void ss2d_coeffs(const float* __restrict__ xd, const float* __restrict__ wdt, float dtb, float Ak, const float (&x)[E],
+                                            int64_t t0, int L, int R, bool vec, float (&a)[E], float (&b)[E], float (&Cv)[E]) {
+    float Bv[E], dl[E], z[E];
+    ss2d_coeffs<E>(xd, wdt, dtb, Ak, x, t0, L, R, vec, a, b, Bv, Cv, dl, z);
+}
+
 template <int NT>
 __device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
 #pragma unroll
@@ -220,6 +300,55 @@ __device__ __forceinline__ float cross_wave_affine(float P, float S, float* ag, 
     const float c0 = carry;
     carry = fmaf(Pt, c0, St);
     return rw > 0 ? fmaf(Px, c0, Sx) : c0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side of the bem_ss2d_scan*_f32 entry points
+// ------------------------------------------------------------------------------------------------
+// Operands of one fused SS2D launch, forward (y0 / y1) or backward (dy / dx / the gradients); the launch helpers take this.
+struct Ss2dArgs {
+    const float *x0, *x1, *xd0, *xd1, *dtw, *dtb, *A, *Ds;
+    float *y0, *y1;
+    const float *dy0, *dy1;
+    float *dx0, *dx1, *dxd0, *dxd1, *dAlog, *dDs, *ddtw, *ddtb, *ws;
+    hipStream_t s;
+    int B, C, L, R, N;
+    int64_t xbs0, xbs1;          // x_dbl batch strides, resolved by ss2d_operands_ok (never 0)
+};
+#define SS2D_FWD_OPERANDS(a) a.x0, a.x1, a.xd0, a.xd1, a.dtw, a.dtb, a.A, a.Ds, a.y0, a.y1
+#define SS2D_BWD_OPERANDS(a) a.x0, a.x1, a.xd0, a.xd1, a.dy0, a.dy1, a.dtw, a.dtb, a.A, a.Ds, a.dx0, a.dx1, a.dxd0, a.dxd1, a.dAlog, a.dDs, a.ddtw, a.ddtb
+
+// The checks every entry point makes before it touches the GPU: no null operand (forward: y; backward: dy, dx and the gradients),
+// B / C / L / R in range (`units` workgroup units per (orientation, image) must fit a 31-bit grid), the x_dbl batch strides (0 = contiguous:
+// 2 * rows_per_dir * L) at least that and, for L % 4 == 0 (float4 rows), multiples of 4, and -- unless the entry point serves unaligned
+// tensors with another kernel -- the (B, C, L) and x_dbl tensors on 16 bytes in that case.  Resolves the strides into `a`.
+static inline int ss2d_operands_ok(const char* who, Ss2dArgs& a, bool bwd, bool need_align, int rmax, int64_t units, int rows_per_dir,
+                                   int64_t xd0_bstride, int64_t xd1_bstride) {
+    BEM_REQUIRE(a.x0 && a.x1 && a.xd0 && a.xd1 && a.dtw && a.dtb && a.A && a.Ds, "%s: null tensor", who);
+    if (bwd) BEM_REQUIRE(a.dy0 && a.dy1 && a.dx0 && a.dx1 && a.dxd0 && a.dxd1 && a.dAlog && a.dDs && a.ddtw && a.ddtb, "%s: null tensor", who);
+    else BEM_REQUIRE(a.y0 && a.y1, "%s: null tensor", who);
+    BEM_REQUIRE(a.B >= 0 && a.C > 0 && a.L >= 0 && a.R >= 1 && units * a.B * 2 < (1ll << 31), "%s: bad shape B=%d C=%d L=%d R=%d", who, a.B, a.C,
+                a.L, a.R);
+    BEM_REQUIRE(a.R <= rmax, "%s: dt_rank R=%d above %d", who, a.R, rmax);
+    const int64_t dense = (int64_t)2 * rows_per_dir * a.L;
+    a.xbs0 = xd0_bstride ? xd0_bstride : dense;
+    a.xbs1 = xd1_bstride ? xd1_bstride : dense;
+    const bool vec = a.L % 4 == 0;
+    BEM_REQUIRE(a.xbs0 >= dense && a.xbs1 >= dense && (!vec || (a.xbs0 % 4 == 0 && a.xbs1 % 4 == 0)), "%s: x_dbl batch strides", who);
+    const uintptr_t bits = (uintptr_t)a.x0 | (uintptr_t)a.x1 | (uintptr_t)a.xd0 | (uintptr_t)a.xd1 |
+                           (bwd ? (uintptr_t)a.dy0 | (uintptr_t)a.dy1 | (uintptr_t)a.dx0 | (uintptr_t)a.dx1 : (uintptr_t)a.y0 | (uintptr_t)a.y1);
+    BEM_REQUIRE(!(need_align && vec) || (bits & 15) == 0, "%s: 16-byte alignment", who);
+    return BEM_OK;
+}
+
+// Raises the dynamic-LDS limit of KERNEL, once per process.
+template <auto KERNEL>
+static inline void set_max_dynamic_lds(int bytes) {
+    static bool done = false;
+    if (!done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        done = true;
+    }
 }
 
 }  // namespace

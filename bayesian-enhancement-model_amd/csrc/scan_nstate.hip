@@ -40,15 +40,6 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ tile, const float
     }
 }
 
-template <int E>
-__device__ __forceinline__ void lds_row(const float* __restrict__ p, float (&v)[E]) {
-#pragma unroll
-    for (int i = 0; i < E; i += 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p + i);
-        v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
-    }
-}
-
 // (P, S) of this lane's E maps composed in scan order, then the wavefront scan: returns the state entering the lane's first
 // element and advances `carry` to the state leaving the tile.
 template <int E, bool REV>
@@ -75,18 +66,32 @@ __device__ __forceinline__ void tile_dt(const float* __restrict__ tile, const fl
     for (int e = 0; e < E; ++e) z[e] = dtb;
     for (int r = 0; r < R; ++r) {
         float v[E];
-        lds_row<E>(tile + r * T + lane * E, v);
+        load4<E>(tile + r * T + lane * E, v);
         const float w = wdt[r];
 #pragma unroll
         for (int e = 0; e < E; ++e) z[e] = fmaf(w, v[e], z[e]);
     }
 }
 
+// coefficients of state n from dl = softplus(dt) and dlx = dl x (shared by the states): a = exp(dl A_n), b = dlx B_n, identity past L
+template <int E>
+__device__ __forceinline__ void state_coeffs(const float (&dl)[E], const float (&dlx)[E], const float (&Bv)[E], float An, int64_t te, int L,
+                                             float (&a)[E], float (&b)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const bool ok = te + e < L;
+        a[e] = ok ? bem_fexp(dl[e] * An) : 1.f;
+        b[e] = ok ? dlx[e] * Bv[e] : 0.f;
+    }
+}
+
 template <int NM, int E, int CB, bool REV>
 __device__ __forceinline__ void scan_n_dir(float* tile, const float* __restrict__ xr, const float* __restrict__ xd, float* __restrict__ yr,
-                                           const float* __restrict__ wdt, float dtb, const float* __restrict__ Ak, float Dk, bool live,
-                                           int L, int R, int N) {
+                                           const Ss2dDir p, bool live, int L, int R, int N) {
     constexpr int T = 64 * E, NT = CB * 64;
+    const float* wdt = p.wdt;
+    const float* Ak = p.A;
+    const float dtb = p.dtb, Dk = p.D;
     const int lane = threadIdx.x & 63;
     const bool vec = (L % 4 == 0);
     const int ntiles = (L + T - 1) / T, rows = R + 2 * N;
@@ -118,14 +123,9 @@ __device__ __forceinline__ void scan_n_dir(float* tile, const float* __restrict_
         for (int n = 0; n < NM; ++n) {
             if (n >= N) continue;
             float Bv[E], Cv[E], a[E], bb[E];
-            lds_row<E>(tile + (R + n) * T + lane * E, Bv);
-            lds_row<E>(tile + (R + N + n) * T + lane * E, Cv);
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const bool ok = te + e < L;
-                a[e] = ok ? bem_fexp(dl[e] * A[n]) : 1.f;
-                bb[e] = ok ? dlx[e] * Bv[e] : 0.f;
-            }
+            load4<E>(tile + (R + n) * T + lane * E, Bv);
+            load4<E>(tile + (R + N + n) * T + lane * E, Cv);
+            state_coeffs<E>(dl, dlx, Bv, A[n], te, L, a, bb);
             float hh = wave_enter<E, REV>(a, bb, carry[n]);
 #pragma unroll
             for (int i = 0; i < E; ++i) {
@@ -145,21 +145,18 @@ __global__ __launch_bounds__(CB * 64) void ss2d_scan_n_kernel(
     const float* __restrict__ dtw, const float* __restrict__ dtb, const float* __restrict__ A, const float* __restrict__ Ds,
     float* __restrict__ y0, float* __restrict__ y1, int Bn, int C, int L, int R, int N, int64_t xbs0, int64_t xbs1) {
     extern __shared__ float tile[];
-    const int G = (C + CB - 1) / CB, wi = blockIdx.x;
-    const int g = wi % G, b = (wi / G) % Bn, o = wi / (G * Bn);
+    const Ss2dItem it = ss2d_item(blockIdx.x, (C + CB - 1) / CB, Bn);
+    const int b = it.b, o = it.o;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = g * CB + wave;
+    const int c = it.u * CB + wave;
     const bool live = c < C;
     const int cc = live ? c : C - 1;                         // parameter reads of an idle slot stay in bounds
     const int64_t row = ((int64_t)b * C + cc) * L;
     const float* xr = (o ? x1 : x0) + row;
     float* yr = (o ? y1 : y0) + row;
     const float* xd = o ? xd1 + (int64_t)b * xbs1 : xd0 + (int64_t)b * xbs0;
-    const int kf = o, kr = o + 2;
-    scan_n_dir<NM, E, CB, false>(tile, xr, xd, yr, dtw + ((int64_t)kf * C + cc) * R, dtb[kf * C + cc], A + ((int64_t)kf * C + cc) * N,
-                                 Ds[kf * C + cc], live, L, R, N);
-    scan_n_dir<NM, E, CB, true>(tile, xr, xd + (int64_t)(R + 2 * N) * L, yr, dtw + ((int64_t)kr * C + cc) * R, dtb[kr * C + cc],
-                                A + ((int64_t)kr * C + cc) * N, Ds[kr * C + cc], live, L, R, N);
+    scan_n_dir<NM, E, CB, false>(tile, xr, xd, yr, ss2d_dir(dtw, dtb, A, Ds, o, C, cc, R, N), live, L, R, N);
+    scan_n_dir<NM, E, CB, true>(tile, xr, xd + (int64_t)(R + 2 * N) * L, yr, ss2d_dir(dtw, dtb, A, Ds, o + 2, C, cc, R, N), live, L, R, N);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -168,9 +165,12 @@ __global__ __launch_bounds__(CB * 64) void ss2d_scan_n_kernel(
 template <int NM, int E, int CB, bool REV>
 __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* accw, const float* __restrict__ xr, const float* __restrict__ dyr,
                                                const float* __restrict__ xd, float* __restrict__ dxd, float* __restrict__ dxr, float* __restrict__ cws,
-                                               const float* __restrict__ wdt, float dtb, const float* __restrict__ Ak, float Dk, bool live, bool first,
-                                               int L, int R, int N, float* dAlog_p, float* dDs_p, float* ddtb_p, float* ddtw_p) {
+                                               const Ss2dDir p, bool live, bool first, int L, int R, int N, float* __restrict__ dAlog,
+                                               float* __restrict__ dDs, float* __restrict__ ddtb, float* __restrict__ ddtw) {
     constexpr int T = 64 * E, NT = CB * 64;
+    const float* wdt = p.wdt;
+    const float* Ak = p.A;
+    const float dtb = p.dtb, Dk = p.D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool vec = (L % 4 == 0);
     const int ntiles = (L + T - 1) / T, rows = R + 2 * N;
@@ -205,13 +205,8 @@ __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* a
         for (int n = 0; n < NM; ++n) {
             if (n >= N) continue;
             float Bv[E], a[E], bb[E];
-            lds_row<E>(tile + (R + n) * T + lane * E, Bv);
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const bool ok = te + e < L;
-                a[e] = ok ? bem_fexp(dl[e] * A[n]) : 1.f;
-                bb[e] = ok ? dlx[e] * Bv[e] : 0.f;
-            }
+            load4<E>(tile + (R + n) * T + lane * E, Bv);
+            state_coeffs<E>(dl, dlx, Bv, A[n], te, L, a, bb);
             (void)wave_enter<E, REV>(a, bb, carry[n]);
         }
     }
@@ -253,13 +248,11 @@ __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* a
                 if (n >= N) continue;
                 const float cin = cws[(int64_t)j * N + n];
                 float Bv[E], Cv[E], a[E], bb[E], hm[E], h[E], ar[E], br[E];
-                lds_row<E>(tile + (R + n) * T + lane * E, Bv);
-                lds_row<E>(tile + (R + N + n) * T + lane * E, Cv);
+                load4<E>(tile + (R + n) * T + lane * E, Bv);
+                load4<E>(tile + (R + N + n) * T + lane * E, Cv);
+                state_coeffs<E>(dl, dlx, Bv, A[n], te, L, a, bb);
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
-                    const bool ok = te + e < L;
-                    a[e] = ok ? bem_fexp(dl[e] * A[n]) : 1.f;
-                    bb[e] = ok ? dlx[e] * Bv[e] : 0.f;
                     ar[e] = a[e];
                     br[e] = a[e] * Cv[e] * dy[e];
                 }
@@ -302,7 +295,7 @@ __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* a
             }
             for (int r = 0; r < R; ++r) {
                 float v[E];
-                lds_row<E>(tile + r * T + lane * E, v);
+                load4<E>(tile + r * T + lane * E, v);
                 const float w = wdt[r];
                 float s = 0.f;
 #pragma unroll
@@ -310,8 +303,7 @@ __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* a
                     s = fmaf(dz[e], v[e], s);
                     atomicAdd(acc + r * T + lane * E + e, dz[e] * w);
                 }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, BEM_WAVE);
+                s = wave_sum(s);
                 if (lane == 0) accw[wave * SN_RMAX + r] += s;
             }
             if (!first) {
@@ -329,24 +321,19 @@ __device__ __forceinline__ void scan_n_dir_bwd(float* tile, float* acc, float* a
         }
     }
     if (live) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            accD += __shfl_xor(accD, d, BEM_WAVE);
-            accB += __shfl_xor(accB, d, BEM_WAVE);
-        }
+        accD = wave_sum(accD);
+        accB = wave_sum(accB);
 #pragma unroll
         for (int n = 0; n < NM; ++n) {
             if (n >= N) continue;
-            float s = dA[n];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, BEM_WAVE);
-            if (lane == 0) atomicAdd(dAlog_p + n, s * A[n]);   // A = -exp(A_logs): dA_logs = dA * A
+            const float s = wave_sum(dA[n]);
+            if (lane == 0) atomicAdd(dAlog + (int64_t)p.kc * N + n, s * A[n]);   // A = -exp(A_logs): dA_logs = dA * A
         }
         if (lane == 0) {
-            atomicAdd(dDs_p, accD);
-            atomicAdd(ddtb_p, accB);
+            atomicAdd(dDs + p.kc, accD);
+            atomicAdd(ddtb + p.kc, accB);
         }
-        if (lane < R) atomicAdd(ddtw_p + lane, accw[wave * SN_RMAX + lane]);
+        if (lane < R) atomicAdd(ddtw + (int64_t)p.kc * R + lane, accw[wave * SN_RMAX + lane]);
     }
 }
 
@@ -364,10 +351,10 @@ __global__ __launch_bounds__(CB * 64) void ss2d_scan_n_bwd_kernel(
     float* tile = lds;
     float* acc = lds + rows * T;
     float* accw = acc + rows * T;
-    const int G = (C + CB - 1) / CB, wi = blockIdx.x;
-    const int g = wi % G, b = (wi / G) % Bn, o = wi / (G * Bn);
+    const Ss2dItem it = ss2d_item(blockIdx.x, (C + CB - 1) / CB, Bn);
+    const int b = it.b, o = it.o;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = g * CB + wave;
+    const int c = it.u * CB + wave;
     const bool live = c < C;
     const int cc = live ? c : C - 1;
     const int64_t row = ((int64_t)b * C + cc) * L;
@@ -378,44 +365,30 @@ __global__ __launch_bounds__(CB * 64) void ss2d_scan_n_bwd_kernel(
     float* dxd = (o ? dxd1 : dxd0) + (int64_t)b * 2 * rows * L;
     const int64_t ntiles = (L + T - 1) / T;
     float* cws = ws + (((int64_t)o * Bn + b) * C + cc) * ntiles * N;   // entry states of every tile, one direction at a time
-    const int kf = o, kr = o + 2;
-    scan_n_dir_bwd<NM, E, CB, false>(tile, acc, accw, xr, dyr, xd, dxd, dxr, cws, dtw + ((int64_t)kf * C + cc) * R, dtb[kf * C + cc],
-                                     A + ((int64_t)kf * C + cc) * N, Ds[kf * C + cc], live, true, L, R, N, dAlog + ((int64_t)kf * C + cc) * N,
-                                     dDs + kf * C + cc, ddtb + kf * C + cc, ddtw + ((int64_t)kf * C + cc) * R);
+    scan_n_dir_bwd<NM, E, CB, false>(tile, acc, accw, xr, dyr, xd, dxd, dxr, cws, ss2d_dir(dtw, dtb, A, Ds, o, C, cc, R, N), live, true, L, R, N,
+                                     dAlog, dDs, ddtb, ddtw);
     scan_n_dir_bwd<NM, E, CB, true>(tile, acc, accw, xr, dyr, xd + (int64_t)rows * L, dxd + (int64_t)rows * L, dxr, cws,
-                                    dtw + ((int64_t)kr * C + cc) * R, dtb[kr * C + cc], A + ((int64_t)kr * C + cc) * N, Ds[kr * C + cc], live,
-                                    false, L, R, N, dAlog + ((int64_t)kr * C + cc) * N, dDs + kr * C + cc, ddtb + kr * C + cc,
-                                    ddtw + ((int64_t)kr * C + cc) * R);
+                                    ss2d_dir(dtw, dtb, A, Ds, o + 2, C, cc, R, N), live, false, L, R, N, dAlog, dDs, ddtb, ddtw);
 }
 
 constexpr int SN_E = 4;          // positions per lane: 256-position tiles, float4 rows
 constexpr int SN_CB = 8;         // channels (wavefronts) per workgroup: divides the n_feat-40 widths 40 / 80 / 160
 
 template <int NM>
-static int launch_fwd(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dtw, const float* dtb, const float* A,
-                      const float* Ds, float* y0, float* y1, int B, int C, int L, int R, int N, int64_t xbs0, int64_t xbs1, hipStream_t s) {
-    const size_t lds = sizeof(float) * (size_t)(R + 2 * N) * 64 * SN_E;
-    ss2d_scan_n_kernel<NM, SN_E, SN_CB><<<cdiv(C, SN_CB) * B * 2, SN_CB * 64, lds, s>>>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, N,
-                                                                                      xbs0, xbs1);
+static int launch_fwd(const Ss2dArgs& a) {
+    const size_t lds = sizeof(float) * (size_t)(a.R + 2 * a.N) * 64 * SN_E;
+    ss2d_scan_n_kernel<NM, SN_E, SN_CB><<<cdiv(a.C, SN_CB) * a.B * 2, SN_CB * 64, lds, a.s>>>(SS2D_FWD_OPERANDS(a), a.B, a.C, a.L, a.R, a.N, a.xbs0, a.xbs1);
     return bem_check_launch("ss2d_scan_n");
 }
 
 template <int NM>
-static int launch_bwd(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dy0, const float* dy1, const float* dtw,
-                      const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0, float* dxd1, float* dAlog, float* dDs,
-                      float* ddtw, float* ddtb, float* ws, int B, int C, int L, int R, int N, int64_t xbs0, int64_t xbs1, hipStream_t s) {
+static int launch_bwd(const Ss2dArgs& a) {
     constexpr size_t lds_max = sizeof(float) * (2 * (size_t)(SN_RMAX + 2 * NM) * 64 * SN_E + SN_CB * SN_RMAX);
     static_assert(lds_max <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ss2d_scan_n_bwd_kernel<NM, SN_E, SN_CB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_max);
-        attr_set = true;
-    }
-    const size_t lds = sizeof(float) * (2 * (size_t)(R + 2 * N) * 64 * SN_E + SN_CB * SN_RMAX);
-    ss2d_scan_n_bwd_kernel<NM, SN_E, SN_CB><<<cdiv(C, SN_CB) * B * 2, SN_CB * 64, lds, s>>>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1,
-                                                                                          dxd0, dxd1, dAlog, dDs, ddtw, ddtb, ws, B, C, L, R, N,
-                                                                                          xbs0, xbs1);
+    set_max_dynamic_lds<&ss2d_scan_n_bwd_kernel<NM, SN_E, SN_CB>>((int)lds_max);
+    const size_t lds = sizeof(float) * (2 * (size_t)(a.R + 2 * a.N) * 64 * SN_E + SN_CB * SN_RMAX);
+    ss2d_scan_n_bwd_kernel<NM, SN_E, SN_CB><<<cdiv(a.C, SN_CB) * a.B * 2, SN_CB * 64, lds, a.s>>>(SS2D_BWD_OPERANDS(a), a.ws, a.B, a.C, a.L, a.R, a.N,
+                                                                                                a.xbs0, a.xbs1);
     return bem_check_launch("ss2d_scan_n_bwd");
 }
 
@@ -426,21 +399,14 @@ extern "C" int bem_ss2d_scan_n_supported(int N) { return N >= 1 && N <= SN_NMAX;
 extern "C" int bem_ss2d_scan_n_f32(const float* x0, const float* x1, const float* xd0, const float* xd1, const float* dtw, const float* dtb,
                                    const float* A, const float* Ds, float* y0, float* y1, int B, int C, int L, int R, int N,
                                    int64_t xd0_bstride, int64_t xd1_bstride, void* stream) {
-    BEM_REQUIRE(x0 && x1 && xd0 && xd1 && dtw && dtb && A && Ds && y0 && y1, "ss2d_scan_n: null tensor");
     BEM_REQUIRE(N >= 1 && N <= SN_NMAX, "ss2d_scan_n: d_state N=%d outside 1..%d", N, SN_NMAX);
-    BEM_REQUIRE(B >= 0 && C > 0 && L >= 0 && R >= 1 && R <= SN_RMAX && (int64_t)cdiv(C, SN_CB) * B * 2 < (1ll << 31),
-                "ss2d_scan_n: bad shape B=%d C=%d L=%d R=%d (dt_rank <= %d)", B, C, L, R, SN_RMAX);
-    const int64_t rows2 = (int64_t)2 * (R + 2 * N) * L;
-    const int64_t xbs0 = xd0_bstride ? xd0_bstride : rows2, xbs1 = xd1_bstride ? xd1_bstride : rows2;
-    BEM_REQUIRE(xbs0 >= rows2 && xbs1 >= rows2 && (L % 4 != 0 || (xbs0 % 4 == 0 && xbs1 % 4 == 0)), "ss2d_scan_n: x_dbl batch strides");
-    if (L % 4 == 0)
-        BEM_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)xd0 | (uintptr_t)xd1 | (uintptr_t)y0 | (uintptr_t)y1) & 15) == 0,
-                    "ss2d_scan_n: 16-byte alignment");
+    Ss2dArgs a{};
+    a.x0 = x0; a.x1 = x1; a.xd0 = xd0; a.xd1 = xd1; a.dtw = dtw; a.dtb = dtb; a.A = A; a.Ds = Ds;
+    a.y0 = y0; a.y1 = y1;
+    a.B = B; a.C = C; a.L = L; a.R = R; a.N = N; a.s = (hipStream_t)stream;
+    if (const int rc = ss2d_operands_ok("ss2d_scan_n", a, false, true, SN_RMAX, cdiv(C, SN_CB), R + 2 * N, xd0_bstride, xd1_bstride)) return rc;
     if (B == 0 || L == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (N <= 4) return launch_fwd<4>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, N, xbs0, xbs1, s);
-    if (N <= 8) return launch_fwd<8>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, N, xbs0, xbs1, s);
-    return launch_fwd<16>(x0, x1, xd0, xd1, dtw, dtb, A, Ds, y0, y1, B, C, L, R, N, xbs0, xbs1, s);
+    return N <= 4 ? launch_fwd<4>(a) : N <= 8 ? launch_fwd<8>(a) : launch_fwd<16>(a);
 }
 
 extern "C" int64_t bem_ss2d_scan_n_bwd_ws_elems(int B, int C, int L, int N) {
@@ -452,26 +418,17 @@ extern "C" int bem_ss2d_scan_n_bwd_f32(const float* x0, const float* x1, const f
                                        const float* dtw, const float* dtb, const float* A, const float* Ds, float* dx0, float* dx1, float* dxd0,
                                        float* dxd1, float* dAlog, float* dDs, float* ddtw, float* ddtb, float* ws, int64_t ws_elems, int B, int C,
                                        int L, int R, int N, int64_t xd0_bstride, int64_t xd1_bstride, void* stream) {
-    BEM_REQUIRE(x0 && x1 && xd0 && xd1 && dy0 && dy1 && dtw && dtb && A && Ds && dx0 && dx1 && dxd0 && dxd1 && dAlog && dDs && ddtw && ddtb && ws,
-                "ss2d_scan_n_bwd: null tensor");
     BEM_REQUIRE(N >= 1 && N <= SN_NMAX, "ss2d_scan_n_bwd: d_state N=%d outside 1..%d", N, SN_NMAX);
-    BEM_REQUIRE(B >= 0 && C > 0 && L >= 0 && R >= 1 && R <= SN_RMAX && (int64_t)cdiv(C, SN_CB) * B * 2 < (1ll << 31),
-                "ss2d_scan_n_bwd: bad shape B=%d C=%d L=%d R=%d (dt_rank <= %d)", B, C, L, R, SN_RMAX);
-    const int64_t rows2 = (int64_t)2 * (R + 2 * N) * L;
-    const int64_t xbs0 = xd0_bstride ? xd0_bstride : rows2, xbs1 = xd1_bstride ? xd1_bstride : rows2;
-    BEM_REQUIRE(xbs0 >= rows2 && xbs1 >= rows2 && (L % 4 != 0 || (xbs0 % 4 == 0 && xbs1 % 4 == 0)), "ss2d_scan_n_bwd: x_dbl batch strides");
+    Ss2dArgs a{};
+    a.x0 = x0; a.x1 = x1; a.xd0 = xd0; a.xd1 = xd1; a.dtw = dtw; a.dtb = dtb; a.A = A; a.Ds = Ds;
+    a.dy0 = dy0; a.dy1 = dy1; a.dx0 = dx0; a.dx1 = dx1; a.dxd0 = dxd0; a.dxd1 = dxd1; a.dAlog = dAlog; a.dDs = dDs; a.ddtw = ddtw; a.ddtb = ddtb; a.ws = ws;
+    a.B = B; a.C = C; a.L = L; a.R = R; a.N = N; a.s = (hipStream_t)stream;
+    BEM_REQUIRE(ws, "ss2d_scan_n_bwd: null tensor");
+    if (const int rc = ss2d_operands_ok("ss2d_scan_n_bwd", a, true, true, SN_RMAX, cdiv(C, SN_CB), R + 2 * N, xd0_bstride, xd1_bstride)) return rc;
     BEM_REQUIRE(ws_elems >= bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N), "ss2d_scan_n_bwd: workspace of %lld floats, %lld needed", (long long)ws_elems,
                 (long long)bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N));
-    if (L % 4 == 0)
-        BEM_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)xd0 | (uintptr_t)xd1 | (uintptr_t)dy0 | (uintptr_t)dy1 | (uintptr_t)dx0 | (uintptr_t)dx1) & 15) == 0,
-                    "ss2d_scan_n_bwd: 16-byte alignment");
     if (B == 0 || L == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nd = sizeof(float) * (size_t)B * rows2;
-    if (hipMemsetAsync(dxd0, 0, nd, s) != hipSuccess || hipMemsetAsync(dxd1, 0, nd, s) != hipSuccess) return bem_check_launch("ss2d_scan_n_bwd memset");
-#define BEM_SN_BWD(NM) return launch_bwd<NM>(x0, x1, xd0, xd1, dy0, dy1, dtw, dtb, A, Ds, dx0, dx1, dxd0, dxd1, dAlog, dDs, ddtw, ddtb, ws, B, C, L, R, N, xbs0, xbs1, s)
-    if (N <= 4) BEM_SN_BWD(4);
-    if (N <= 8) BEM_SN_BWD(8);
-    BEM_SN_BWD(16);
-#undef BEM_SN_BWD
+    const size_t nd = sizeof(float) * (size_t)B * 2 * (R + 2 * N) * L;
+    if (hipMemsetAsync(dxd0, 0, nd, a.s) != hipSuccess || hipMemsetAsync(dxd1, 0, nd, a.s) != hipSuccess) return bem_check_launch("ss2d_scan_n_bwd memset");
+    return N <= 4 ? launch_bwd<4>(a) : N <= 8 ? launch_bwd<8>(a) : launch_bwd<16>(a);
 }

@@ -1,5 +1,5 @@
 // Shared device helpers of the x6 (3-limb bf16) matrix-core kernels: operand typedefs, the exact limb split, the six-product MAC,
-// the accumulator layout and the XCD-aware tile order.  Included by pw_gemm_x6.hip, pack.hip, conv_x6.hip, upfuse_x6.hip, wgrad_x6.hip and (through
+// the accumulator layout (the XCD-aware tile order xcd_tile() is in bem_common.h).  Included by pw_gemm_x6.hip, pack.hip, conv_x6.hip, upfuse_x6.hip, wgrad_x6.hip and (through
 // x6_tile.h) gdmlp_x6.hip and ss2d_front_x6.hip; see the header comment of pw_gemm_x6.hip.
 #pragma once
 #include "bem_common.h"
@@ -12,13 +12,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t fbits(float v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ float bitsf(uint32_t u) { return __builtin_bit_cast(float, u); }
-
-// Workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Give every XCD a contiguous run of pixel
-// tiles so that the chunks one L2 collects (and later writes back) for a plane are adjacent in memory.
-__device__ __forceinline__ int xcd_tile(int x, int nx) {
-    const int per = nx >> 3, rem = nx & 7, xcd = x & 7, idx = x >> 3;
-    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
 
 // exact 3-limb split of 8 values (the lane's 8 channels of one k-block and sub-tile) into three MFMA operands.
 // Limbs are taken by round-to-nearest-even (v_cvt_pk_bf16_f32, two values per instruction): |m| <= 2^-8 |v|,

@@ -15,7 +15,7 @@ def timeit(fn, n=reps):
 
 
 B = 64
-for C, H in ((40, 128), (80, 64)):
+for C, H in ((40, 128), (80, 64), (160, 32)):
     L, R = H * H, (C + 15) // 16
     g = torch.Generator().manual_seed(0)
     x = torch.randn(B, C, H, H, generator=g).cuda()

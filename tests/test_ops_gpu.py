@@ -162,7 +162,8 @@ def _ss2d_fused64(x0, x1, xd0, xd1, dtw, dtb, A, Ds):
                                    (1, 40, 224, 320, 3),      # config-5 level 0 (448x640): 35 chunk carries
                                    (1, 80, 112, 160, 5),      # config-5 level 1: L % 2048 != 0, generic chunked kernel
                                    (1, 160, 56, 80, 10),      # config-5 level 2
-                                   (1, 80, 128, 128, 5)])     # sibling level 1: chunked form with a runtime dt_rank
+                                   (1, 80, 128, 128, 5),      # sibling level 1: chunked form with a runtime dt_rank
+                                   (1, 18, 32, 32, 10)])      # channel-blocked rows form: grid of 10 (not a multiple of 8), last group 2 of 4 channels
 def test_ss2d_scan_long_planes_vs_float64(ops, shape):
     """bem_ss2d_scan on the long planes the shipped nets reach, at a recurrence-dominated operating point (Ds ~ 0.1 N(0,1), dt from
     0.05 to ~1, B and C of unit size: the state term C*h is as large as D*u) against the float64 closed form.  y is held to
@@ -678,7 +679,8 @@ def test_gdmlp_x6_vs_chain_and_float64(ops, cfg):
     close(y, ref, 1e-4, 4e-5, f"gdmlp_x6 vs torch f64 {cfg}")
 
 
-@pytest.mark.parametrize("shape", [(2, 40, 128, 128, 3), (1, 80, 64, 64, 5), (2, 160, 32, 32, 10), (1, 6, 16, 64, 10), (1, 5, 256, 16, 5)])
+@pytest.mark.parametrize("shape", [(2, 40, 128, 128, 3), (1, 80, 64, 64, 5), (2, 160, 32, 32, 10), (1, 6, 16, 64, 10), (1, 5, 256, 16, 5),
+                                   (1, 18, 32, 32, 10)])      # grid of 10 workgroups (not a multiple of 8), last group 2 of 4 channels
 def test_ss2d_scan_row_major_form(ops, shape):
     """bem_ss2d_scan_rm (orientation 1 staged through LDS, y1 row-major) against the transposed-tensor form: identical
     arithmetic, so the results must agree to the last bit; non-square planes and a partial channel group included."""
