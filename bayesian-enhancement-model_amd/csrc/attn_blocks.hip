@@ -30,8 +30,7 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
     for (int r = wave; r < Cr; r += 4) {
         double acc = 0.0;
         for (int c = lane; c < C; c += 64) acc = fma((double)w1[(int64_t)r * C + c], (double)m[c], acc);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
+        acc = wave_sum(acc);
         if (lane == 0) h[r] = fmaxf((float)acc, 0.f);
     }
     __syncthreads();
@@ -121,8 +120,7 @@ __global__ __launch_bounds__(256) void chan_dot_kernel(const float* __restrict__
         const float* bp = b2 + ((int64_t)b * C + c) * HW;
         for (int64_t p = threadIdx.x; p < HW; p += 256) acc = fmaf(ap[p], bp[p], acc);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -152,16 +150,14 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
     for (int r = wave; r < Cr; r += 4) {       // the forward's h, bit for bit (same sum, same order): the ReLU mask is the one y was made with
         double acc = 0.0;
         for (int c = lane; c < C; c += 64) acc = fma((double)w1[(int64_t)r * C + c], (double)m[c], acc);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
+        acc = wave_sum(acc);
         if (lane == 0) h[r] = fmaxf((float)acc, 0.f);
     }
     __syncthreads();
     for (int r = wave; r < Cr; r += 4) {       // dh[r] = sum_c W2[c][r] dz2[c]
         float acc = 0.f;
         for (int c = lane; c < C; c += 64) acc = fmaf(w2[(int64_t)c * Cr + r], dz2[c], acc);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
+        acc = wave_sum(acc);
         if (lane == 0) dz1[r] = h[r] > 0.f ? acc : 0.f;
     }
     __syncthreads();
@@ -236,8 +232,7 @@ __global__ __launch_bounds__(256) void sa_bwd_dw_kernel(const float* __restrict_
         const int yy = (int)(p / W) + dy - r, xx = (int)(p % W) + dxx - r;
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) acc = fmaf(map[(b * 2 + ch) * HW + (int64_t)yy * W + xx], dpre[i], acc);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, BEM_WAVE);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(dw + tap, sh[0] + sh[1] + sh[2] + sh[3]);

@@ -8,22 +8,10 @@
 //   - fused AdamW + global-norm clip on one flat parameter buffer (torch.optim.AdamW, clip_grad_norm_)
 // All f32, NCHW planar; reductions over pixels go wave (DPP / shuffles) -> LDS -> one float atomic per workgroup.
 #include "bem_common.h"
+#include "wavelet.h"
 #include <algorithm>
 
 namespace {
-
-#define GRID1D(n) dim3((unsigned)cdiv64((n), 256))
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
-    return v;
-}
 
 // ---------------------------------------------------------------- L1 loss -------------------------------------------
 // sum |pred - gt| in f64 (one atomic per workgroup); dpred = sign(pred - gt) * scale (scale = loss_weight / numel).
@@ -37,7 +25,7 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred,
         s += fabsf(d);
         if (dpred) dpred[i] = d > 0.f ? scale : (d < 0.f ? -scale : 0.f);
     }
-    s = wave_sum_d(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
@@ -45,13 +33,6 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred,
 __global__ void l1_final_kernel(const double* __restrict__ acc, float* __restrict__ loss, double inv_n) { if (loss) loss[0] = (float)(acc[0] * inv_n); }
 
 // ---------------------------------------------------------------- IWT + Hamilton backward ---------------------------
-__device__ __forceinline__ void iwt4f(float ll, float hl, float lh, float hh, float (&o)[4]) {
-    ll /= 2; hl /= 2; lh /= 2; hh /= 2;
-    o[0] = ll - hl - lh + hh;
-    o[1] = ll - hl + lh - hh;
-    o[2] = ll + hl - lh - hh;
-    o[3] = ll + hl + lh + hh;
-}
 __global__ void iwt_hamilton_bwd_kernel(const float* __restrict__ q1w, const float* __restrict__ q2w, const float* __restrict__ dout,
                                         float* __restrict__ d1, float* __restrict__ d2, int h, int w, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -64,8 +45,8 @@ __global__ void iwt_hamilton_bwd_kernel(const float* __restrict__ q1w, const flo
     float P[4][4], Q[4][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        iwt4f(a[(int64_t)k * hw], a[(int64_t)(4 + k) * hw], a[(int64_t)(8 + k) * hw], a[(int64_t)(12 + k) * hw], P[k]);
-        iwt4f(c[(int64_t)k * hw], c[(int64_t)(4 + k) * hw], c[(int64_t)(8 + k) * hw], c[(int64_t)(12 + k) * hw], Q[k]);
+        iwt4(a[(int64_t)k * hw], a[(int64_t)(4 + k) * hw], a[(int64_t)(8 + k) * hw], a[(int64_t)(12 + k) * hw], P[k]);
+        iwt4(c[(int64_t)k * hw], c[(int64_t)(4 + k) * hw], c[(int64_t)(8 + k) * hw], c[(int64_t)(12 + k) * hw], Q[k]);
     }
     const int W2 = 2 * w;
     const float* gp = dout + (int64_t)b * 3 * 4 * hw + (int64_t)(2 * y) * W2 + 2 * x;
@@ -541,7 +522,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
         s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += (double)v * v; }
-    s = wave_sum_d(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
@@ -579,7 +560,7 @@ extern "C" int bem_l1_loss_f32(const float* pred, const float* gt, float* dpred,
                                const float* gmul, void* stream) {
     BEM_REQUIRE(pred && gt && (loss || dpred) && ws && n > 0, "l1_loss: null pointer / empty tensor");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, sizeof(double), s) != hipSuccess) return bem_check_launch("l1_loss memset");
+    BEM_ZERO(ws, sizeof(double), s, "l1_loss");
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, 256), 2048);
     l1_kernel<<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, weight / (float)n, gmul);
     l1_final_kernel<<<1, 1, 0, s>>>(ws, loss, (double)weight / (double)n);
@@ -721,7 +702,7 @@ extern "C" int bem_dwact_bwd_f32(const float* t, const float* w, const float* bi
 extern "C" int bem_grad_sumsq_f32(const float* g, int64_t n, double* acc, void* stream) {
     BEM_REQUIRE(g && acc && n > 0 && ((uintptr_t)g & 15) == 0, "grad_sumsq: bad arguments (16-byte aligned buffer)");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(acc, 0, sizeof(double), s) != hipSuccess) return bem_check_launch("grad_sumsq memset");
+    BEM_ZERO(acc, sizeof(double), s, "grad_sumsq");
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, 1024), 1024);
     sumsq_kernel<<<grid, 256, 0, s>>>(g, n, acc);
     return bem_check_launch("grad_sumsq");

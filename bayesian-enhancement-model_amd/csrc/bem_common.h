@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../../include/bem_hip.h"
+#include "reduce.h"
 
 #define BEM_WAVE 64
 
@@ -27,8 +28,15 @@ static inline int bem_check_launch(const char* what) {
     return BEM_OK;
 }
 
+// Zero `bytes` at p on stream s ahead of a kernel that accumulates there; a failure leaves the entry point with the launch error.
+#define BEM_ZERO(p, bytes, s, what)                                                                         \
+    do {                                                                                                    \
+        if (hipMemsetAsync((p), 0, (bytes), (s)) != hipSuccess) return bem_check_launch(what " memset");    \
+    } while (0)
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+#define GRID1D(n) dim3((unsigned)cdiv64((n), 256))      // one thread per element, 256 per workgroup
 
 // Workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Give every XCD a contiguous run of work items (the pixel
 // tiles of a plane in the x6 kernels, the channel rows of one (orientation, image) in the scans), so that what one L2 collects
@@ -72,7 +80,7 @@ __device__ __forceinline__ float bem_erf_fast(float x) {
 __device__ __forceinline__ float bem_gelu_fast(float x) { return 0.5f * x * (1.f + bem_erf_fast(x * 0.70710678118654752440f)); }
 
 // Philox4x32-10 counter-based generator + Box-Muller: one N(0,1) draw per (element index, stream id) under a 64-bit seed.
-// Shared by the Bayesian weight sampler (elementwise.hip) and the fused sample-and-pack kernels (pack.hip): the same
+// Shared by the Bayesian weight sampler and the fused sample-and-pack kernels (both in pack.hip): the same
 // (i, seed, stream) gives the same draw in both.
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll

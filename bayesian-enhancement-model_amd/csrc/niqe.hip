@@ -93,12 +93,6 @@ __global__ __launch_bounds__(256) void niqe_resize_w_kernel(const float* __restr
     out[i] = (float)acc * 255.f;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
-    return v;
-}
-
 // compute_feature of one block: the AGGD fit (estimate_aggd_param) of the block and of its four paired products with
 // np.roll(block, s) (wrapping inside the block), s in (0,1), (1,0), (1,1), (1,-1).  One workgroup per (block, scale, candidate);
 // blocks are numbered idx_w-major like niqe.py's loops.  alpha = gam[argmin((r_gam - rhatnorm)^2)] by a brute-force scan of the
@@ -211,8 +205,7 @@ __global__ __launch_bounds__(64) void niqe_mvg_kernel(const double* __restrict__
         clean[r] = ok;
         mine += ok;
     }
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) mine += __shfl_xor(mine, dd, BEM_WAVE);
+    mine = wave_sum(mine);
     if (t == 0) { ncl_s = mine; bad_s = 0; }
     __syncthreads();
     const int ncl = ncl_s;

@@ -4,6 +4,7 @@
 //   * x6, three bf16 limbs (pack_x6_*, bem_pack_pw_weight_x6*): (nsets, MT, KB, 3, 64) 16-byte vectors, the weight operand of the x6 kernels
 //     (pw_gemm_x6.hip, conv_x6.hip, gdmlp_x6.hip, ss2d_front_x6.hip, upfuse_x6.hip); the layout is described in the header of pw_gemm_x6.hip.
 //     sample_pack_x6_kernel and ebank_sample_kernel draw Bayesian weights (Philox, bem_common.h) and store them in that format.
+// The natural-order samplers of the same Philox stream (randn_kernel, bnn_sample_kernel) are here too: every Philox draw is in this file.
 #include "bem_common.h"
 #include "x6_common.h"
 
@@ -108,6 +109,37 @@ __global__ void sample_pack_x6_kernel(const float* __restrict__ mu, const float*
     sample_pack_x6_item(i, mu, rho, eps_in, Wp, M, K, MT, KB, seed, stream_id, sigma_given);
 }
 
+// ---------------------------------------------------------------- Bayesian sampling ----------
+// stream_add (all three samplers): an optional device-resident addend of the Philox stream id -- the per-iteration part of the id
+// ([forward epoch] << 20, see SampleCtx.next_stream) kept in HBM so that a captured HIP graph of the step draws fresh numbers on
+// every replay; NULL = the id is complete as passed.
+__global__ void randn_kernel(float* __restrict__ out, int64_t total, uint64_t seed, uint64_t stream_id, const uint64_t* __restrict__ stream_add) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (stream_add) stream_id += stream_add[0];
+    if (i < total) out[i] = philox_normal(i, seed, stream_id);
+}
+
+// one thread = four consecutive elements = one Philox counter block
+__global__ void bnn_sample_kernel(const float* __restrict__ mu, const float* __restrict__ rho,
+                                  const float* __restrict__ eps_in, float* __restrict__ out, int64_t n, int64_t total,
+                                  uint64_t seed, uint64_t stream_id, const uint64_t* __restrict__ stream_add) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i0 = 4 * j;
+    if (i0 >= total) return;
+    if (stream_add) stream_id += stream_add[0];
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!eps_in) philox_normal4(j, seed, stream_id, z);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t i = i0 + q;
+        if (i < total) {
+            const int64_t e = i % n;
+            const float eps = eps_in ? eps_in[i] : z[q];
+            out[i] = mu[e] + log1pf(expf(rho[e])) * eps;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // All Bayesian tensors of a net drawn for a stochastic (eval) forward in ONE launch: the Stage-I net of the Monte-Carlo loop has 60
 // Bayesian leaves / 90 tensors, i.e. 90 sampling launches per forward that sit between the layers' own kernels on planes of H/16 x W/16
@@ -159,6 +191,23 @@ extern "C" int bem_pack_pw_weight_f32(const float* W, float* Wp, int nsets, int 
     dim3 grid((unsigned)cdiv64((int64_t)MT * KS * 64, 256), nsets);
     pack_pw_weight_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(W, Wp, M, K, MT, KS);
     return bem_check_launch("pack_pw_weight");
+}
+
+extern "C" int bem_bnn_sample_f32(const float* mu, const float* rho, const float* eps_in, float* out, int nsets,
+                                  int64_t n, uint64_t seed, uint64_t stream_id, const uint64_t* stream_add, void* stream) {
+    BEM_REQUIRE(mu && rho && out, "bnn_sample: null tensor");
+    BEM_REQUIRE(nsets >= 0 && n >= 0, "bnn_sample: bad shape");
+    const int64_t total = (int64_t)nsets * n;
+    if (total == 0) return BEM_OK;
+    bnn_sample_kernel<<<GRID1D(cdiv64(total, 4)), 256, 0, (hipStream_t)stream>>>(mu, rho, eps_in, out, n, total, seed, stream_id, stream_add);
+    return bem_check_launch("bnn_sample");
+}
+
+extern "C" int bem_randn_f32(float* out, int64_t n, uint64_t seed, uint64_t stream_id, const uint64_t* stream_add, void* stream) {
+    BEM_REQUIRE(out && n >= 0, "randn: bad arguments");
+    if (n == 0) return BEM_OK;
+    randn_kernel<<<GRID1D(n), 256, 0, (hipStream_t)stream>>>(out, n, seed, stream_id, stream_add);
+    return bem_check_launch("randn");
 }
 
 extern "C" int bem_bnn_ebank_sample_f32(const void* segs, const void* blks, int nblk, float* arena, uint64_t seed, uint64_t stream_base,

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(NT) void selective_scan_bwd_kernel(
                     atomicAdd(dC + bc + t0 + e, dy[e] * h[e]);
                 }
             }
-            accA = block_reduce_sum<NT>(accA, red);
+            accA = block_sum<NT / BEM_WAVE>(accA, red);
             if (threadIdx.x == 0) atomicAdd(dA + (int64_t)d * dstate + n, accA);
         }
         float dd[E];
@@ -208,8 +208,8 @@ __global__ __launch_bounds__(NT) void selective_scan_bwd_kernel(
         store_row<E>(ddelta + row, t0, L, vec, dd);
         __syncthreads();
     }
-    accD = block_reduce_sum<NT>(accD, red);
-    accBias = block_reduce_sum<NT>(accBias, red);
+    accD = block_sum<NT / BEM_WAVE>(accD, red);
+    accBias = block_sum<NT / BEM_WAVE>(accBias, red);
     if (threadIdx.x == 0) {
         if (dD) atomicAdd(dD + d, accD);
         if (ddbias) atomicAdd(ddbias + d, accBias);

@@ -125,9 +125,9 @@ __device__ __forceinline__ void ss2d_dir_bwd(const float* __restrict__ xr, const
                 atomicAdd(dxd + (int64_t)(R + 1) * L + t0 + e, dCv[e]);
             }
     }
-    accA = block_reduce_sum<NT>(accA, red);
-    accD = block_reduce_sum<NT>(accD, red);
-    accB = block_reduce_sum<NT>(accB, red);
+    accA = block_sum<NT / BEM_WAVE>(accA, red);
+    accD = block_sum<NT / BEM_WAVE>(accD, red);
+    accB = block_sum<NT / BEM_WAVE>(accB, red);
     __syncthreads();
     if (threadIdx.x == 0) {
         atomicAdd(dAlog + p.kc, accA * Ak);
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(NT) void ss2d_scan_bwd_rows_kernel(
             for (int q = 0; q < NP; ++q) {
                 float v = pacc[ch][q];
 #pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
+                for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);      // not wave_sum(): profiles/small_kernels_bench.txt
                 if (lane == 0) redp[wave][ch * NP + q] = v;
             }
         __syncthreads();
@@ -472,7 +472,8 @@ extern "C" int bem_ss2d_scan_bwd_f32(const float* x0, const float* x1, const flo
     if (B == 0 || L == 0) return BEM_OK;
     hipStream_t s = a.s;
     const size_t nd = sizeof(float) * (size_t)B * 2 * (R + 2) * L;
-    if (hipMemsetAsync(dxd0, 0, nd, s) != hipSuccess || hipMemsetAsync(dxd1, 0, nd, s) != hipSuccess) return bem_check_launch("ss2d_scan_bwd memset");
+    BEM_ZERO(dxd0, nd, s, "ss2d_scan_bwd");
+    BEM_ZERO(dxd1, nd, s, "ss2d_scan_bwd");
     static const bool fast = !(getenv("BEM_SCAN_BWD_ROWS") && atoi(getenv("BEM_SCAN_BWD_ROWS")) == 0);
     if (fast) {
         // whole-row channel-blocked forms for the plane sizes / dt_ranks of the shipped configuration (n_feat 40: R = 3 / 5 / 10)

@@ -142,12 +142,6 @@ __device__ __forceinline__ void store4(float* p, const float (&v)[E]) {
     for (int i = 0; i < E; i += 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Fused SS2D scans: a launch covers 2 orientations x Bn images x n units (channels, or groups of CB channels), unit fastest.
 // ------------------------------------------------------------------------------------------------
@@ -202,20 +196,6 @@ __device__ __forceinline__ void ss2d_coeffs(const float* __restrict__ xd, const 
                                             int64_t t0, int L, int R, bool vec, float (&a)[E], float (&b)[E], float (&Cv)[E]) {
     float Bv[E], dl[E], z[E];
     ss2d_coeffs<E>(xd, wdt, dtb, Ak, x, t0, L, R, vec, a, b, Bv, Cv, dl, z);
-}
-
-template <int NT>
-__device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, BEM_WAVE);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < NT / BEM_WAVE; ++w) s += sh[w];
-    return s;
 }
 
 template <int CTRL, int ROWMASK>

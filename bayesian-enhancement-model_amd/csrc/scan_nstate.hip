@@ -429,6 +429,7 @@ extern "C" int bem_ss2d_scan_n_bwd_f32(const float* x0, const float* x1, const f
                 (long long)bem_ss2d_scan_n_bwd_ws_elems(B, C, L, N));
     if (B == 0 || L == 0) return BEM_OK;
     const size_t nd = sizeof(float) * (size_t)B * 2 * (R + 2 * N) * L;
-    if (hipMemsetAsync(dxd0, 0, nd, a.s) != hipSuccess || hipMemsetAsync(dxd1, 0, nd, a.s) != hipSuccess) return bem_check_launch("ss2d_scan_n_bwd memset");
+    BEM_ZERO(dxd0, nd, a.s, "ss2d_scan_n_bwd");
+    BEM_ZERO(dxd1, nd, a.s, "ss2d_scan_n_bwd");
     return N <= 4 ? launch_bwd<4>(a) : N <= 8 ? launch_bwd<8>(a) : launch_bwd<16>(a);
 }

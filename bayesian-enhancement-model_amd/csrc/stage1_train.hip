@@ -15,16 +15,6 @@ namespace {
 
 constexpr int NT = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 __device__ __forceinline__ float softplus_ref(float r) { return log1pf(expf(r)); }     // torch.log1p(torch.exp(rho)), conv.py:101
 __device__ __forceinline__ float sigmoid_ref(float r) { return 1.f / (1.f + expf(-r)); }
 
@@ -46,7 +36,7 @@ __global__ void kl_kernel(const float* __restrict__ mu, const float* __restrict_
         const float sq = softplus_ref(rho[i]), sp = softplus_ref(prho[i]), d = mu[i] - pmu[i];
         acc += logf(sp) - logf(sq) + (sq * sq + d * d) / (2.f * sp * sp) - 0.5f;
     }
-    const float s = block_sum(acc, sh);
+    const float s = block_sum<NT / BEM_WAVE>(acc, sh);
     if (threadIdx.x == 0) atomicAdd(out, s * inv_n);
 }
 
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(NT) void bank_kl_kernel(const bank_seg* __restrict_
             acc += logf(sp) - logf(sq) + (sq * sq + d * d) / (2.f * sp * sp) - 0.5f;
         }
     }
-    const float s = block_sum(acc, sh);
+    const float s = block_sum<NT / BEM_WAVE>(acc, sh);
     if (threadIdx.x == 0) atomicAdd(out, s * sg.inv_n);
 }
 
@@ -186,11 +176,11 @@ __global__ void mask_token_bwd_kernel(const float* __restrict__ dout, const floa
         dfea[i] = d * (1.f - w);
         acc += d * w;
     }
-    const float s = block_sum(acc, sh);
+    const float s = block_sum<NT / BEM_WAVE>(acc, sh);
     if (threadIdx.x == 0) atomicAdd(dtoken + c, s);
 }
 
-// inverse gather of space_to_depth_kernel (elementwise.hip): dx (B,C,H,W)[2y+dy][2x+dx] = dy4 (B,4C,H/2,W/2)[(dy + 2 dx) C + c][y][x]
+// inverse gather of space_to_depth_kernel (layout.hip): dx (B,C,H,W)[2y+dy][2x+dx] = dy4 (B,4C,H/2,W/2)[(dy + 2 dx) C + c][y][x]
 __global__ void depth_to_space_kernel(const float* __restrict__ d4, float* __restrict__ dx, int C, int H, int W, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= total) return;
@@ -220,11 +210,11 @@ __global__ void prelu_bwd_kernel(const float* __restrict__ x, const float* __res
         dx[i] = v >= 0.f ? d : a * d;
         acc += v >= 0.f ? 0.f : d * v;
     }
-    const float s = block_sum(acc, sh);
+    const float s = block_sum<NT / BEM_WAVE>(acc, sh);
     if (threadIdx.x == 0) atomicAdd(dslope, s);
 }
 
-// adjoint of bilinear_up_kernel (elementwise.hip): every output pixel hands its gradient to the four input pixels it read
+// adjoint of bilinear_up_kernel (layout.hip): every output pixel hands its gradient to the four input pixels it read
 __global__ void bilinear_up_bwd_kernel(const float* __restrict__ dout, float* __restrict__ dx, int C, int H, int W, int s, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= total) return;
@@ -385,7 +375,7 @@ extern "C" int bem_bilinear_up_bwd_f32(const float* dout, float* dx, int B, int 
     const int64_t total = (int64_t)B * C * H * W * s * s;
     if (total == 0) return BEM_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * C * H * W, st) != hipSuccess) return bem_check_launch("bilinear_up_bwd memset");
+    BEM_ZERO(dx, sizeof(float) * (size_t)B * C * H * W, st, "bilinear_up_bwd");
     bilinear_up_bwd_kernel<<<(unsigned)((total + NT - 1) / NT), NT, 0, st>>>(dout, dx, C, H, W, s, total);
     return bem_check_launch("bilinear_up_bwd");
 }

@@ -19,12 +19,6 @@ constexpr int UQ_NRG = 511, UQ_NYB = 1021;
 constexpr int UQ_CL = 0, UQ_CRG = 256, UQ_CYB = UQ_CRG + UQ_NRG, UQ_CMAX = UQ_CYB + UQ_NYB, UQ_NCNT = UQ_CMAX + 4;
 constexpr int UQ_NLAB = 256 + 3072 + 9;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, BEM_WAVE);
-    return v;
-}
-
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 __device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
 
@@ -142,8 +136,7 @@ __global__ __launch_bounds__(256) void uiqm_sobel_max_kernel(const uint8_t* __re
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         int m = p < np_ ? sobel_m2(rs + ((int64_t)b * 3 + c) * np_, Hr, (int)(p / UQ_W), (int)(p % UQ_W)) : 0;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d, BEM_WAVE));
+        m = wave_max(m);
         if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&cnt[(int64_t)b * UQ_NCNT + UQ_CMAX + c], m);
     }
 }
@@ -191,15 +184,9 @@ __global__ __launch_bounds__(256) void uiqm_blocks_kernel(const uint8_t* __restr
         }
     }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], d, BEM_WAVE));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], d, BEM_WAVE));
-        }
-        umn = min(umn, __shfl_xor(umn, d, BEM_WAVE));
-        umx = max(umx, __shfl_xor(umx, d, BEM_WAVE));
-    }
+    for (int c = 0; c < 3; ++c) { mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); }
+    umn = wave_min(umn);
+    umx = wave_max(umx);
     if (lane != 0) return;
     const float w = (float)(2.0 / (double)nb);
 #pragma unroll

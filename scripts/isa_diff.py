@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel ISA comparison of two csrc trees (a refactor must leave the machine code of the kernels it does not mean to change alone).
 
-  python scripts/isa_diff.py <parent csrc dir> <changed csrc dir> [file.hip ...]      default: every *.hip of the changed tree
+  python scripts/isa_diff.py <parent csrc dir> <changed csrc dir> [file.hip ...]      default: every *.hip of either tree
   ISA_DIFF_SHOW=<text>   also print a unified diff of the instruction streams of the DIFF kernels whose name contains <text>
 
 Both sides are compiled with isa_audit.compile_to_isa (the Makefile's flags).  Per kernel: demangled name (without its parameter list), SAME / DIFF / NEW / GONE,
 and instruction count, VGPRs and scratch bytes of the parent -> the change.  Two kernels are SAME when their instruction streams are equal
 after comments, labels and assembler directives are dropped (branch targets are compared by their number within the function).
-Exit code 1 when any kernel is not SAME.
+A kernel missing from the same-named file is looked up by name in the other files of that tree: a kernel that only moved prints
+SAME with both file names.  The lookup goes by the demangled name alone (kernels sit in anonymous namespaces) and takes the first file that has it:
+a new kernel that shares its name with one elsewhere in the tree is compared with that one, not listed as NEW.  Exit code 1 when any kernel is not SAME.
 """
 import concurrent.futures
 import difflib
@@ -48,18 +50,24 @@ def main():
     if len(sys.argv) < 3:
         print(__doc__); return 2
     pdir, cdir = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])
-    files = [os.path.basename(f) for f in sys.argv[3:]] or sorted(os.path.basename(f) for f in glob.glob(os.path.join(cdir, "*.hip")))
-    jobs = [os.path.join(d, f) for f in files for d in (pdir, cdir)]
+    both = lambda pat: sorted({os.path.basename(f) for d in (pdir, cdir) for f in glob.glob(os.path.join(d, pat))})
+    files = [os.path.basename(f) for f in sys.argv[3:]] or both("*.hip")
+    jobs = [os.path.join(d, f) for f in files for d in (pdir, cdir) if os.path.exists(os.path.join(d, f))]
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
-        texts = list(ex.map(compile_to_isa, jobs))
+        texts = dict(zip(jobs, ex.map(compile_to_isa, jobs)))
+    old, new = ({f: kernels(texts.get(os.path.join(d, f), "")) for f in files} for d in (pdir, cdir))
+    where = lambda side, k: next((f for f in files if k in side[f]), None)      # a kernel that moved: looked up by name in the whole tree
     ndiff = total = 0
-    for i, f in enumerate(files):
-        old, new = kernels(texts[2 * i]), kernels(texts[2 * i + 1])
-        for k in sorted(set(old) | set(new)):
-            o, n = old.get(k), new.get(k)
+    for f in files:
+        for k in sorted(set(old[f]) | set(new[f])):
+            fo, fn = (f if k in old[f] else where(old, k)), (f if k in new[f] else where(new, k))
+            if k not in new[f] and fn:
+                continue                                                        # listed under the file that has it now
+            o, n = old[fo][k] if fo else None, new[fn][k] if fn else None
             tag = "GONE" if n is None else "NEW " if o is None else "SAME" if o[0] == n[0] else "DIFF"
             fmt = lambda s: "     -     -    -" if s is None else f"{len(s[0]):6d} {s[1]:5d} {s[2]:4d}"
-            print(f"{f:16s} {tag}  instr/vgpr/scratch {fmt(o)}  -> {fmt(n)}  {k.split('(')[0]}")
+            name = f if fo in (None, f) else f"{fo} -> {f}"
+            print(f"{name:16s} {tag}  instr/vgpr/scratch {fmt(o)}  -> {fmt(n)}  {k.split('(')[0]}")
             show = os.environ.get("ISA_DIFF_SHOW")
             if tag == "DIFF" and show and show in k:
                 print("\n".join(difflib.unified_diff(o[0], n[0], "parent", "change", n=2, lineterm="")))

@@ -1,4 +1,4 @@
-"""Plain-torch references of the eval step's entry and exit kernels in csrc/elementwise.hip (not collected by pytest), one function per
+"""Plain-torch references of the eval step's entry and exit kernels in csrc/layout.hip and csrc/selection.hip (not collected by pytest), one function per
 entry point, written from that file's comments and the restatements in oracle/bem_oracle.py (which carry the file:line citations).  Nothing
 here imports bem.
 

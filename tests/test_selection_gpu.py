@@ -1,4 +1,4 @@
-"""The eval step's entry and exit kernels of csrc/elementwise.hip (pad_reflect, resize_down, bilinear_up, plane_mean, cond_postproc; the
+"""The eval step's entry and exit kernels of csrc/layout.hip and csrc/selection.hip (pad_reflect, resize_down, bilinear_up, plane_mean, cond_postproc; the
 three candidate_finalize grids, select_best / select_scores with both gathers, ssim, mc_mean + mc_rescale) at op level against the float64
 references of tests/selection_ref.py, on the shape tables there: the smallest shapes at which each chunked, capped or strided loop makes a
 second, ragged pass, and N = 64.
