@@ -1,15 +1,22 @@
 """build_loss (basicsr/losses/__init__.py) for the losses of the hot path's training step.
 
-Only ``L1Loss`` is on the path (PerceptualLoss needs VGG19 weights that are not available offline);
-it runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn)."""
+``L1Loss`` runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn).  ``PerceptualLoss``
+(VGG19 features, criterion l1) is bem.percep's module: one autograd node of HIP kernels (bem.autograd.PerceptualFn); its weights are
+read from a torchvision state dict on disk (bem.percep.weights_path), never fetched."""
 from copy import deepcopy
 
 import torch.nn as nn
 
 from basicsr.utils.registry import LOSS_REGISTRY
+from basicsr.utils.registry import ARCH_REGISTRY
 from bem import autograd as _ag
+from bem.percep import PerceptualLoss, VGGFeatureExtractor
 
-__all__ = ["build_loss", "L1Loss"]
+__all__ = ["build_loss", "L1Loss", "PerceptualLoss", "VGGFeatureExtractor"]
+
+LOSS_REGISTRY.register(PerceptualLoss)
+if "VGGFeatureExtractor" not in ARCH_REGISTRY:
+    ARCH_REGISTRY.register(VGGFeatureExtractor)                # basicsr/archs/vgg_arch.py:54
 
 
 @LOSS_REGISTRY.register()
@@ -31,7 +38,4 @@ class L1Loss(nn.Module):
 def build_loss(opt):
     opt = deepcopy(opt)
     loss_type = opt.pop("type")
-    if loss_type == "PerceptualLoss":
-        raise NotImplementedError("PerceptualLoss needs torchvision's pretrained VGG19 weights (vgg_arch.py:103-108), which cannot be "
-                                  "fetched in this environment; remove `perceptual_opt` to train with the pixel loss only")
     return LOSS_REGISTRY.get(loss_type)(**opt)

@@ -40,8 +40,12 @@ class ConditionGenerator(BaseModel):
         if self.ema_decay > 0:
             raise NotImplementedError("ConditionGenerator: ema_decay > 0 (a second, averaged copy of the net) is not used by the shipped option files")
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
-        self.cri_perceptual = build_loss(train_opt["perceptual_opt"]).to(self.device) if train_opt.get("perceptual_opt") else None
-        if self.cri_pix is None and self.cri_perceptual is None:
+        if train_opt.get("perceptual_opt"):
+            raise NotImplementedError("ConditionGenerator: perceptual_opt is not available for Stage I: its predictions are 8x8 planes, below what "
+                                      "VGG19's deeper layers (conv5_4 needs 16x16) can take, and its training step is a captured graph; "
+                                      "remove `perceptual_opt` (the Stage-I option files of the reference train on the pixel loss)")
+        self.cri_perceptual = None
+        if self.cri_pix is None:
             raise ValueError("Both pixel and perceptual losses are None.")
         self.optimizers, self.schedulers = [], []
         self.setup_optimizers()

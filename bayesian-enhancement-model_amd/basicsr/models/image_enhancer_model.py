@@ -2,7 +2,8 @@
 (:64-128 settings, :130-148 feed_train_data, :165-216 optimize_parameters).
 
 The step runs entirely on the HIP path: condition upsample + concat (bem.ops), forward / backward (bem.autograd), global-norm clip +
-AdamW on one flat buffer (bem.train.BemAdamW), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
+AdamW on one flat buffer (bem.train.BemAdamW), the pixel loss and -- with ``train.perceptual_opt`` -- the VGG19 perceptual loss
+(bem.percep), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
 gradient norm come back as device scalars (read them when logging).  AMP (`use_amp`) is not offered: the path is f32."""
 from collections import OrderedDict
 
@@ -12,6 +13,7 @@ from basicsr.archs import build_network
 from basicsr.losses import build_loss
 from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
+from bem import autograd as ag
 from bem import ops
 from bem.train import BemAdamW
 
@@ -93,11 +95,24 @@ class ImageEnhancer(BaseModel):
         ops.bilinear_up(self.conds, s, dst=x, dst_c0=3)                # F.interpolate(conds, scale_factor=s, 'bilinear') into channels 3..5
         _, preds = self.net_g(x, mask=None)                           # the Decomp* archs ignore the MIM mask (DDWavelet_arch.py:301)
         loss_dict = OrderedDict()
-        if self.cri_pix is None:
-            raise NotImplementedError("ImageEnhancer: the pixel loss is the only loss on the HIP path")
-        l_total = l_pix = self.cri_pix(preds, self.gt)
-        w = self.opt["train"]["pixel_opt"].get("loss_weight", 1)
-        loss_dict["l_pix"] = l_pix.detach() if w == 1 else l_pix.detach() / w
+        if self.cri_perceptual is None:
+            l_total = l_pix = self.cri_pix(preds, self.gt)
+        else:
+            # :183-191: l_total = l_pix + l_percep; preds feeds both losses, its two gradients are summed by bem_add_f32 (ag.fork)
+            p_pix, p_per = ag.fork(preds) if self.cri_pix is not None else (None, preds)
+            l_percep, _ = self.cri_perceptual(p_per, self.gt)
+            l_pix = None if self.cri_pix is None else self.cri_pix(p_pix, self.gt)
+            if l_percep is None:                                         # perceptual_weight <= 0 (:186): the term is off
+                if l_pix is None:
+                    raise ValueError("Both pixel and perceptual losses are None.")
+                l_total = l_pix
+            else:
+                l_total = l_percep if l_pix is None else ag.AddFn.apply(l_pix, l_percep)
+        if l_pix is not None:
+            w = self.opt["train"]["pixel_opt"].get("loss_weight", 1)
+            loss_dict["l_pix"] = l_pix.detach() if w == 1 else l_pix.detach() / w
+        if self.cri_perceptual is not None and l_percep is not None:
+            loss_dict["l_percep"] = l_percep.detach() / self.cri_perceptual.perceptual_weight          # :188
         l_total.backward()
         self.sync_gradients(self.optimizer_g)
         mgn = self.opt["train"].get("max_grad_norm")

@@ -7,7 +7,7 @@
     save 'latest'.
 
   python basicsr/train.py --opt Options/DecompDualBranch2DDWavelet_4.yml --synthetic 64 [--auto_resume] [--debug]
-      [--force_yml train:total_iter=200 logger:save_checkpoint_freq=50] [--launcher pytorch]
+      [--force_yml train:total_iter=200 logger:save_checkpoint_freq=50] [--launcher pytorch] [--vgg_weights vgg19-dcbb9e9d.pth]
 
 What is the hot path runs on the HIP kernels (``optimize_parameters`` of the two model classes: forward, backward, clip, AdamW with no
 host synchronisation inside the step; validation through the inference kernels).  What is control plane stays small and host-side:

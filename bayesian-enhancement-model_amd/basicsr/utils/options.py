@@ -80,7 +80,9 @@ def parse_options(root_path, is_train=True, argv=None):
     """Command line + option file of the training / test drivers (basicsr/utils/options.py:99-200): same flags (--opt --launcher
     --auto_resume --debug --local_rank --force_yml), same distributed / seed / path / debug handling, returns (opt, args).
     ``--force_yml a:b=v`` walks the keys instead of exec'ing a string.  Two extra flags select the tensor dataset shim of basicsr.data
-    (the file-backed datasets are outside the HIP path): ``--synthetic N`` and ``--pairs file.pt``."""
+    (the file-backed datasets are outside the HIP path): ``--synthetic N`` and ``--pairs file.pt``; ``--vgg_weights PATH`` names the VGG19
+    state dict of ``train.perceptual_opt`` (bem.percep.weights_path) by SETTING the environment variable ``BEM_VGG19_WEIGHTS`` of this
+    process, which is not restored: a caller that parses options in-process and goes on afterwards saves and restores it itself."""
     import argparse
     import random
 
@@ -94,7 +96,12 @@ def parse_options(root_path, is_train=True, argv=None):
     p.add_argument("--force_yml", nargs="+", default=None, help="Force to update yml files. Examples: train:ema_decay=0.999")
     p.add_argument("--synthetic", type=int, default=0, help="train / validate on N seeded synthetic pairs (basicsr.data shim)")
     p.add_argument("--pairs", default=None, help="train / validate on a .pt file of dict(lq, gt) tensors (basicsr.data shim)")
+    p.add_argument("--vgg_weights", default=None, help="torchvision vgg19 state dict for train.perceptual_opt (sets BEM_VGG19_WEIGHTS; "
+                                                       "default experiments/pretrained_models/vgg19-dcbb9e9d.pth)")
     args = p.parse_args(argv)
+    if args.vgg_weights:
+        import os
+        os.environ["BEM_VGG19_WEIGHTS"] = os.path.abspath(args.vgg_weights)
     with open(args.opt, "r") as f:
         opt = yaml.load(f, Loader=ordered_yaml()[0])
     if args.launcher == "none":

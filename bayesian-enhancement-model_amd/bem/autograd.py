@@ -96,6 +96,115 @@ def l1_loss(pred, gt, weight=1.0):
     return L1LossFn.apply(pred, gt, float(weight))
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# VGG19 perceptual loss (basic_loss.py:198-222 over vgg_arch.py:141-161)
+# ------------------------------------------------------------------------------------------------------------------
+def _vgg_walk(vgg, x, keep=None, rows=None):
+    """The conv / ReLU / pool walk of ``vgg.names`` over the normalised batch x (N,8,H,W).  Returns {requested name: feature}; ``keep``
+    (a dict) receives the first ``rows`` batch rows of the post-ReLU output of every convolution whose ReLU is part of the walk, copied
+    out as soon as it exists (a view where the whole tensor is a requested relu* feature and stays alive anyway), so that the N-row
+    tensor itself is released once the next layer has read it.  A convolution carries its ReLU in its epilogue unless its own value is
+    requested: then the value before the ReLU is the feature and bem_relu_f32 continues the walk."""
+    names, want, w = vgg.names, set(vgg.layer_name_list), vgg.conv_operands()
+    feats = {}
+    for i, n in enumerate(names):
+        if n.startswith("conv"):
+            cw, bias, _ = w[n]
+            has_relu = i + 1 < len(names)
+            if n in want:
+                feats[n] = pre = ops.conv2d(x, cw, bias, relu=False)
+                x = ops.relu(pre) if has_relu else pre
+            else:
+                x = ops.conv2d(x, cw, bias, relu=True)
+            if has_relu and keep is not None:
+                keep[n] = x[:rows] if names[i + 1] in want else _rows(x, rows)
+        elif n.startswith("relu"):
+            if n in want:
+                feats[n] = x
+        else:
+            x = ops.maxpool2(x)
+    return feats
+
+
+def vgg_features(vgg, x):
+    """VGGFeatureExtractor.forward for one image batch (no gradient): {name: feature}."""
+    B = x.shape[0]
+    return _vgg_walk(vgg, ops.vgg_prep(x, x, vgg.use_input_norm, vgg.range_norm)[:B])
+
+
+class PerceptualFn(Function):
+    """percep_loss of PerceptualLoss.forward(pred, gt), criterion l1.  Forward: both images as one 2B-row batch through the walk, one
+    bem_l1_loss_f32 per requested layer between the two halves, the values summed on the device.  Backward: the pred half only, against
+    the frozen weights: no weight gradient, none for gt.  Saved: the post-ReLU activations of the pred rows (ReLU masks, pool argmax)
+    and the requested features."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mod):
+        vgg = mod.vgg
+        pred, gt = pred.contiguous(), gt.contiguous()
+        B = pred.shape[0]
+        need_bwd = ctx.needs_input_grad[0]
+        keep = {} if need_bwd else None
+        feats = _vgg_walk(vgg, ops.vgg_prep(pred, gt, vgg.use_input_norm, vgg.range_norm), keep, B)
+        total = None
+        for n, f in feats.items():
+            l = ops.l1_loss(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight))
+            total = l if total is None else ops.add(total, l)
+        if need_bwd:
+            ctx.mod, ctx.B = mod, B
+            ctx.feat_names, ctx.act_names = list(feats), list(keep)
+            ctx.save_for_backward(*feats.values(), *keep.values())
+        return total.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        mod, B = ctx.mod, ctx.B
+        vgg = mod.vgg
+        names, w = vgg.names, vgg.conv_operands()
+        nf = len(ctx.feat_names)
+        feats = dict(zip(ctx.feat_names, ctx.saved_tensors[:nf]))
+        acts = dict(zip(ctx.act_names, ctx.saved_tensors[nf:]))
+        gmul = g.reshape(1).contiguous().float()
+
+        def dfeat(n):
+            f = feats[n]
+            return ops.l1_loss_bwd(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight), gmul)
+
+        d, masked = None, False          # d: gradient at the output of layer i; masked: the mask of the ReLU it leaves is already in it
+        for i in range(len(names) - 1, -1, -1):
+            n = names[i]
+            if n.startswith("pool"):
+                d, masked = ops.relu_pool_bwd(acts["conv" + names[i - 1][4:]], d), True
+            elif n.startswith("relu"):
+                if n in feats:
+                    gf = dfeat(n)
+                    if d is None:
+                        d, masked = gf, False
+                    elif masked:
+                        d = ops.add(d, ops.relu_bwd(acts["conv" + n[4:]], gf, inplace=True))
+                    else:
+                        d = ops.add(d, gf)
+            else:
+                if d is not None and not masked:
+                    d = ops.relu_bwd(acts[n], d, inplace=True)       # d is this node's own tensor
+                if n in feats:
+                    gf = dfeat(n)
+                    d = gf if d is None else ops.add(d, gf)
+                d, masked = ops.conv2d(d, w[n][2], None), False
+        return ops.vgg_prep_bwd(d, B, vgg.use_input_norm, vgg.range_norm), None, None
+
+
+def _rows(t, B):
+    """The first B batch rows of a contiguous (N,C,H,W) tensor as a tensor of their own (bem_copy_channels_f32)."""
+    out = torch.empty((B,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+    ops.copy_channels(t[:B], out, 0)
+    return out
+
+
+def perceptual_loss(pred, gt, mod):
+    return PerceptualFn.apply(pred, gt.detach(), mod)          # basic_loss.py:210
+
+
 class IwtHamiltonFn(Function):
     @staticmethod
     def forward(ctx, q1w, q2w):

@@ -155,6 +155,12 @@ SIGNATURES = {
     "bem_fusion_head_bwd_f32": [P, I64, P, I64] + [P] * 11 + [I64, I, I, I, I, I, I, P],
     "bem_grad_sumsq_f32": [P, I64, P, P],
     "bem_adamw_step_f32": [P, P, P, P, I64, F, F, F, F, F, I, F, P, P, P, P],
+    "bem_vgg_prep_f32": [P, P, P, I, I, I, I, I, P],
+    "bem_vgg_prep_bwd_f32": [P, I64, P, I, I, I, I, I, P],
+    "bem_maxpool2_f32": [P, P, I64, I, I, P],
+    "bem_relu_pool_bwd_f32": [P, P, P, I64, I, I, P],
+    "bem_relu_bwd_f32": [P, P, P, I64, P],
+    "bem_relu_f32": [P, P, I64, P],
     "bem_last_error": [],
     "bem_abi_version": [],
 }

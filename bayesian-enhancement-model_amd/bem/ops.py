@@ -1603,6 +1603,74 @@ def add(a, b, alpha=1.0):
     return out
 
 
+# --------------------------------------------------------------------------- perceptual loss --
+# What runs between the convolutions of the VGG19 feature pass (percep.hip; bem.autograd.PerceptualFn is the caller).
+def vgg_prep(pred, gt, input_norm=True, range_norm=False):
+    """pred, gt (B,3,H,W) -> (2B,8,H,W): rows [0,B) pred, [B,2B) gt, channels 0..2 normalised (vgg_arch.py:150-153), 3..7 zero."""
+    _chk(pred, "pred"); _chk(gt, "gt")
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != gt.shape:
+        raise ValueError(f"vgg_prep: two (B,3,H,W) tensors of one shape required, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    B, _, H, W = pred.shape
+    xn = torch.empty(2 * B, 8, H, W, device=pred.device, dtype=torch.float32)
+    check(lib().bem_vgg_prep_f32(_p(pred), _p(gt), _p(xn), B, H, W, int(bool(input_norm)), int(bool(range_norm)), _stream()), "vgg_prep")
+    return xn
+
+
+def vgg_prep_bwd(dxn, B, input_norm=True, range_norm=False):
+    """dpred (B,3,H,W) from channels 0..2 of the first B rows of dxn (rows >= B, C >= 3, H, W)."""
+    _chk(dxn, "dxn")
+    if dxn.dim() != 4 or dxn.shape[1] < 3 or not 0 <= B <= dxn.shape[0]:
+        raise ValueError(f"vgg_prep_bwd: dxn {tuple(dxn.shape)} does not hold {B} rows of three planes")
+    _, C, H, W = dxn.shape
+    dpred = torch.empty(B, 3, H, W, device=dxn.device, dtype=torch.float32)
+    check(lib().bem_vgg_prep_bwd_f32(_p(dxn), C * H * W, _p(dpred), B, H, W, int(bool(input_norm)), int(bool(range_norm)), _stream()),
+          "vgg_prep_bwd")
+    return dpred
+
+
+def _pool_planes(op, x):
+    if x.dim() < 2 or x.shape[-2] < 2 or x.shape[-1] < 2:
+        raise ValueError(f"{op}: planes of at least 2 x 2 required, got {tuple(x.shape)}")
+    return _prod(x.shape[:-2]), x.shape[-2], x.shape[-1]
+
+
+def maxpool2(x):
+    """nn.MaxPool2d(2, 2) over the last two dimensions (floor: an odd last row / column is dropped)."""
+    _chk(x, "x")
+    P, H, W = _pool_planes("maxpool2", x)
+    out = torch.empty(tuple(x.shape[:-2]) + (H // 2, W // 2), device=x.device, dtype=torch.float32)
+    check(lib().bem_maxpool2_f32(_p(x), _p(out), P, H, W, _stream()), "maxpool2")
+    return out
+
+
+def relu_pool_bwd(y, dpool):
+    """Gradient of maxpool2(y) with respect to the input of the ReLU that made y: dpool at each window's first maximum where y > 0."""
+    _chk(y, "y"); _chk(dpool, "dpool")
+    P, H, W = _pool_planes("relu_pool_bwd", y)
+    if tuple(dpool.shape) != tuple(y.shape[:-2]) + (H // 2, W // 2):
+        raise ValueError(f"relu_pool_bwd: dpool {tuple(dpool.shape)} is not the pooled shape of y {tuple(y.shape)}")
+    dy = torch.empty_like(y)
+    check(lib().bem_relu_pool_bwd_f32(_p(y), _p(dpool), _p(dy), P, H, W, _stream()), "relu_pool_bwd")
+    return dy
+
+
+def relu_bwd(y, dy, inplace=False):
+    """dy * (y > 0); ``inplace`` writes into dy."""
+    _chk(y, "y"); _chk(dy, "dy")
+    if y.shape != dy.shape:
+        raise ValueError("relu_bwd: shapes differ")
+    out = dy if inplace else torch.empty_like(dy)
+    check(lib().bem_relu_bwd_f32(_p(y), _p(dy), _p(out), y.numel(), _stream()), "relu_bwd")
+    return out
+
+
+def relu(x):
+    _chk(x, "x")
+    out = torch.empty_like(x)
+    check(lib().bem_relu_f32(_p(x), _p(out), x.numel(), _stream()), "relu")
+    return out
+
+
 def _ln_bwd_cost(x1, x2, dres, want_n, **_):
     return 4.0 * x1.numel() * (3 + (x2 is not None) + (dres is not None) + bool(want_n)), 0.0
 

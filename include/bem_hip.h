@@ -593,6 +593,31 @@ int bem_prelu_bwd_f32(const float* x, const float* slope, const float* dout, flo
  * dout (B,C,H*s,W*s) -> dx (B,C,H,W), zeroed by the call. */
 int bem_bilinear_up_bwd_f32(const float* dout, float* dx, int B, int C, int H, int W, int s, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * VGG19 perceptual loss (basicsr/losses/basic_loss.py:146-238): the kernels between its convolutions (csrc/percep.hip).
+ * All tensors f32, channel-planar, contiguous; every kernel is one pass and writes each output element itself (no memset).
+ * ------------------------------------------------------------------------------------------- */
+
+/* Input normalisation of VGGFeatureExtractor.forward (basicsr/archs/vgg_arch.py:150-153) for both images at once:
+ * pred, gt (B,3,H,W) -> xn (2B,8,H,W), rows [0,B) from pred and [B,2B) from gt; channels 0..2 = (x - mean) / std (input_norm; a true
+ * division) after x = (x + 1) / 2 (range_norm), channels 3..7 zero (conv1_1 with its weight zero-padded to 8 input channels). */
+int bem_vgg_prep_f32(const float* pred, const float* gt, float* xn, int B, int H, int W, int input_norm, int range_norm, void* stream);
+/* Its adjoint for the pred rows: dpred (B,3,H,W) = dxn[:, :3] / std (/ 2 under range_norm); dxn_bstride = elements between rows of dxn. */
+int bem_vgg_prep_bwd_f32(const float* dxn, int64_t dxn_bstride, float* dpred, int B, int H, int W, int input_norm, int range_norm,
+                         void* stream);
+
+/* nn.MaxPool2d(kernel_size=2, stride=2) (vgg_arch.py:120): x (planes,H,W) -> out (planes,H/2,W/2), floor: an odd last row / column is
+ * dropped.  H, W >= 2. */
+int bem_maxpool2_f32(const float* x, float* out, int64_t planes, int H, int W, void* stream);
+/* Backward of pool(y) with y = relu(.) and of that ReLU (autograd of vgg_arch.py:156-157 over a 'relu*', 'pool*' pair): dy (planes,H,W) =
+ * dpool (planes,H/2,W/2) of the window at its first maximum in row-major order (torch's rule) where y > 0 there, zero elsewhere -- a
+ * dropped odd row / column included. */
+int bem_relu_pool_bwd_f32(const float* y, const float* dpool, float* dy, int64_t planes, int H, int W, void* stream);
+/* Backward of nn.ReLU (vgg_arch.py:156-157 over a 'relu*' entry) on its output y: out = dy * (y > 0); out may be dy. */
+int bem_relu_bwd_f32(const float* y, const float* dy, float* out, int64_t n, void* stream);
+/* nn.ReLU (the same lines): needed where a requested 'conv*' feature is kept before its ReLU and the walk goes on; out may be x. */
+int bem_relu_f32(const float* x, float* out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
