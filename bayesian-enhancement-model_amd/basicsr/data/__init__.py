@@ -10,12 +10,16 @@ resize), ``mask`` (B,S/16,S/16) for the Stage-I MIM token, ``lq_path``.  Two sou
 
 Random crops of ``gt_size``, optional flips (``geometric_augs``), the condition planes and the mask are made on the device by the
 HIP kernels of bem.ops / torch index arithmetic on the batch -- no worker processes.  A reference option file that names
-``Dataset_PairedImage_Mask`` is redirected here only when the driver is given ``--synthetic`` or ``--pairs``; otherwise it raises."""
+``Dataset_PairedImage_Mask`` is redirected here only when the driver is given ``--synthetic`` or ``--pairs``; otherwise it trains
+from its ``dataroot_gt`` / ``dataroot_lq`` folders through ``paired_image_dataset`` (device-resident uint8 store, one
+``bem.ops.batch_assemble`` launch per step)."""
 import math
 
 import torch
 
-__all__ = ["build_dataset", "build_dataloader", "TensorPairDataset", "TensorBatchLoader"]
+from .paired_image_dataset import DATASET_TYPE, PairedImageBatchLoader, PairedImageMaskDataset, pad_and_condition
+
+__all__ = ["build_dataset", "build_dataloader", "TensorPairDataset", "TensorBatchLoader", "PairedImageMaskDataset", "PairedImageBatchLoader"]
 
 
 class TensorPairDataset:
@@ -60,8 +64,7 @@ class TensorBatchLoader:
         return math.ceil(n / (self.batch * self.world)) if self.train else n
 
     def __iter__(self):
-        from bem import ops
-        g = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch * 101 + self.rank)
+        g =torch.Generator().manual_seed(self.seed * 1000003 + self.epoch * 101 + self.rank)
         N = len(self.dataset)
         s = int(self.cond.get("scale_down", 16))
         if self.train:
@@ -86,15 +89,9 @@ class TensorBatchLoader:
                 if k & 2:
                     lq, gt = lq.flip(-2), gt.flip(-2)
             lq, gt = lq.contiguous(), gt.contiguous()
-            f = 4 * s
-            hp, wp = lq.shape[-2] % f, lq.shape[-1] % f
-            if hp or wp:                               # validation on whole images: pad like eval.py:146-153 before the condition planes
-                Hp, Wp = lq.shape[-2] + (f - hp) % f, lq.shape[-1] + (f - wp) % f
-                lqp, gtp = ops.pad_reflect(lq, Hp, Wp), ops.pad_reflect(gt, Hp, Wp)
-            else:
-                lqp, gtp = lq, gt
-            out = dict(lq=lqp, gt=gtp, lq_down=ops.resize_down(lqp, s), gt_down=ops.resize_down(gtp, s), crop_hw=tuple(lq.shape[-2:]),
-                       lq_path=[f"tensor_{int(j):05d}" for j in idx])
+            out = pad_and_condition(lq, gt, s)          # validation on whole images: pad like eval.py:146-153 before the condition planes
+            lqp = out["lq"]
+            out["lq_path"] = [f"tensor_{int(j):05d}" for j in idx]
             if self.train and self.opt.get("mask_ratio") is not None:
                 hd, wd = lqp.shape[-2] // s, lqp.shape[-1] // s
                 out["mask"] = (torch.rand(lq.shape[0], hd, wd, generator=g) < float(self.opt["mask_ratio"])).float().to(self.device)
@@ -102,9 +99,13 @@ class TensorBatchLoader:
 
 
 def build_dataset(dataset_opt):
+    if dataset_opt.get("type") == DATASET_TYPE:
+        return PairedImageMaskDataset(dataset_opt)
     return TensorPairDataset(dataset_opt)
 
 
 def build_dataloader(dataset, dataset_opt, num_gpu=1, dist=False, sampler=None, seed=None, device="cuda", rank=0, world=1, train=None):
     train = dataset_opt.get("phase", "train") == "train" if train is None else train
+    if isinstance(dataset, PairedImageMaskDataset):
+        return PairedImageBatchLoader(dataset, dataset_opt, device, seed=seed, rank=rank, world=world, train=train)
     return TensorBatchLoader(dataset, dataset_opt, device, seed=seed, rank=rank, world=world, train=train)

@@ -11,9 +11,10 @@
 
 What is the hot path runs on the HIP kernels (``optimize_parameters`` of the two model classes: forward, backward, clip, AdamW with no
 host synchronisation inside the step; validation through the inference kernels).  What is control plane stays small and host-side:
-the message logger is ``print`` (TensorBoard / wandb are not dependencies), the datasets are the tensor shim of ``basicsr.data`` (the
-file-backed datasets are host I/O outside the path: pass ``--synthetic N`` or ``--pairs file.pt``), there are no prefetcher threads
-(the batches already live on the device).  ``--launcher pytorch`` (under ``python -m torch.distributed.run``) trains data-parallel:
+the message logger is ``print`` (TensorBoard / wandb are not dependencies), the datasets live on the device: without a flag the
+``Dataset_PairedImage_Mask`` folders of the option file, decoded once into a uint8 store and assembled by one kernel launch per step
+(``basicsr.data.paired_image_dataset``); with ``--synthetic N`` or ``--pairs file.pt`` the tensor shim of ``basicsr.data``.  There are
+no prefetcher threads (the batches already live on the device).  ``--launcher pytorch`` (under ``python -m torch.distributed.run``) trains data-parallel:
 one process per GPU, the flat gradient buffer averaged by one RCCL all-reduce per step (bem.train.BemAdamW.all_reduce_grads)."""
 import datetime
 import math
@@ -42,12 +43,14 @@ def create_train_val_dataloader(opt, device):
         dataset_opt["model_type"] = opt["model_type"]
         if phase == "train":
             ratio = dataset_opt.get("dataset_enlarge_ratio", 1)
-            if opt["model_type"] == "ConditionGenerator":
+            folders = dataset_opt.get("type") == "Dataset_PairedImage_Mask"     # emits a mask only under its own ``mim:`` block
+            if opt["model_type"] == "ConditionGenerator" and not folders:
                 dataset_opt.setdefault("mask_ratio", 0.4)          # Dataset_PairedImage_Mask's MIM mask (paired_image_dataset.py:374-383)
             train_set = build_dataset(dataset_opt)
             train_loader = build_dataloader(train_set, dataset_opt, num_gpu=opt["num_gpu"], dist=opt["dist"], seed=opt["manual_seed"],
                                             device=device, rank=opt["rank"], world=opt["world_size"], train=True)
-            per_epoch = math.ceil(len(train_set) * ratio / (dataset_opt["batch_size_per_gpu"] * opt["world_size"]))
+            # the folder loader drops a partial last batch: its len() is what an epoch yields
+            per_epoch = len(train_loader) if folders else math.ceil(len(train_set) * ratio / (dataset_opt["batch_size_per_gpu"] * opt["world_size"]))
             total_iters = int(opt["train"]["total_iter"])
             total_epochs = math.ceil(total_iters / max(per_epoch, 1))
             print(f"Training statistics:\n\tNumber of train images: {len(train_set)}\n\tDataset enlarge ratio: {ratio}"

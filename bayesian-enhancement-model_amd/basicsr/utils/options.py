@@ -80,7 +80,7 @@ def parse_options(root_path, is_train=True, argv=None):
     """Command line + option file of the training / test drivers (basicsr/utils/options.py:99-200): same flags (--opt --launcher
     --auto_resume --debug --local_rank --force_yml), same distributed / seed / path / debug handling, returns (opt, args).
     ``--force_yml a:b=v`` walks the keys instead of exec'ing a string.  Two extra flags select the tensor dataset shim of basicsr.data
-    (the file-backed datasets are outside the HIP path): ``--synthetic N`` and ``--pairs file.pt``; ``--vgg_weights PATH`` names the VGG19
+    (without them a ``Dataset_PairedImage_Mask`` option file trains from its image folders): ``--synthetic N`` and ``--pairs file.pt``; ``--vgg_weights PATH`` names the VGG19
     state dict of ``train.perceptual_opt`` (bem.percep.weights_path) by SETTING the environment variable ``BEM_VGG19_WEIGHTS`` of this
     process, which is not restored: a caller that parses options in-process and goes on afterwards saves and restores it itself."""
     import argparse

@@ -161,6 +161,7 @@ SIGNATURES = {
     "bem_relu_pool_bwd_f32": [P, P, P, I64, I, I, P],
     "bem_relu_bwd_f32": [P, P, P, I64, P],
     "bem_relu_f32": [P, P, I64, P],
+    "bem_batch_assemble_u8": [P, P, I64, P, P, I, P, P, P, I, I, I, I, I, P, P, P, P, P],
     "bem_last_error": [],
     "bem_abi_version": [],
 }

@@ -1072,6 +1072,37 @@ def resize_down(x, s):
     return out
 
 
+def batch_assemble(lq_arena, gt_arena, table, table_dev, plan, plan_dev, row0, B, Sh, Sw, s, noise_dev=None, noise_steps=0):
+    """Rows [row0, row0 + B) of an epoch plan -> lq, gt (B,3,Sh,Sw), lq_down, gt_down (B,3,Sh/s,Sw/s) from the uint8 image store, one launch.
+    ``table`` (n,3) int64 (offset, H, W) and ``plan`` (R,4) int32 (image, top, left, mode) are host tensors, ``table_dev`` / ``plan_dev``
+    their device copies; ``noise_dev`` (R,3) float32 (t, b, c) with ``noise_steps`` (bit 0 temperature, 1 brightness, 2 contrast).
+    ``s`` = 0 returns None for the two down planes (whole validation images whose size no scale_down divides)."""
+    _chk(lq_arena, "lq_arena", torch.uint8); _chk(gt_arena, "gt_arena", torch.uint8)
+    _chk(table_dev, "table_dev", torch.int64); _chk(plan_dev, "plan_dev", torch.int32)
+    _chk(noise_dev, "noise_dev", optional=True)
+    for n, t, dt, w in (("table", table, torch.int64, 3), ("plan", plan, torch.int32, 4)):
+        if t.is_cuda or t.dtype != dt or t.dim() != 2 or t.shape[1] != w or not t.is_contiguous():
+            raise ValueError(f"batch_assemble: {n} must be a contiguous host (rows,{w}) {dt} tensor")
+    if lq_arena.dim() != 1 or lq_arena.shape != gt_arena.shape:
+        raise ValueError("batch_assemble: the two arenas must be flat and of one size")
+    if table_dev.shape != table.shape or plan_dev.shape != plan.shape:
+        raise ValueError("batch_assemble: the device tables must mirror the host tables")
+    if not (0 <= row0 and B > 0 and row0 + B <= plan.shape[0]):
+        raise ValueError(f"batch_assemble: rows [{row0}, {row0 + B}) outside a plan of {plan.shape[0]} rows")
+    if noise_dev is not None and tuple(noise_dev.shape) != (plan.shape[0], 3):
+        raise ValueError("batch_assemble: noise_dev must be (rows,3)")
+    if s < 0 or Sh <= 0 or Sw <= 0:
+        raise ValueError("batch_assemble: crop and scale_down must be positive (scale_down 0: no down planes)")
+    dev = lq_arena.device
+    lq, gt = torch.empty(B, 3, Sh, Sw, device=dev), torch.empty(B, 3, Sh, Sw, device=dev)
+    lqd, gtd = (torch.empty(B, 3, Sh // s, Sw // s, device=dev), torch.empty(B, 3, Sh // s, Sw // s, device=dev)) if s else (None, None)
+    check(lib().bem_batch_assemble_u8(_p(lq_arena), _p(gt_arena), lq_arena.numel(), _p(table), _p(table_dev), table.shape[0],
+                                      ctypes.c_void_p(plan.data_ptr() + 16 * row0), ctypes.c_void_p(plan_dev.data_ptr() + 16 * row0),
+                                      ctypes.c_void_p(0 if noise_dev is None else noise_dev.data_ptr() + 12 * row0), int(noise_steps),
+                                      B, Sh, Sw, s, _p(lq), _p(gt), _p(lqd), _p(gtd), _stream()), "batch_assemble")
+    return lq, gt, lqd, gtd
+
+
 def randn(shape, device, seed=0, stream_id=0, stream_add=None):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     check(lib().bem_randn_f32(_p(out), out.numel(), seed, stream_id, _p(stream_add), _stream()), "randn")

@@ -618,6 +618,24 @@ int bem_relu_bwd_f32(const float* y, const float* dy, float* out, int64_t n, voi
 /* nn.ReLU (the same lines): needed where a requested 'conv*' feature is kept before its ReLU and the walk goes on; out may be x. */
 int bem_relu_f32(const float* x, float* out, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training batches from the device-resident image store (csrc/batch_assemble.hip): Dataset_PairedImage_Mask.__getitem__ for a whole
+ * batch in one launch (basicsr/data/paired_image_dataset.py:333-379: utils/img_util.py:196-211 padding, data/transforms.py:228-273
+ * data_augmentation, utils/labelnoise.py:55-69 add_label_noise, the cv2.resize condition planes :366-371, img2tensor :375-379).
+ *
+ * lq_arena / gt_arena: arena_bytes of uint8 each; image i is (H,W,3) RGB at byte table[3i] with H = table[3i+1], W = table[3i+2] (any
+ * offset, the arenas are read byte-wise).  plan row j = (image, top, left, mode): the crop [top, top+Sh) x [left, left+Sw) of the image
+ * padded 'symmetric' at the bottom / right to at least (Sh, Sw), then rot90(mode / 2) and flipud if mode is odd, / 255.f, written
+ * channel-first to lq[j], gt[j] (B,3,Sh,Sw).  noise_steps (bit 0 temperature, 1 brightness, 2 contrast; 0 = off) applies the label noise
+ * of noise row j = (t, b, c) to gt: blue * t and red / t in float64, clipped to [0,1], rounded to f32; * b clipped; c * (x - 0.5) + 0.5
+ * clipped.  lq_down, gt_down (B,3,Sh/s,Sw/s) = the x1/s INTER_LINEAR planes of the finished lq[j], gt[j], bit for bit what
+ * bem_resize_down_f32 returns for them.  table_host / plan_host are host copies of table_dev / plan_dev (n_img rows, B rows): every
+ * row is checked against the store on the host before the launch.  s even, Sh % s == Sw % s == 0, or s = 0 with null lq_down / gt_down
+ * (no condition planes: whole validation images of any size); modes 2, 3, 6, 7 need Sh == Sw. */
+int bem_batch_assemble_u8(const uint8_t* lq_arena, const uint8_t* gt_arena, int64_t arena_bytes, const int64_t* table_host,
+                          const int64_t* table_dev, int n_img, const int32_t* plan_host, const int32_t* plan_dev, const float* noise_dev,
+                          int noise_steps, int B, int Sh, int Sw, int s, float* lq, float* gt, float* lq_down, float* gt_down, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
