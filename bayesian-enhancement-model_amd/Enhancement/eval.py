@@ -15,10 +15,12 @@ scores every candidate with NIQE on the device (bem.ops.niqe) and keeps the firs
 file ``niqe_pris_params.npz`` of a BasicSR install (basicsr/metrics/), which is data and not shipped here.  ``--no_ref uiqm_uciqe``
 scores every candidate with UIQM and UCIQE on the device (bem.ops.uiqm_uciqe) and keeps the first maximum of ``w * uiqm / max(uiqm) +
 (1 - w) * uciqe / max(uciqe)``, w = ``--uiqm_weight`` (eval.py:277-278); images must resize to at least 10 rows at width 256.  ``--lpips``
-needs a network whose weights are outside this path and raises a clear error.  Scoring happens after the candidates are gathered, so
-every mode works on the sample-sharded ``torchrun`` path.
+(with ``--target_dir``) adds LPIPS v0.1 / AlexNet of the selected image against the target on the device (bem.lpips); its two weight files,
+``alexnet-owt-7be5be79.pth`` of torchvision and ``alex.pth`` of the lpips package, are data and not shipped here: ``--lpips_weights DIR``, the
+environment variable BEM_LPIPS_WEIGHTS or experiments/pretrained_models/ names the directory holding them.  Scoring happens after the
+candidates are gathered, so every mode works on the sample-sharded ``torchrun`` path.
 Output: ``<result_dir>/<dataset>/<image>.png`` (the selected candidate) and ``result.txt`` with the reference's summary lines
-(``Best_NIQE``, then ``Best_UIQM`` and ``Best_UCIQE``, after the PSNR / SSIM lines, eval.py:344-355)."""
+(``Best_lpips`` after the PSNR / SSIM lines, then ``Best_NIQE``, then ``Best_UIQM`` and ``Best_UCIQE``, eval.py:339-355)."""
 import argparse
 import os
 import sys
@@ -51,6 +53,7 @@ def get_parser():
     p.add_argument("--niqe_params", default="", type=str, help="niqe_pris_params.npz of a BasicSR install (basicsr/metrics/), for --no_ref niqe")
     p.add_argument("--uiqm_weight", default=1.0, type=float, help="Balance between UIQM and UICIQE")
     p.add_argument("--lpips", action="store_true", help="True to compute LPIPS")
+    p.add_argument("--lpips_weights", default="", type=str, help="directory holding alexnet-owt-7be5be79.pth and alex.pth, for --lpips")
     p.add_argument("--deterministic", action="store_true", help="Use deterministic mode")
     p.add_argument("--parallel_num", default=1, type=int, help="accepted for compatibility: all samples of an image run as one batch")
     p.add_argument("--seed", default=287128, type=int, help="fix random seed to reproduce consistent results")
@@ -82,7 +85,14 @@ def load_params(net, path):
 def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.lpips:
-        raise SystemExit("--lpips is a host-side metric package outside the HIP path (SURVEY.md section 2 row 1)")
+        # checked before any option-file, model or device work
+        if not args.target_dir:
+            raise SystemExit("--lpips is a full-reference metric: it needs --target_dir")
+        from bem.lpips import find_weight_files
+        try:
+            find_weight_files(args.lpips_weights or None)
+        except FileNotFoundError as e:
+            raise SystemExit(f"--lpips: {e} (--lpips_weights DIR)")
     if args.no_ref == "uiqm_uciqe":
         # checked before any model or device work
         if not os.path.isdir(args.input_dir):
@@ -129,7 +139,11 @@ def main(argv=None):
         scorer = UiqmUciqe(args.uiqm_weight)
     else:
         scorer = FullReference(args.psnr_weight) if args.target_dir else None
-    psnr, ssim, mc_psnr, mc_ssim, niqe, uiqm, uciqe = [], [], [], [], [], [], []
+    psnr, ssim, mc_psnr, mc_ssim, niqe, uiqm, uciqe, lpips_ = [], [], [], [], [], [], [], []
+    loss_fn = None
+    if args.lpips and rank == 0:          # every rank holds the gathered best image: one computes the metric
+        from bem.lpips import LPIPS
+        loss_fn = LPIPS(net="alex", verbose=False, weights_dir=args.lpips_weights or None).cuda()
     t0 = time.perf_counter()
     with torch.inference_mode():
         for i, name in enumerate(names):
@@ -152,6 +166,8 @@ def main(argv=None):
                 ssim.append(float(ops.ssim(best.contiguous(), tgt.contiguous(), 1)[0]))
                 if args.Monte_Carlo:
                     mc_psnr.append(float(r["mc_psnr"][0])); mc_ssim.append(float(r["mc_ssim"][0]))
+                if loss_fn is not None:
+                    lpips_.append(float(loss_fn.distance01(tgt, best)[0]))      # eval.py:301-306, the quantisation of save_rgb below
             if rank == 0:
                 save_rgb(os.path.join(result_dir, os.path.splitext(name)[0] + ".png"), best[0].permute(1, 2, 0).cpu().numpy())
     if world > 1:
@@ -159,12 +175,15 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
-        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, result_dir=result_dir)
+        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir)
     print(f"running time: {time.perf_counter() - t0:.4f} sec")
     with open(os.path.join(result_dir, "result.txt"), "w") as f:
         if args.target_dir:
             for label, vals, unit in (("Best_PSNR", psnr, " dB"), ("Best_SSIM", ssim, "")):
                 line = f"{label}: {np.mean(vals):.4f}{unit}"
+                print(line); f.write(line + " \n")
+            if args.lpips:
+                line = f"Best_lpips: {np.mean(lpips_):.4f}"
                 print(line); f.write(line + " \n")
             if args.Monte_Carlo:
                 for label, vals, unit in (("MC_PSNR", mc_psnr, " dB"), ("MC_SSIM", mc_ssim, "")):
@@ -177,7 +196,7 @@ def main(argv=None):
             for label, vals in (("Best_UIQM", uiqm), ("Best_UCIQE", uciqe)):
                 line = f"{label}: {np.mean(vals):.4f}"
                 print(line); f.write(line + " \n")
-    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, result_dir=result_dir)
+    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir)
 
 
 if __name__ == "__main__":

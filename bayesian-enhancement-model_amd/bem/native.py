@@ -161,13 +161,17 @@ SIGNATURES = {
     "bem_relu_pool_bwd_f32": [P, P, P, I64, I, I, P],
     "bem_relu_bwd_f32": [P, P, P, I64, P],
     "bem_relu_f32": [P, P, I64, P],
+    "bem_lpips_prep_f32": [P, P, P, I, I, I, I, P],
+    "bem_maxpool3s2_f32": [P, I64, I64, P, I64, I, I, P],
+    "bem_lpips_layer_ws_elems": [I, I, I],
+    "bem_lpips_layer_f32": [P, I64, I64, I64, P, P, I64, P, I, I, I, I, I, P],
     "bem_batch_assemble_u8": [P, P, I64, P, P, I, P, P, P, I, I, I, I, I, P, P, P, P, P],
     "bem_last_error": [],
     "bem_abi_version": [],
 }
 _RESTYPE = {"bem_last_error": ctypes.c_char_p, "bem_pw_packed_elems": c_int64, "bem_pw_x6_packed_elems": c_int64, "bem_selective_scan_bwd_ws_elems": c_int64,
             "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64, "bem_uiqm_ws_bytes": c_int64,
-            "bem_ss2d_scan_n_bwd_ws_elems": c_int64, "bem_fusion_head_bwd_ws_elems": c_int64}
+            "bem_ss2d_scan_n_bwd_ws_elems": c_int64, "bem_fusion_head_bwd_ws_elems": c_int64, "bem_lpips_layer_ws_elems": c_int64}
 
 _lib = None
 

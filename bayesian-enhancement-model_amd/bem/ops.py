@@ -663,6 +663,7 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
     ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
     Runs as an implicit GEMM on the matrix cores (Cout <= 160), else on the direct VALU kernel.
     dilation 2 (3x3, pad 2) and 3x3 stride 2 exist in the shifted-tap form only (QD model2 / model3).
+    5x5 stride 1 (LPIPS conv2) exists for Cin % 8 == 0: 25 shifted taps where the width is even and pad is 2, the direct kernel otherwise.
     ``w``: a ConvWeight, whose packed forms are reused, or a plain (Cout, Cin, KH, KW) tensor, packed for this call alone."""
     cw = w if isinstance(w, ConvWeight) else ConvWeight(w)
     w = cw.w
@@ -702,6 +703,11 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
         # nine shifted 1x1 taps on the bf16-limb GEMM machinery (conv_x6.hip)
         check(lib().bem_conv3x3_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
                                        Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
+        return out
+    if USE_CONV_X6 and (KH, KW, stride, pad) == (5, 5, 1, 2) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
+        # 25 shifted 1x1 taps on the same machinery (LPIPS conv2); odd widths: the direct kernel at the end
+        check(lib().bem_conv_taps_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 5, 1, 1, int(relu),
+                                         res1_rep, _stream()), "conv_taps_x6")
         return out
     conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
         and xbs % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
@@ -1700,6 +1706,83 @@ def relu(x):
     out = torch.empty_like(x)
     check(lib().bem_relu_f32(_p(x), _p(out), x.numel(), _stream()), "relu")
     return out
+
+
+# --------------------------------------------------------------------------- LPIPS -------------
+# What runs around the five convolutions of LPIPS v0.1 / AlexNet (lpips.hip; bem.lpips.LPIPS is the caller).
+LPIPS_MIN_HW = 31          # 31 -> 7 (conv1) -> 3 (pool) -> 1 (pool): below it the second pool has no output
+
+
+def lpips_conv1_hw(H, W):
+    """Output size of AlexNet's first convolution (11x11, stride 4, pad 2)."""
+    return (H - 7) // 4 + 1, (W - 7) // 4 + 1
+
+
+def lpips_prep(ref, pred, quantise=True, normalize=False):
+    """ref, pred (B,3,H,W) -> (2B,48,Hb,Wb), rows [0,B) ref and [B,2B) pred: img_as_ubyte and im2tensor (``quantise``: inputs in [0,1]) or
+    2 x - 1 (``normalize``: inputs in [0,1], not quantised) or neither (inputs in [-1,1] already), the scaling layer, and the 4x4 space-to-depth block layout conv1 reads (include/bem_hip.h: bem_lpips_prep_f32)."""
+    _chk(ref, "ref"); _chk(pred, "pred")
+    if ref.dim() != 4 or ref.shape[1] != 3 or ref.shape != pred.shape:
+        raise ValueError(f"lpips_prep: two (B,3,H,W) tensors of one shape required, got {tuple(ref.shape)} and {tuple(pred.shape)}")
+    B, _, H, W = ref.shape
+    if H < LPIPS_MIN_HW or W < LPIPS_MIN_HW:
+        raise ValueError(f"lpips_prep: images of at least {LPIPS_MIN_HW} x {LPIPS_MIN_HW} required, got {H} x {W}")
+    Ho, Wo = lpips_conv1_hw(H, W)
+    xs = torch.empty(2 * B, 48, Ho + 2, (Wo + 3) // 2 * 2, device=ref.device, dtype=torch.float32)
+    check(lib().bem_lpips_prep_f32(_p(ref), _p(pred), _p(xs), B, H, W, 1 if quantise else 2 if normalize else 0, _stream()), "lpips_prep")
+    return xs
+
+
+def _plane_view(op, x, lead):
+    """Checks a float32 device tensor whose last two dimensions may be a crop of a wider plane (unit stride along the last one) and whose
+    ``lead`` dimensions before them are evenly strided; returns the strides of those dimensions and of the rows."""
+    if not x.is_cuda:
+        raise native.BemNativeError(f"{op}: x must be a CUDA/HIP tensor: the BEM hot path has no CPU implementation")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{op}: x must be float32, got {x.dtype}")
+    if x.dim() != lead + 2 or x.stride(-1) != 1 or min(x.shape) < 1:
+        raise ValueError(f"{op}: a non-empty {lead + 2}-dimensional tensor with unit stride along the last dimension required, got "
+                         f"{tuple(x.shape)} / {x.stride()}")
+    return x.stride()[:-1]
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2) over the last two dimensions of x (B,C,H,W), floor mode (leftover rows / columns are dropped); x may be a crop of
+    a wider contiguous tensor (conv1's output inside its block grid)."""
+    bs, cs, rs = _plane_view("maxpool3s2", x, 2)
+    B, C, H, W = x.shape
+    if H < 3 or W < 3:
+        raise ValueError(f"maxpool3s2: planes of at least 3 x 3 required, got {tuple(x.shape)}")
+    if B != 1 and bs != C * cs:
+        raise ValueError(f"maxpool3s2: planes are not evenly strided ({x.stride()})")
+    out = torch.empty(B, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1, device=x.device, dtype=torch.float32)
+    check(lib().bem_maxpool3s2_f32(_p(x), cs, rs, _p(out), B * C, H, W, _stream()), "maxpool3s2")
+    return out
+
+
+def lpips_layer(feat, lin, ws=None, out=None, first=True):
+    """Distance head of one layer: feat (2B,C,h,w) (rows b and B + b are pair b; may be a crop of a wider tensor), lin (C) -> (out (B) f32,
+    ws).  ``first`` starts the f64 running sum in ws from zero; later layers pass the returned ws and out back and add to it."""
+    bs, cs, rs = _plane_view("lpips_layer", feat, 2)
+    _chk(lin, "lin")
+    B2, C, h, w = feat.shape
+    if B2 % 2 or lin.numel() != C:
+        raise ValueError(f"lpips_layer: feat {tuple(feat.shape)} needs an even number of rows and lin {tuple(lin.shape)} one weight per channel")
+    B = B2 // 2
+    need = lib().bem_lpips_layer_ws_elems(B, h, w)
+    if ws is None or ws.numel() < need:
+        if not first:
+            raise ValueError("lpips_layer: a later layer needs the workspace of the first (it holds the running sum)")
+        ws = torch.empty(need, device=feat.device, dtype=torch.float64)
+    _chk(ws, "ws", dtype=torch.float64)
+    if out is None:
+        out = torch.empty(B, device=feat.device, dtype=torch.float32)
+    _chk(out, "out")
+    if out.numel() != B:
+        raise ValueError("lpips_layer: out shape")
+    check(lib().bem_lpips_layer_f32(_p(feat), bs, cs, rs, _p(lin), _p(ws), ws.numel(), _p(out), B, C, h, w, int(bool(first)), _stream()),
+          "lpips_layer")
+    return out, ws
 
 
 def _ln_bwd_cost(x1, x2, dres, want_n, **_):

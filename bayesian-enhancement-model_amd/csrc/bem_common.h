@@ -63,6 +63,9 @@ __device__ __forceinline__ float valu_copy(float v) {
     asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(v));
     return r;
 }
+// skimage's img_as_ubyte of a float image in [0, 1], kept as a float: rint(255 x), half to even.  SSIM and LPIPS quantise with this one
+// function, and it is what the eval driver's save_rgb writes to the PNG.
+__device__ __forceinline__ float bem_ubyte(float x) { return rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.f); }
 __device__ __forceinline__ float bem_silu(float x) { return x / (1.f + bem_fexp(-x)); }
 __device__ __forceinline__ float bem_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7) on the hardware exp / rcp: ~12 instructions instead of

@@ -620,8 +620,10 @@ extern "C" int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w,
         conv2d_kernel<3, 3, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
     else if (KH == 4 && KW == 4 && stride == 2)
         conv2d_kernel<4, 4, 2><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
+    else if (KH == 5 && KW == 5 && stride == 1 && Cin % 8 == 0)       // the channel counts the 5x5 tap form takes at even widths: this is its odd-width half
+        conv2d_kernel<5, 5, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
     else
-        BEM_REQUIRE(false, "conv2d: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2)", KH, KW, stride);
+        BEM_REQUIRE(false, "conv2d: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2, and 5x5 s1 for Cin %% 8 == 0)", KH, KW, stride);
     return bem_check_launch("conv2d");
 }
 

@@ -189,7 +189,7 @@ int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp,
 }
 
 // ================================================================================================
-// Dense convolutions as shifted 1x1 GEMM taps on the same x6 machinery (3x3 stride 1 pad 1; 4x4 stride 2 pad 1):
+// Dense convolutions as shifted 1x1 GEMM taps on the same x6 machinery (3x3 stride 1 pad 1, dilated or strided; 5x5 stride 1 pad 2):
 //     out[co][p] = relu?( sum_{tap} sum_ci W[co][ci][tap] * x[ci][S*p + tap offset] + bias[co] ) + res1 + res2
 // No im2col patch: tap (ky, kx) reads the input pixels of the wave's 64 output pixels straight from global memory (the
 // displaced reads of a k-block overlap and are served by L1 / L2), masks the pixels that fall outside the image, splits
@@ -335,9 +335,9 @@ static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, 
                             const char* what) {
     BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "%s: null tensor or res1_rep < 1", what);
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", what);
-    BEM_REQUIRE((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1),
-                "%s: supported forms are 3x3 s1 (dilation 1 / 2, padding = dilation) and 3x3 s2 p1", what);
-    const int pad = dil;                                        // "same" padding of the dilated 3x3; 1 for the others
+    BEM_REQUIRE((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1) || (KH == 5 && stride == 1 && dil == 1),
+                "%s: supported forms are 3x3 s1 (dilation 1 / 2, padding = dilation), 3x3 s2 p1 and 5x5 s1 p2", what);
+    const int pad = dil * (KH - 1) / 2;                         // "same" padding of the (dilated) window; 1 for the strided 3x3
     const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
     BEM_REQUIRE(Ho > 0 && Wo > 0 && Wo % 2 == 0 && Cin % 8 == 0 && H * W >= 2, "%s: needs an even output width and Cin %% 8 == 0 (got Wo=%d Cin=%d)", what, Wo, Cin);
     BEM_REQUIRE(((uintptr_t)Wp & 15) == 0 && (((uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 7) == 0,
@@ -350,7 +350,10 @@ static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, 
     const int mtw = k.MT == 1 ? 1 : 2;
     dim3 grid(cdiv(Ho * Wo, 256), cdiv(k.MT, mtw), B);
     hipStream_t s = (hipStream_t)stream;
-    if (KH == 3 && stride == 1) {
+    if (KH == 5) {
+        if (mtw == 1) conv_taps_x6_kernel<1, 5, 5, 1><<<grid, 256, 0, s>>>(k);
+        else conv_taps_x6_kernel<2, 5, 5, 1><<<grid, 256, 0, s>>>(k);
+    } else if (KH == 3 && stride == 1) {
         if (mtw == 1) conv_taps_x6_kernel<1, 3, 3, 1><<<grid, 256, 0, s>>>(k);
         else conv_taps_x6_kernel<2, 3, 3, 1><<<grid, 256, 0, s>>>(k);
     } else {

@@ -167,8 +167,8 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
     for (int i = threadIdx.x; i < SS_IN * SS_IN; i += 256) {
         const int r = i / SS_IN, c = i % SS_IN;
         const int y = min(ty * SS_T + r, h - 1), x = min(tx * SS_T + c, w - 1);
-        sa[r][c] = rintf(fminf(fmaxf(pa[(int64_t)y * w + x], 0.f), 1.f) * 255.f);     // img_as_ubyte: rint(255 x), half to even
-        sb[r][c] = rintf(fminf(fmaxf(pb[(int64_t)y * w + x], 0.f), 1.f) * 255.f);
+        sa[r][c] = bem_ubyte(pa[(int64_t)y * w + x]);
+        sb[r][c] = bem_ubyte(pb[(int64_t)y * w + x]);
     }
     __syncthreads();
     const int oy = threadIdx.x / SS_T, ox = threadIdx.x % SS_T;

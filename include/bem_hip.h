@@ -217,8 +217,8 @@ int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const float* Wp, con
                          const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream);
 
 /* The general entry of the tap form: K x K taps with `stride` and `dilation`; supported: 3x3 s1 d1 (pad 1), 3x3 s1 d2 (pad 2: the dilated
- * branch convolutions of QD/model2.py:171-181), 3x3 s2 d1 (pad 1: down_conv of QD/model3.py:176), 4x4 s2 d1 (pad 1).  Wp as above
- * (K*K tap matrices, tap = ky*K + kx). */
+ * branch convolutions of QD/model2.py:171-181), 3x3 s2 d1 (pad 1: down_conv of QD/model3.py:176), 5x5 s1 d1 (pad 2: the second AlexNet convolution of
+ * LPIPS).  Wp as above (K*K tap matrices, tap = ky*K + kx). */
 int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
                          float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
                          void* stream);
@@ -617,6 +617,34 @@ int bem_relu_pool_bwd_f32(const float* y, const float* dpool, float* dy, int64_t
 int bem_relu_bwd_f32(const float* y, const float* dy, float* out, int64_t n, void* stream);
 /* nn.ReLU (the same lines): needed where a requested 'conv*' feature is kept before its ReLU and the walk goes on; out may be x. */
 int bem_relu_f32(const float* x, float* out, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * LPIPS v0.1 with the AlexNet trunk, forward only (csrc/lpips.hip; the metric of Enhancement/eval.py:143-145,301-306 and
+ * Enhancement/cal_metrics_with_imgs.py:39-41,51-55).  The five convolutions are bem_conv3x3_x6_f32 / bem_conv_taps_x6_f32 / bem_conv2d_f32.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Input stage for both images at once, written as the operand of the first convolution.  ref, pred (B,3,H,W), H, W >= 31 (below that the
+ * second pool has no output).  mode 1: images in [0,1] -> u = rint(clip(x,0,1) * 255) (img_as_ubyte, the quantisation of
+ * bem_ssim_f32), u / 127.5 - 1 (lpips.im2tensor); mode 0: x is already in [-1,1]; mode 2: 2 x - 1 (forward(normalize=True)).  Then the scaling layer (x - shift_c) / scale_c, true f32
+ * divisions.  xs (2B,48,Hb,Wb), rows [0,B) from ref and [B,2B) from pred, Hb = (H-7)/4 + 3, Wb = (W-7)/4 + 3 rounded up to even: block
+ * (by,bx), channel 16 c + 4 dy + dx holds the scaled pixel (4 by - 2 + dy, 4 bx - 2 + dx) of colour c, zero outside the image.  With the
+ * 11x11 weight zero-padded to 12x12 and cut the same way into (64,48,3,3), conv1 of AlexNet (stride 4, pad 2) at (oy,ox) is the 3x3 pad-1
+ * convolution of xs at (oy + 1, ox + 1). */
+int bem_lpips_prep_f32(const float* ref, const float* pred, float* xs, int B, int H, int W, int mode, void* stream);
+
+/* nn.MaxPool2d(kernel_size=3, stride=2), floor mode, no padding, torch's NaN rule (a NaN in the window is the result): x (planes,H,W) read
+ * at x_pstride elements between planes and x_rstride between rows (a cropped view of a wider tensor) -> out (planes,(H-3)/2+1,(W-3)/2+1)
+ * contiguous.  H, W >= 3. */
+int bem_maxpool3s2_f32(const float* x, int64_t x_pstride, int64_t x_rstride, float* out, int64_t planes, int H, int W, void* stream);
+
+/* Distance head of one layer: feat (2B,C,h,w) at the given batch / channel / row strides, rows b and B + b the two images of pair b; lin (C)
+ * the layer's 1x1 weights.  Per pixel in f64: yhat = y * (1 / (sqrt(sum_c y^2) + 1e-10)) for both images, sum_c lin[c] (yhat0 - yhat1)^2; then the
+ * mean over pixels from per-workgroup partials added in a fixed order (no atomics: a call repeats bit for bit).  ws: at least
+ * bem_lpips_layer_ws_elems(B,h,w) doubles; ws[0,B) is the running sum over layers, started from zero by the call with first != 0 and
+ * added to by the others, so the calls of one metric share one ws; out (B) f32 = that sum after this layer. */
+int64_t bem_lpips_layer_ws_elems(int B, int h, int w);
+int bem_lpips_layer_f32(const float* feat, int64_t f_bstride, int64_t f_cstride, int64_t f_rstride, const float* lin, double* ws,
+                        int64_t ws_elems, float* out, int B, int C, int h, int w, int first, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training batches from the device-resident image store (csrc/batch_assemble.hip): Dataset_PairedImage_Mask.__getitem__ for a whole
