@@ -1,4 +1,5 @@
 """BNN conversion / prediction-mode helpers (basicsr/bayesian/tools.py:48-84)."""
+from bem.bayes import KLFn
 from bem.modules import (Conv2dReparameterization, DwConv2d, Linear2d, Linear2dReparameterization,  # noqa: F401
                          PwConv2d)
 
@@ -50,9 +51,8 @@ def set_prediction_type(model, deterministic=True):
 def get_kl_loss(m):
     """Sum over the Bayesian leaves below ``m`` of KL(q || EMA prior) (tools.py:76-84; base_layer.py:26-40): a 0-dim device tensor
     whose backward accumulates into mu / rho .grad.  None when ``m`` holds no Bayesian leaf, as in the reference."""
-    from bem import autograd as ag
     leaves = [layer for layer in m.modules() if hasattr(layer, "kl_terms")]
     if not leaves:
         return None
     params = [p for layer in leaves for t in layer.kl_terms() for p in t[:2]]
-    return ag.KLFn.apply(leaves, *params)
+    return KLFn.apply(leaves, *params)

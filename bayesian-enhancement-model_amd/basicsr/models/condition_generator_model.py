@@ -6,12 +6,13 @@ from collections import OrderedDict
 import torch
 
 from basicsr.archs import build_network
-from basicsr.bayesian import convert2bnn, convert2bnn_selective, get_kl_loss
+from basicsr.bayesian import convert2bnn, convert2bnn_selective, get_kl_loss, set_prediction_type
 from basicsr.losses import build_loss
 from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
-from bem.train import BemAdamW
+from bem import bayes, ops
+from bem.train import BemAdamW, StepState
 
 
 @MODEL_REGISTRY.register()
@@ -92,25 +93,22 @@ class ConditionGenerator(BaseModel):
         (bem.train.StepState).  BEM_STAGE1_GRAPH=0, injected eps, a distributed run or an active launch profile keep the ordinary form."""
         if current_iter > self.opt["train"]["scheduler"]["periods"][0]:
             self.mask = None
-        from bem import ops
-        from bem.modules import _SAMPLE_CTX
         skip = [self.net_g.mask_token] if self.mask is None else []
-        if (os.environ.get("BEM_STAGE1_GRAPH", "1") != "0" and _SAMPLE_CTX[0] is None and not self.opt.get("dist") and ops._PROF is None
+        if (os.environ.get("BEM_STAGE1_GRAPH", "1") != "0" and bayes.scope.ctx is None and not self.opt.get("dist") and ops._PROF is None
                 and self.optimizer_g.graph_safe(skip)):
             return self._optimize_graphed(current_iter, skip)
         return self._step_body(current_iter, skip, None)
 
     def _step_body(self, current_iter, skip, state):
-        from bem.modules import _SAMPLE_CTX, SampleCtx, sampling
         self.optimizer_g.zero_grad()
         # the weight draws of iteration i come from Philox streams keyed by (manual_seed, rank, i): a resumed run draws what the
         # uninterrupted run would have drawn (the reference's resumed run restarts torch's generator instead)
         seed, rank = int(self.opt.get("manual_seed") or 0) & 0xFFFFFFFF, int(self.opt.get("rank", 0))
         if state is not None:
-            ctx = SampleCtx(1, None, seed=seed, rank=rank, epoch_dev=state.epoch_dev)
+            ctx = bayes.SampleCtx(1, None, seed=seed, rank=rank, epoch_dev=state.epoch_dev)
         else:
-            ctx = _SAMPLE_CTX[0] or SampleCtx(1, None, seed=seed, rank=rank, epoch=int(current_iter) & 0xFFFFFF)   # an enclosing context (injected eps) wins
-        with sampling(ctx):
+            ctx = bayes.scope.ctx or bayes.SampleCtx(1, None, seed=seed, rank=rank, epoch=int(current_iter) & 0xFFFFFF)   # an enclosing context (injected eps) wins
+        with bayes.sampling(ctx):
             _, preds = self.net_g(self.lq.contiguous(), mask=self.mask)
         loss_dict = OrderedDict()
         l_kl = get_kl_loss(self.net_g)
@@ -137,31 +135,27 @@ class ConditionGenerator(BaseModel):
         """One captured step per input geometry: {"graph", "state", static inputs, the step's loss tensors}.  The first iteration with a
         geometry runs the ordinary way (it is also the warm-up that leaves every lazily created buffer in place); the second records the
         step -- recording launches nothing -- and is then replayed like all later ones."""
-        import bem.train as bt
         key = (tuple(self.lq.shape), tuple(self.gt.shape), None if self.mask is None else tuple(self.mask.shape))
         graphs = self.__dict__.setdefault("_graphs", {})
         g = graphs.get(key)
-        bank = self.get_bare_model(self.net_g).__dict__.get("_bayes_bank")
-        if isinstance(g, dict) and g["bank_sig"] is not (bank.sig if bank is not None else None):
+        bank_sig = lambda: getattr(bayes.BayesBank.of(self.get_bare_model(self.net_g)), "sig", None)
+        if isinstance(g, dict) and g["bank_sig"] is not bank_sig():
             g = None                 # the bank rebuilt its tables (a parameter / gradient / prior buffer moved): the recorded launches point at the old ones
         if g is None:
             graphs[key] = "warm"
             return self._step_body(current_iter, skip, None)
         if g == "warm":
-            g = {"state": bt.StepState(self.lq.device), "lq": self.lq.clone(), "gt": self.gt.clone(),
+            g = {"state": StepState(self.lq.device), "lq": self.lq.clone(), "gt": self.gt.clone(),
                  "mask": None if self.mask is None else self.mask.clone(), "graph": torch.cuda.CUDAGraph()}
             feed = self.lq, self.gt, self.mask
             self.lq, self.gt, self.mask = g["lq"], g["gt"], g["mask"]
             torch.cuda.synchronize()
-            bt.STEP_STATE[0] = g["state"]
             try:
-                with torch.cuda.graph(g["graph"]):
+                with bayes.capturing(g["state"]), torch.cuda.graph(g["graph"]):
                     g["losses"], g["norm"] = self._step_body(current_iter, skip, g["state"])
             finally:
-                bt.STEP_STATE[0] = None
                 self.lq, self.gt, self.mask = feed
-            bank = self.get_bare_model(self.net_g).__dict__.get("_bayes_bank")
-            g["bank_sig"] = bank.sig if bank is not None else None
+            g["bank_sig"] = bank_sig()
             graphs[key] = g
         for dst, src in ((g["lq"], self.lq), (g["gt"], self.gt), (g["mask"], self.mask)):
             if dst is not None and dst.data_ptr() != src.data_ptr():
@@ -177,8 +171,6 @@ class ConditionGenerator(BaseModel):
     def validation(self, dataloader, current_iter, tb_logger=None, save_img=False, rgb2bgr=True, use_image=True):
         """Mean PSNR of the predicted condition planes against the down-sampled ground truth, deterministic weights (mu), float form on
         the device."""
-        from basicsr.bayesian import set_prediction_type
-        from bem import ops
         was_training = self.net_g.training
         self.net_g.eval()
         set_prediction_type(self.net_g, True)

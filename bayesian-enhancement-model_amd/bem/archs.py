@@ -20,9 +20,9 @@ import torch
 import torch.nn as nn
 
 from . import autograd as ag
+from . import bayes
 from . import ops
-from .modules import (Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _need_cuda, fold_up_fuse, grad_mode, make_vss_level,
-                      set_module_paths)
+from .modules import Conv2dK, ConvT2x2, LayerNorm2d, PwConv2d, VSSBlock, _need_cuda, fold_up_fuse, grad_mode, make_vss_level
 from .native import BemNativeError
 
 _QD_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "basicsr", "QD", "checkpoints")
@@ -848,67 +848,32 @@ class Network(nn.Module):
 
     def forward(self, x, mask=None):
         _need_cuda(x)
-        from .modules import _SAMPLE_CTX, _TRAIN_STEP, SampleCtx, sampling
-        ctx = _SAMPLE_CTX[0]
         if grad_mode(self):
-            return self._forward_train(x, mask, ctx)
-        if ctx is None:      # one weight sample per batch element, fresh Philox streams for this forward
-            ctx = SampleCtx(x.shape[0], None, seed=torch.initial_seed() & 0xFFFFFFFF)
-        with torch.no_grad(), sampling(ctx):
-            set_module_paths(self)
+            return self._forward_train(x, mask)
+        # without an enclosing context: one weight sample per batch element, fresh Philox streams for this forward
+        ctx = bayes.scope.ctx or bayes.SampleCtx(x.shape[0], None, seed=torch.initial_seed() & 0xFFFFFFFF)
+        with torch.no_grad(), bayes.eval_sampling(self, ctx):
             x = x.contiguous()
-            bank = None
-            if ctx.eps is None and ctx.nsets > 1:
-                from .modules import EvalSampleBank
-                bank = self.__dict__.get("_eval_bank")
-                if bank is None:
-                    bank = self.__dict__["_eval_bank"] = EvalSampleBank(self)
-                ctx.counter0 = ctx.counter
-                if bank.usable(ctx):
-                    bank.sample(ctx)                     # all leaves' weight sets in one launch; the first Philox forward goes leaf by leaf
             fea0 = self.first_conv(x)
             dec = self.subnets[0](fea0)
             # proj(fea0 + dec) = proj_nobias(fea0) + proj(dec)   (UNet_arch.py:361,470-472; conv is linear)
             base = ops.conv2d(fea0, self.proj.conv_weight(), None, pad=1)
             out = self.proj(dec, res1=base)
-            ctx.bank = None
         return [x, out]
 
-    def _forward_train(self, x, mask, ctx):
+    def _forward_train(self, x, mask):
         """Training forward (UNet_arch.py:447-474 with module.training): one weight sample per Bayesian leaf for the whole batch
         (conv.py:100-104 draws eps once per forward), EMA prior update before the draw, optional MIM token mix, autograd nodes over the
         HIP kernels.  The returned prediction carries the anchor that folds the sampled-weight gradients into mu / rho after backward."""
-        from .modules import _TRAIN_STEP, SampleCtx, sampling
-        if ctx is None:
-            ctx = SampleCtx(1, None, seed=torch.initial_seed() & 0xFFFFFFFF)
+        ctx = bayes.scope.ctx or bayes.SampleCtx(1, None, seed=torch.initial_seed() & 0xFFFFFFFF)
         if ctx.nsets != 1:
             raise BemNativeError("Network: a training forward shares one weight sample across the batch (SampleCtx(nsets=1))")
-        step = ag.BayesStep()
-        prev = _TRAIN_STEP[0]
-        _TRAIN_STEP[0] = step
-        ops.bump_weight_epoch()              # every training forward draws new weights: packed / transposed copies of the last draw are stale
-        try:
-            with sampling(ctx):
-                set_module_paths(self)
-                if os.environ.get("BEM_BAYES_BANK", "1") != "0":
-                    from .modules import BayesBank
-                    from .train import STEP_STATE
-                    bank = self.__dict__.get("_bayes_bank")
-                    if bank is None:
-                        bank = self.__dict__["_bayes_bank"] = BayesBank(self)
-                    if bank.ready() and bank.usable(ctx):
-                        bank.sample(ctx, step, STEP_STATE[0])      # every leaf's prior EMA + draw + sample in one launch
-                step.counter0 = ctx.counter if step.bank is None else 0
-                fea = self.first_conv(x.contiguous())
-                if mask is not None:
-                    fea = ag.MaskTokenFn.apply(fea, mask, self.mask_token)
-                fa, fb = ag.fork(fea)
-                dec = self.subnets[0](fa)
-                out = self.proj(ag.AddFn.apply(fb, dec))
-                out = ag.BayesAnchorFn.apply(out, step)
-                bank = self.__dict__.get("_bayes_bank")
-                if bank is not None and not bank.ready() and ctx.eps is None:
-                    bank.try_build()                               # this forward went leaf by leaf and recorded its draw order
-        finally:
-            _TRAIN_STEP[0] = prev
+        with bayes.train_sampling(self, ctx) as step:
+            fea = self.first_conv(x.contiguous())
+            if mask is not None:
+                fea = ag.MaskTokenFn.apply(fea, mask, self.mask_token)
+            fa, fb = ag.fork(fea)
+            dec = self.subnets[0](fa)
+            out = self.proj(ag.AddFn.apply(fb, dec))
+            out = bayes.BayesAnchorFn.apply(out, step)
         return [x, out]

@@ -41,14 +41,14 @@ def _w2d(w):
 
 def wb(m):
     """(weight, bias | None) tensors of a leaf: nn.Conv2d / nn.Linear parameters, or -- for a Bayesian leaf in a training forward -- the
-    weights it sampled for this forward (modules._BayesBase.train_sample); their .grad is the buffer the reparameterisation kernel
+    weights it sampled for this forward (``m.sample``, a bayes.Sample); their .grad is the buffer the reparameterisation kernel
     later folds into mu / rho."""
     if hasattr(m, "mu_weight"):
         if m.deterministic:
             return m.mu_weight, (m.mu_bias if m.bias else None)
-        if getattr(m, "_ws", None) is None:
+        if m.sample is None:
             raise RuntimeError("Bayesian leaf: no weight sample is active (training forwards run under Network.forward)")
-        return m._ws, m._bs
+        return m.sample.w, m.sample.b
     return m.weight, m.bias
 
 
@@ -513,76 +513,6 @@ class MaskTokenFn(Function):
     def backward(ctx, g):
         (mask,) = ctx.saved_tensors
         return ops.mask_token_bwd(g.contiguous(), mask, grad_of(ctx.token).view(-1)), None, None
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# Bayesian leaves in training (basicsr/bayesian/conv.py:84-114, linear.py:61-90, tools.py:76-84)
-# ------------------------------------------------------------------------------------------------------------------
-class BayesStep:
-    """One training forward's Bayesian bookkeeping: the leaves that drew a weight sample, to be folded back into mu / rho once the
-    whole backward pass has run (the sampled weight's gradient is complete only then)."""
-
-    def __init__(self):
-        self.leaves = []
-        self.done = False
-        self.bank = None                 # modules.BayesBank when the samples of this forward were drawn by its one launch
-
-    def finish(self):
-        if self.done:
-            return
-        self.done = True
-        if self.bank is not None:        # dmu += dw, drho += dw eps sigmoid(rho) for every tensor of the net in one launch
-            ops.bnn_bank_reparam_bwd_(self.bank)
-            for m in self.leaves:
-                m._ws = m._bs = m._eps_w = m._eps_b = m._sample_owner = None
-            return
-        for m in self.leaves:
-            m.fold_sample_grads()
-
-
-class BayesAnchorFn(Function):
-    """Identity on the network output; its backward (the first node of the pass) queues BayesStep.finish to run after the pass."""
-
-    @staticmethod
-    def forward(ctx, out, step):
-        ctx.step = step
-        return out.view_as(out)
-
-    @staticmethod
-    def backward(ctx, g):
-        torch.autograd.Variable._execution_engine.queue_callback(ctx.step.finish)
-        return g, None
-
-
-class KLFn(Function):
-    """sum over the Bayesian leaves of kl_div(q || EMA prior).mean() for weight (+ bias)  (get_kl_loss, tools.py:76-84)."""
-
-    @staticmethod
-    def forward(ctx, leaves, *params):
-        out = torch.zeros(1, device=params[0].device, dtype=torch.float32)
-        st = getattr(leaves[0], "_sample_owner", None)
-        bank = getattr(st, "bank", None)
-        if bank is not None and len(bank.leaves) == len(leaves) and all(a is b and a._sample_owner is st for a, b in zip(bank.leaves, leaves)):
-            ops.bnn_bank_kl_(bank, out)              # the forward that has just run drew its samples through the bank: same tensors, one launch
-            ctx.bank = bank
-            return out.reshape(())
-        ctx.bank = None
-        for m in leaves:
-            for mu, rho, pmu, prho in m.kl_terms():
-                ops.bnn_kl_(mu.detach(), rho.detach(), pmu, prho, out)
-        ctx.leaves = leaves
-        return out.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        g = g.reshape(1).contiguous().float()
-        if ctx.bank is not None:
-            ops.bnn_bank_kl_bwd_(ctx.bank, g)
-            return (None,) * len(ctx.needs_input_grad)
-        for m in ctx.leaves:
-            for mu, rho, pmu, prho in m.kl_terms():
-                ops.bnn_kl_bwd_(mu.detach(), rho.detach(), pmu, prho, g, grad_of(mu), grad_of(rho))
-        return (None,) * (1 + len(ctx.needs_input_grad) - 1)
 
 
 class ScaledSumFn(Function):

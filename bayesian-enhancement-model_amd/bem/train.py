@@ -64,9 +64,6 @@ class StepState:
             fn()
 
 
-STEP_STATE = [None]        # set while a step is being captured: leaves and the optimizer take their per-iteration scalars from it
-
-
 class BemAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **ignored):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)

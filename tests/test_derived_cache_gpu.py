@@ -9,6 +9,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 COUNTED = ("pack_pw_weight", "pack_pw_weight_jobs", "bnn_sample")
+# the Bayesian steps of a Stage-I forward / training iteration: one launch over the whole net (a bank), or one per tensor
+BANKED = ("bnn_bank_sample", "bnn_bank_kl_", "bnn_bank_kl_bwd_", "bnn_bank_reparam_bwd_", "bnn_ebank_sample")
+PER_TENSOR = ("randn", "bnn_prior_ema_", "bnn_kl_", "bnn_kl_bwd_", "bnn_reparam_bwd_", "bnn_sample_packed")
 
 
 @pytest.fixture(scope="module")
@@ -21,7 +24,7 @@ def ops():
 
 @pytest.fixture
 def calls(ops, monkeypatch):
-    """{name: [first argument of each call]} for the wrappers in COUNTED; ``calls.mark()`` starts a new count.
+    """{name: [first argument of each call]} for the wrappers in COUNTED, BANKED and PER_TENSOR; ``calls.mark()`` starts a new count.
     ops.attn_fold packs the per-image matrix it has just folded from the features -- an activation, which no cache could hold: those
     calls of pack_pw_weight are counted apart, under "attn_fold", and every test states how many it expects."""
     class Calls(dict):
@@ -31,9 +34,9 @@ def calls(ops, monkeypatch):
 
         def n(self, name):
             return len(self[name])
-    rec = Calls({n: [] for n in COUNTED + ("attn_fold",)})
+    rec = Calls({n: [] for n in COUNTED + BANKED + PER_TENSOR + ("attn_fold",)})
     inside = []
-    for name in COUNTED:
+    for name in COUNTED + BANKED + PER_TENSOR:
         def wrapped(*a, _orig=getattr(ops, name), _name=name, **k):
             rec["attn_fold" if inside and _name == "pack_pw_weight" else _name].append(a[0])
             return _orig(*a, **k)
@@ -114,10 +117,11 @@ def test_training_steps_leave_nothing_behind(ops, calls):
 
 def test_bank_preseed_serves_forward_and_backward(ops, calls, monkeypatch):
     """Stage-I training with Philox draws: iteration 1 goes leaf by leaf and builds the BayesBank, iteration 2 takes every Bayesian 1x1
-    leaf's operands -- forward (M, K) and transposed, for the input-gradient GEMM -- from the bank's one packing launch."""
+    leaf's operands -- forward (M, K) and transposed, for the input-gradient GEMM -- from the bank's one packing launch.  The launch budget
+    of iteration 2 follows from the code: every Bayesian step of the iteration is one launch over the whole net, none is per tensor."""
     from basicsr.bayesian import get_kl_loss
     from bem import autograd as ag
-    from bem.modules import SampleCtx, sampling
+    from bem.modules import BayesBank, SampleCtx, sampling
     from bem.pipeline import build_nets, synthetic_pair
     from bem.train import BemAdamW
     monkeypatch.setenv("BEM_BAYES_BANK", "1")
@@ -133,7 +137,7 @@ def test_bank_preseed_serves_forward_and_backward(ops, calls, monkeypatch):
         opt.clip_grad_norm_(1.0)
         opt.step()
         torch.cuda.synchronize()
-        bank = net.__dict__["_bayes_bank"]
+        bank = BayesBank.of(net)
         assert bank.ready() and len(bank.packs) >= 10
         if it == 0:
             assert calls.n("pack_pw_weight_jobs") == 0 and calls.n("bnn_sample") > 0 and calls.n("pack_pw_weight") >= 2 * len(bank.packs)
@@ -141,11 +145,31 @@ def test_bank_preseed_serves_forward_and_backward(ops, calls, monkeypatch):
 
     def sampled(t):             # a view (natural or transposed) of a weight the bank sampled
         return lo <= t.data_ptr() < hi
-    assert all(sampled(m._bank_wv) for m, _, _ in bank.packs)
+    assert all(sampled(wv) for _, _, _, wv in bank.packs)
     assert calls.n("pack_pw_weight_jobs") == 1 and calls.n("bnn_sample") == 0
+    budget = {n: calls.n(n) for n in BANKED + PER_TENSOR}
+    assert budget == {**{n: 1 for n in BANKED}, **{n: 0 for n in PER_TENSOR}, "bnn_ebank_sample": 0}, budget
     assert [tuple(t.shape) for t in calls["pack_pw_weight"] if sampled(t)] == []
-    for m, _, tr in bank.packs:                                              # what the backward read is the bank's transposed pack
+    for m, _, tr, _ in bank.packs:                                              # what the backward read is the bank's transposed pack
         assert ops.derived(m).d["T"][1] is tr
+
+
+def test_second_stochastic_eval_forward_is_one_sampling_launch(ops, calls):
+    """Stage-I eval with Philox draws of 4 weight sets (2 images x 2 samples: one set per batch row): the first forward goes leaf by leaf
+    and records its streams, the second takes every leaf's sets from the EvalSampleBank's one launch."""
+    from bem.modules import EvalSampleBank, SampleCtx, sampling
+    from bem.pipeline import build_nets, synthetic_pair
+    net = build_nets(n_feat=16, num_blocks=(1, 1, 1), seed=100, device="cuda")[0].eval()
+    lq = synthetic_pair((2, 3, 16, 16), seed=6, device="cuda")[0].repeat_interleave(2, 0).contiguous()
+    for it in range(2):
+        calls.mark()
+        with sampling(SampleCtx(4, None, seed=7, epoch=it + 1)):
+            out = net(lq)[-1]
+        if it == 0:
+            assert calls.n("bnn_ebank_sample") == 0 and calls.n("bnn_sample") > 0 and calls.n("bnn_sample_packed") > 0
+    bank = EvalSampleBank.of(net)
+    assert bank is not None and bank.sig is not None and bool(torch.isfinite(out).all())
+    assert calls.n("bnn_ebank_sample") == 1 and calls.n("bnn_sample") == 0 and calls.n("bnn_sample_packed") == 0
 
 
 def test_raw_tensor_conv_keeps_nothing(ops):

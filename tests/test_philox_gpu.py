@@ -366,25 +366,13 @@ class TrainLeaves(nn.Module):
         return [self.a, self.b, self.c, self.d, self.e, self.f, self.g]
 
 
-def train_forward(net, ctx, bank):
-    """The sampling part of Network._forward_train: the bank's one launch when it is ready, otherwise leaf by leaf (which records the draw
-    order the bank is then built from)."""
-    from bem import autograd as ag, modules as M
-    from bem import ops
-    step = ag.BayesStep()
-    prev, M._TRAIN_STEP[0] = M._TRAIN_STEP[0], step
-    ops.bump_weight_epoch()
-    try:
-        with M.sampling(ctx):
-            if bank.ready() and bank.usable(ctx):
-                bank.sample(ctx, step, None)
-            step.counter0 = ctx.counter if step.bank is None else 0
-            for m in net.leaves():
-                m._sampled(1)
-            if not bank.ready():
-                bank.try_build()
-    finally:
-        M._TRAIN_STEP[0] = prev
+def train_forward(net, ctx):
+    """The sampling part of Network._forward_train (bayes.train_sampling): the bank's one launch when it is ready, otherwise leaf by leaf
+    (which records the draw order the bank is then built from)."""
+    from bem.bayes import train_sampling
+    with train_sampling(net, ctx) as step:
+        for m in net.leaves():
+            m._sampled(1)
     return step
 
 
@@ -408,6 +396,7 @@ def test_train_bank_against_the_model(ops, monkeypatch, dev_epoch):
     2^-12 of the result: the bound is 1 ulp.  (At d = 0.7, iteration 20, the same three roundings reach 1.25 ulp in a float32 emulation on
     the CPU: 1 ulp is not a property of this expression there.)"""
     from bem.modules import BayesBank, SampleCtx
+    monkeypatch.setenv("BEM_BAYES_BANK", "1")
     net = TrainLeaves().cuda().train()
     randomize(net, 11)
     g = torch.Generator().manual_seed(12)
@@ -434,17 +423,17 @@ def test_train_bank_against_the_model(ops, monkeypatch, dev_epoch):
         d = float(np.float32(d))
         return d * f64(prior) + (1.0 - d) * f64(param)
 
-    bank = BayesBank(net)
+    bank = BayesBank.of(net, create=True)
     # ---- iteration 1, leaf by leaf
     before = {(id(m), k, pn): getattr(m, f"prior_{pn}_{k}").clone() for m, k in kinds for pn in ("mu", "rho")}
-    train_forward(net, context(E1), bank)
+    train_forward(net, context(E1))
     calls = rec.take()
     assert [c["kind"] for c in calls] == ["randn"] * T          # (the leaf forms w from that eps through the injected-eps path)
     assert [c["sid"] for c in calls] == [P.stream_id(rank, E1, t) for t in range(1, T + 1)]
     d1 = DECAY
     for m, k in kinds:
-        t = m._draw_order[k]
-        e, w = (m._eps_w, m._ws) if k == "weight" else (m._eps_b, m._bs)
+        t = m.draws[k]
+        e, w = (m.sample.eps_w, m.sample.w) if k == "weight" else (m.sample.eps_b, m.sample.b)
         mu, rho = getattr(m, f"mu_{k}"), getattr(m, f"rho_{k}")
         check_z("randn (training leaf)", e, mu.numel(), seed, P.stream_id(rank, E1, t), f"{type(m).__name__}.{k}")
         check_w("bnn_sample (training leaf)", w, mu, rho, 1, seed, P.stream_id(rank, E1, t), f"{type(m).__name__}.{k}")
@@ -466,7 +455,7 @@ def test_train_bank_against_the_model(ops, monkeypatch, dev_epoch):
         arena[pad] = SENT
     bank.gw.fill_(SENT)                                               # the sampling launch zeroes the samples' gradients, and only them
     pm0, pr0 = bank.pm.clone(), bank.pr.clone()
-    train_forward(net, context(E2), bank)
+    train_forward(net, context(E2))
     calls = rec.take()
     assert [c["kind"] for c in calls] == ["bbank"]
     ids = calls[0]["sids"]
@@ -479,7 +468,7 @@ def test_train_bank_against_the_model(ops, monkeypatch, dev_epoch):
         mu, rho = getattr(m, f"mu_{k}"), getattr(m, f"rho_{k}")
         sid = P.stream_id(rank, E2, c)
         what = f"{type(m).__name__}.{k} n={k_}"
-        assert k_ == mu.numel() and c == m._draw_order[k]
+        assert k_ == mu.numel() and c == m.draws[k]
         e = bank.eps[o:o + k_]
         check_z("bank_sample eps", e, k_, seed, sid, what)
         assert bits_equal(e, ops.randn((k_,), "cuda", seed, sid)), what
@@ -487,7 +476,7 @@ def test_train_bank_against_the_model(ops, monkeypatch, dev_epoch):
         assert float(bank.gw[o:o + k_].abs().max()) == 0, what
         assert ulp_ok(bank.pm[o:o + k_], ema(pm0[o:o + k_], mu, d2)).all(), what
         assert ulp_ok(bank.pr[o:o + k_], ema(pr0[o:o + k_], rho, d2)).all(), what
-        wv, ev = (m._ws, m._eps_w) if k == "weight" else (m._bs, m._eps_b)
+        wv, ev = (m.sample.w, m.sample.eps_w) if k == "weight" else (m.sample.b, m.sample.eps_b)
         assert wv.data_ptr() == bank.w.data_ptr() + 4 * o and ev.data_ptr() == bank.eps.data_ptr() + 4 * o
         assert getattr(m, f"prior_mu_{k}").data_ptr() == bank.pm.data_ptr() + 4 * o
     rec.take()

@@ -781,7 +781,7 @@ def test_stage1_training_gradients_golden(dev):
         err = float((p.grad.cpu() - ref).abs().max())
         assert err <= 2e-3 * scale + 1e-7, (k, err, scale)
     # a second backward through the same graph is refused by autograd; a second FORWARD draws a new sample and a new EMA step
-    assert all(m._ws is None for m in net.modules() if hasattr(m, "kl_terms"))
+    assert all(m.sample is None for m in net.modules() if hasattr(m, "kl_terms"))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -829,13 +829,14 @@ def test_stage1_bayes_bank_equals_the_per_leaf_steps(dev, tmp_path, monkeypatch)
     against the same 6 iterations done tensor by tensor (BEM_BAYES_BANK=0), both launched kernel by kernel.  The bank draws every tensor
     from the Philox stream the per-leaf forward uses for it, so the two runs see the same weight samples: parameters, EMA priors and
     losses agree to the noise of the atomically reduced gradients."""
+    from bem.modules import BayesBank
     monkeypatch.setenv("BEM_STAGE1_GRAPH", "0")
     monkeypatch.setenv("BEM_BAYES_BANK", "0")
     a, ia = _run_driver(tmp_path / "A", "CG_UNet_LOLv1.yml", [], 6)
-    assert a.net_g.__dict__.get("_bayes_bank") is None
+    assert BayesBank.of(a.net_g) is None
     monkeypatch.setenv("BEM_BAYES_BANK", "1")
     b, ib = _run_driver(tmp_path / "B", "CG_UNet_LOLv1.yml", [], 6)
-    bank = b.net_g.__dict__.get("_bayes_bank")
+    bank = BayesBank.of(b.net_g)
     assert bank is not None and bank.ready() and len(bank.views) == sum(2 if m.bias else 1 for m in bank.leaves) >= 30
     pa, pb = dict(a.net_g.named_parameters()), dict(b.net_g.named_parameters())
     worst = max(float((pa[k].detach() - pb[k].detach()).abs().max()) for k in pa)
