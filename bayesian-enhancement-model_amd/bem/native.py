@@ -1,4 +1,10 @@
-"""ctypes binding of libbem_hip.so (C ABI declared in include/bem_hip.h).
+"""ctypes binding of libbem_hip.so, derived from the C ABI's own declaration (include/bem_hip.h).
+
+The header is the one place where an entry point's arguments are written down: this module parses its prototypes and the two
+argument-block structs when it is imported (a few milliseconds; the structs must be complete before anyone can fill one) and
+``lib()`` applies them to the loaded library.  A wrong argument type at this seam would not raise -- it would shift every later
+argument of the call -- so a declaration the parser does not understand is an error, never skipped
+(tests/test_native_binding_cpu.py compares the result with what a C++ compiler makes of the same header).
 
 There is deliberately no fallback: if the library is missing or a call is rejected the caller
 gets an exception (``BemNativeError``) -- the product path never computes on the CPU."""
@@ -6,11 +12,13 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from ctypes import c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEM_HIP_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libbem_hip.so"))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
+HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "bem_hip.h")
 
 
 class BemNativeError(RuntimeError):
@@ -18,160 +26,68 @@ class BemNativeError(RuntimeError):
 
 
 class PwArgs(ctypes.Structure):
-    """Mirror of ``bem_pw_args`` (include/bem_hip.h)."""
-    _fields_ = [
-        ("x1", c_void_p), ("x2", c_void_p), ("C1", c_int), ("C2", c_int), ("in_mode", c_int),
-        ("ln_w", c_void_p), ("ln_b", c_void_p), ("ln_eps", c_float),
-        ("Wp", c_void_p), ("w_bstride", c_int64),
-        ("bias", c_void_p), ("bias_bstride", c_int64),
-        ("res", c_void_p),
-        ("prelu", c_void_p), ("act", c_int),
-        ("out", c_void_p), ("out_mode", c_int), ("Win", c_int),
-        ("B", c_int), ("M", c_int), ("K", c_int), ("L", c_int),
-    ]
+    """``bem_pw_args``; the fields are taken from the header below."""
 
 
 class WgradArgs(ctypes.Structure):
-    """Mirror of ``bem_wgrad_args`` (include/bem_hip.h)."""
-    _fields_ = [
-        ("dy", c_void_p), ("dy_bstride", c_int64), ("M", c_int),
-        ("x1", c_void_p), ("x1_bstride", c_int64), ("C1", c_int),
-        ("x2", c_void_p), ("x2_bstride", c_int64), ("C2", c_int),
-        ("dw", c_void_p), ("ldw", c_int64), ("blk_rows", c_int), ("perm", c_int * 4),
-        ("dbias", c_void_p),
-        ("B", c_int), ("L", c_int),
-    ]
+    """``bem_wgrad_args``; the fields are taken from the header below."""
 
 
 P, I, I64, U64, F = c_void_p, c_int, c_int64, c_uint64, c_float
 
-# name -> argtypes (return type int unless listed in _RESTYPE); this table is what the
-# "every declared symbol is exported" CPU test checks against include/bem_hip.h.
-SIGNATURES = {
-    "bem_selective_scan_fwd_f32": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    "bem_selective_scan_fwd_in16": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
-    "bem_cast16_to_f32": [P, P, ctypes.c_int64, I, P],
-    "bem_cast_f32_to16": [P, P, ctypes.c_int64, I, P],
-    "bem_selective_scan_bwd_ws_elems": [I, I, I, I],
-    "bem_selective_scan_bwd_f32": [P] * 16 + [I, I, I, I, I, I, P],
-    "bem_cross_scan_f32": [P, P, I, I, I, I, P],
-    "bem_cross_merge_f32": [P, P, I, I, I, I, P],
-    "bem_ss2d_scan_strided_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I64, I64, P],
-    "bem_ss2d_scan_rm_supported": [I, I, I],
-    "bem_ss2d_scan_rm_f32": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I64, I64, P],
-    "bem_pack_pw_weight_f32": [P, P, I, I, I, P],
-    "bem_pw_packed_elems": [I, I],
-    "bem_pw_gemm_x6_f32": [ctypes.POINTER(PwArgs), P],
-    "bem_pack_pw_weight_x6": [P, P, I, I, I, P],
-    "bem_pack_pw_weight_x6_strided": [P, P, I, I, I, I64, I64, I64, P],
-    "bem_pack_pw_weight_x6_jobs": [P, P, I, P, P],
-    "bem_pw_x6_packed_elems": [I, I],
-    "bem_bnn_sample_pack_x6": [P, P, P, P, I, I, I, U64, U64, P, I, P],
-    "bem_upfuse_x6_f32": [P, P, P, P, P, P, I, I, I, I, P],
-    "bem_store_words": [P, P, I, P],
-    "bem_bnn_ebank_sample_f32": [P, P, I, P, U64, U64, P],
-    "bem_bnn_bank_sample_f32": [P, P, I, P, P, P, P, P, F, P, U64, U64, P, P],
-    "bem_bnn_bank_kl_f32": [P, P, I, P, P, P, P],
-    "bem_bnn_bank_kl_bwd_f32": [P, P, I, P, P, P, P],
-    "bem_bnn_bank_reparam_bwd_f32": [P, P, I, P, P, P],
-    "bem_row_scale_f32": [P, P, P, I, I, P],
-    "bem_se_gate_f32": [P, P, P, P, I, I, I, P],
-    "bem_spatial_attention_f32": [P, P, P, P, P, I, I, I, I, I, P],
-    "bem_hamilton_bwd_f32": [P, P, P, I, I, I, P],
-    "bem_chan_scale_f32": [P, P, I64, P, P, F, P, I, I, I64, P],
-    "bem_chan_dot_f32": [P, P, P, I, I, I64, I, P],
-    "bem_se_gate_bwd_f32": [P, P, P, P, P, P, P, P, I, I, I, P],
-    "bem_spatial_attention_bwd_f32": [P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_bnn_prior_ema_f32": [P, P, P, P, F, P, I64, P],
-    "bem_bnn_kl_f32": [P, P, P, P, I64, P, P],
-    "bem_bnn_kl_bwd_f32": [P, P, P, P, I64, P, P, P, P],
-    "bem_bnn_reparam_bwd_f32": [P, P, P, P, P, I64, P],
-    "bem_mask_token_f32": [P, P, P, P, I, I, I, I, P],
-    "bem_mask_token_bwd_f32": [P, P, P, P, I, I, I, I, P],
-    "bem_depth_to_space_f32": [P, P, I, I, I, I, P],
-    "bem_prelu_f32": [P, P, P, I64, P],
-    "bem_prelu_bwd_f32": [P, P, P, P, P, I64, P],
-    "bem_bilinear_up_bwd_f32": [P, P, I, I, I, I, I, P],
-    "bem_gdmlp_x6_f32": [P, P, P, F, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_conv3x3_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, P],
-    "bem_conv4x4s2_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, P],
-    "bem_conv4x4s2_fast_supported": [I, I, I],
-    "bem_conv3x3_rows_supported": [I, I, I],
-    "bem_ss2d_front_x6_f32": [P, P, P, F, P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_conv_taps_x6_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
-    "bem_dwconv3x3_f32": [P, P, I64, P, I64, P, I, I, I, I, I, P],
-    "bem_conv2d_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
-    "bem_conv2d_mfma_f32": [P, I64, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P],
-    "bem_quat_dwt_f32": [P, I64, P, I, I, I, P],
-    "bem_cond_dwt_f32": [P, P, I, I, I, I, P],
-    "bem_dwt_f32": [P, P, I, I, I, I, P],
-    "bem_iwt_f32": [P, P, I, I, I, I, P],
-    "bem_iwt_hamilton_f32": [P, P, P, I, I, I, P],
-    "bem_hamilton_f32": [P, P, I, I, I, P],
-    "bem_hamilton_full_f32": [P, P, P, I, I, I, P],
-    "bem_attn_stats_f64": [P, P, P, I, I, P],
-    "bem_attn_fold_f32": [P, P, P, P, P, P, I, I, P],
-    "bem_transpose_planes_f32": [P, I64, P, I64, I, I, I, I, P],
-    "bem_copy_channels_f32": [P, I64, P, I64, I, I, I, P],
-    "bem_copy_channels_rep_f32": [P, I64, P, I64, I, I, I, I, P],
-    "bem_add_channels_f32": [P, I64, P, I64, I, I, I, P],
-    "bem_bilinear_up_f32": [P, I64, P, I64, I, I, I, I, I, P],
-    "bem_space_to_depth_f32": [P, P, I, I, I, I, P],
-    "bem_pixel_shuffle2_f32": [P, P, I, I, I, I, P],
-    "bem_bnn_sample_f32": [P, P, P, P, I, I64, U64, U64, P, P],
-    "bem_select_best_f32": [P, P, P, P, P, I, I, I64, P],
-    "bem_ssim_f32": [P, P, P, P, I, I, I, I, P],
-    "bem_select_scores_f32": [P, P, P, F, I, P, P, P, P, I, I, I64, P],
-    "bem_niqe_f32": [P, P, P, P, P, I, P, P, I, P, P, I, P, P, I64, I, I, I, P],
-    "bem_niqe_ws_bytes": [I, I, I],
-    "bem_uiqm_uciqe_f32": [P, P, P, P, I, P, P, I, P, P, P, I64, I, I, I, I, P],
-    "bem_uiqm_ws_bytes": [I, I, I, I],
-    "bem_mc_mean_f32": [P, P, P, P, I, I, I, I, I, I, I, P],
-    "bem_pad_reflect_f32": [P, P, I, I, I, I, I, P],
-    "bem_resize_down_f32": [P, P, I, I, I, I, P],
-    "bem_randn_f32": [P, I64, U64, U64, P, P],
-    "bem_cond_postproc_f32": [P, P, P, P, I, I, I, I, F, P],
-    "bem_plane_mean_f32": [P, P, I, I, I, I, I, P],
-    "bem_candidate_finalize_f32": [P, P, P, P, P, I, I, I, I, I, I, I, P],
-    "bem_l1_loss_f32": [P, P, P, P, P, I64, F, P, P],
-    "bem_iwt_hamilton_bwd_f32": [P, P, P, P, P, I, I, I, P],
-    "bem_pixel_unshuffle2_f32": [P, P, I, I, I, I, P],
-    "bem_channel_sum_f32": [P, P, I, I, I64, P],
-    "bem_add_f32": [P, P, P, I64, F, P],
-    "bem_ln_bwd_f32": [P, P, P, P, P, F, P, P, P, P, P, I, I, I64, P],
-    "bem_ln_fwd_f32": [P, P, P, P, F, P, I, I, I64, P],
-    "bem_dwact_bwd_f32": [P, P, P, P, P, P, P, I, I, I, I, I, P],
-    "bem_pw_wgrad_f32": [ctypes.POINTER(WgradArgs), P],
-    "bem_pw_wgrad_x6_f32": [ctypes.POINTER(WgradArgs), P, I64, P],
-    "bem_pw_wgrad_x6_ws_elems": [I, I, I, I],
-    "bem_conv_wgrad_f32": [P, P, I64, P, P, I, I, I, I, I, I, I, I, I, P],
-    "bem_ss2d_scan_bwd_f32": [P] * 18 + [I, I, I, I, I64, I64, P],
-    "bem_ss2d_scan_n_supported": [I],
-    "bem_ss2d_scan_n_f32": [P] * 10 + [I, I, I, I, I, I64, I64, P],
-    "bem_ss2d_scan_n_bwd_ws_elems": [I, I, I, I],
-    "bem_ss2d_scan_n_bwd_f32": [P] * 19 + [I64, I, I, I, I, I, I64, I64, P],
-    "bem_fusion_head_f32": [P, I64, P, I64, P, P, P, P, P, I, I, I, I, I, I, P],
-    "bem_fusion_head_bwd_ws_elems": [I, I, I],
-    "bem_fusion_head_bwd_f32": [P, I64, P, I64] + [P] * 11 + [I64, I, I, I, I, I, I, P],
-    "bem_grad_sumsq_f32": [P, I64, P, P],
-    "bem_adamw_step_f32": [P, P, P, P, I64, F, F, F, F, F, I, F, P, P, P, P],
-    "bem_vgg_prep_f32": [P, P, P, I, I, I, I, I, P],
-    "bem_vgg_prep_bwd_f32": [P, I64, P, I, I, I, I, I, P],
-    "bem_maxpool2_f32": [P, P, I64, I, I, P],
-    "bem_relu_pool_bwd_f32": [P, P, P, I64, I, I, P],
-    "bem_relu_bwd_f32": [P, P, P, I64, P],
-    "bem_relu_f32": [P, P, I64, P],
-    "bem_lpips_prep_f32": [P, P, P, I, I, I, I, P],
-    "bem_maxpool3s2_f32": [P, I64, I64, P, I64, I, I, P],
-    "bem_lpips_layer_ws_elems": [I, I, I],
-    "bem_lpips_layer_f32": [P, I64, I64, I64, P, P, I64, P, I, I, I, I, I, P],
-    "bem_batch_assemble_u8": [P, P, I64, P, P, I, P, P, P, I, I, I, I, I, P, P, P, P, P],
-    "bem_last_error": [],
-    "bem_abi_version": [],
-}
-_RESTYPE = {"bem_last_error": ctypes.c_char_p, "bem_pw_packed_elems": c_int64, "bem_pw_x6_packed_elems": c_int64, "bem_selective_scan_bwd_ws_elems": c_int64,
-            "bem_pw_wgrad_x6_ws_elems": c_int64, "bem_niqe_ws_bytes": c_int64, "bem_uiqm_ws_bytes": c_int64,
-            "bem_ss2d_scan_n_bwd_ws_elems": c_int64, "bem_fusion_head_bwd_ws_elems": c_int64, "bem_lpips_layer_ws_elems": c_int64}
+# The header's whole vocabulary.  Every pointer is a c_void_p except the two argument blocks; anything else is an error, never a guess.
+_SCALARS = {"int": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
+_RETURNS = {"int": c_int, "int64_t": c_int64, "const char*": ctypes.c_char_p}
+_STRUCTS = {"bem_pw_args": PwArgs, "bem_wgrad_args": WgradArgs}
+
+
+def _ctype(decl: str, line: int):
+    """ctypes type and name of one ``type name`` / ``type name[n]`` declaration (a parameter or a struct field)."""
+    m = re.fullmatch(r"(.*?[\s*])(\w+)(?:\[(\d+)\])?", decl.strip(), re.S)
+    typ = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())) if m else ""
+    if typ.endswith("*"):
+        block = re.fullmatch(r"const (\w+)\*", typ)
+        t = ctypes.POINTER(_STRUCTS[block.group(1)]) if block and block.group(1) in _STRUCTS else P
+    elif typ in _SCALARS:
+        t = _SCALARS[typ]
+    else:
+        raise BemNativeError(f"bem_hip.h line {line}: no ctypes mapping for `{' '.join(decl.split())}`")
+    return (t * int(m.group(3)) if m.group(3) else t), m.group(2)
+
+
+def parse_header(text: str):
+    """C declarations of the header -> ({function: (restype, [argtypes])}, {struct: [(field, ctype)]}).  Comments and preprocessor lines
+    are blanked in place, so errors name the header's own line; a statement that is neither a prototype nor one of the argument-block
+    typedefs raises."""
+    blank = lambda m: "\n" * m.group(0).count("\n")
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", blank, text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}\s*\Z', "", text)
+    line = lambda pos: text.count("\n", 0, pos) + 1
+    structs, protos = {}, {}
+
+    def struct(m):
+        structs[m.group(2)] = [_ctype(d, line(m.start()))[::-1] for d in m.group(1).split(";") if d.strip()]
+        return blank(m)
+    text = re.sub(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    for m in re.finditer(r"[^;\s][^;]*", text):
+        stmt, at = " ".join(m.group(0).split()), line(m.start())
+        p = re.fullmatch(r"(.*?[\s*])(bem_\w+)\s*\((.*)\)", stmt)
+        ret = re.sub(r"\s*\*\s*", "*", p.group(1)).strip() if p else None
+        if ret not in _RETURNS:
+            raise BemNativeError(f"bem_hip.h line {at}: not a prototype this binding understands: `{stmt}`")
+        args = [] if p.group(3).strip() in ("", "void") else p.group(3).split(",")
+        protos[p.group(2)] = (_RETURNS[ret], [_ctype(a, at)[0] for a in args])
+    return protos, structs
+
+
+try:
+    with open(HEADER) as _f:
+        _PROTOS, _FIELDS = parse_header(_f.read())
+except OSError as e:
+    raise BemNativeError(f"{HEADER}: the C ABI header is the source of the binding and must ship with the package ({e})")
+PwArgs._fields_, WgradArgs._fields_ = (_FIELDS[n] for n in _STRUCTS)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _PROTOS.items()}     # name -> argtypes, as declared in the header
 
 _lib = None
 
@@ -195,10 +111,9 @@ def lib():
                 f"{LIB_PATH} not found: the HIP library is required (no CPU fallback). "
                 f"Build it with `make -C {CSRC}` or __graft_entry__.build().")
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, (restype, argtypes) in _PROTOS.items():
             fn = getattr(L, name)          # AttributeError here = symbol missing from the build
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPE.get(name, c_int)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

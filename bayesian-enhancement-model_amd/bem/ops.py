@@ -2,7 +2,9 @@
 
 Each wrapper checks operand shapes on the host before anything is launched (a kernel fault can take
 the whole GPU host down), allocates the output with torch (device memory is torch's job here) and
-launches on torch's current stream.  No wrapper computes anything itself."""
+launches on torch's current stream.  No wrapper computes anything itself: the constant tables some kernels read are built by
+bem.tables (numpy, on the host) and uploaded once per device (``_tables``); scratch buffers that outlive a call are kept per stream
+(``_scratch``), all others are allocated by the call."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +18,7 @@ import torch
 
 from . import native
 from .native import PwArgs, check, lib
+from .tables import UIQM_WIDTH, lab_tables, niqe_gamma_table, niqe_resize_table, pil_resize_table, uiqm_resized_rows  # noqa: F401  (host builders; callers of ops.<name> keep working)
 
 
 def _stream():
@@ -124,6 +127,30 @@ def _bracket(cost, sees=None):
             return out
         return op
     return deco
+
+
+# ----------------------------------------------------------------- cached device memory ----
+_SCRATCH = {}            # (tag, device, stream) -> a kernel's scratch buffer
+_TABLES = {}             # (key, device) -> constant table(s) of bem.tables on the device
+
+
+def _scratch(tag, device, n, dtype):
+    """The scratch buffer ``tag`` of at least n elements for a launch on ``device``'s current stream.  Launches on one stream are ordered, so
+    they share one buffer, which grows and never shrinks; another stream (or another tag) gets its own, so two streams never meet in one."""
+    key = (tag, str(device), torch.cuda.current_stream(device).cuda_stream)
+    ws = _SCRATCH.get(key)
+    if ws is None or ws.numel() < n:
+        ws = _SCRATCH[key] = torch.empty(n, device=device, dtype=dtype)
+    return ws
+
+
+def _tables(key, device, build):
+    """What ``build()`` returns (one numpy array or a tuple of them), uploaded once per device."""
+    k = (key, str(device))
+    if k not in _TABLES:
+        t = build()
+        _TABLES[k] = tuple(torch.from_numpy(a).to(device) for a in t) if isinstance(t, tuple) else torch.from_numpy(t).to(device)
+    return _TABLES[k]
 
 
 _GRID_MAX = 65535        # the y and z extent of a launch grid: planes, candidates (x 3 channels) or images go there
@@ -1367,67 +1394,14 @@ def mc_mean(raw, target, samples_per_image, h, w, gt_mean):
     return out
 
 
-# NIQE (basicsr/metrics/niqe.py as Enhancement/eval.py:248-254 calls it).  Derived tables, built on the host once and kept on the device:
-# the AGGD shape grid of estimate_aggd_param (niqe.py:24-26) with its closed-form gamma ratios, and per input length the weights and
-# symmetric-padded source indices of MATLAB's antialiased bicubic x0.5 resize (matlab_functions.py:16-81).
+# NIQE (basicsr/metrics/niqe.py as Enhancement/eval.py:248-254 calls it).  Its tables (bem.tables): the AGGD shape grid, and per cropped
+# length the weights and source indices of the x0.5 resize.
 NIQE_BLOCK = 96
-_niqe_cache = {}
-
-
-def niqe_gamma_table():
-    """(4, 9801) f64: gam = arange(0.2, 10.001, 0.001), r_gam = G(2/a)^2 / (G(1/a) G(3/a)), sqrt(G(1/a) / G(3/a)), G(2/a) / G(1/a)."""
-    import math
-    import numpy as np
-    gam = np.arange(0.2, 10.001, 0.001)
-    rec = np.reciprocal(gam)
-    tab = np.empty((4, gam.size))
-    tab[0] = gam
-    for i, (a, r) in enumerate(zip(gam.tolist(), rec.tolist())):
-        tab[1, i] = math.gamma(r * 2) ** 2 / (math.gamma(r) * math.gamma(r * 3))
-        tab[2, i] = math.sqrt(math.gamma(1 / a) / math.gamma(3 / a))
-        tab[3, i] = math.gamma(2 / a) / math.gamma(1 / a)
-    return tab
-
-
-def niqe_resize_table(n, scale=0.5):
-    """MATLAB imresize (bicubic, antialiased) along one axis of length n, in float32 like the reference: weights (out, K) f32 and the
-    0-based source index of every tap (out, K) int32 with the symmetric padding folded in; all-zero end columns trimmed."""
-    import math
-    import numpy as np
-    f32 = np.float32
-    out = math.ceil(n * scale)
-    width = 4.0 / scale if scale < 1 else 4.0
-    x = np.arange(1, out + 1, dtype=f32)
-    u = x / f32(scale) + f32(0.5 * (1 - 1 / scale))
-    left = np.floor(u - f32(width / 2))
-    taps = math.ceil(width) + 2
-    idx = left[:, None] + np.arange(taps, dtype=f32)[None, :]
-    d = np.abs((u[:, None] - idx) * f32(scale) if scale < 1 else u[:, None] - idx)
-    d2, d3 = d ** 2, d ** 3
-    cub = (f32(1.5) * d3 - f32(2.5) * d2 + f32(1)) * (d <= 1) + (f32(-0.5) * d3 + f32(2.5) * d2 - f32(4) * d + f32(2)) * ((d > 1) & (d <= 2))
-    wt = (f32(scale) * cub if scale < 1 else cub).astype(f32)
-    wt = wt / wt.sum(axis=1, keepdims=True)
-    keep = np.ones(taps, bool)
-    keep[0] = not (wt[:, 0] == 0).any()
-    keep[-1] = not (wt[:, -1] == 0).any()
-    wt, idx = wt[:, keep], idx[:, keep].astype(np.int64) - 1
-    idx = np.where(idx < 0, -idx - 1, idx)
-    idx = np.where(idx >= n, 2 * n - 1 - idx, idx)
-    return np.ascontiguousarray(wt, dtype=f32), np.ascontiguousarray(idx, dtype=np.int32)
 
 
 def _niqe_tables(device, Hc, Wc):
-    key = (str(device), "gamma")
-    if key not in _niqe_cache:
-        _niqe_cache[key] = torch.from_numpy(niqe_gamma_table()).to(device)
-    rs = []
-    for n in (Hc, Wc):
-        k = (str(device), "resize", n)
-        if k not in _niqe_cache:
-            wt, ix = niqe_resize_table(n)
-            _niqe_cache[k] = (torch.from_numpy(wt).to(device), torch.from_numpy(ix).to(device))
-        rs.append(_niqe_cache[k])
-    return _niqe_cache[key], rs[0], rs[1]
+    return (_tables("niqe_gamma", device, niqe_gamma_table),
+            *(_tables(("niqe_resize", n), device, lambda: niqe_resize_table(n)) for n in (Hc, Wc)))
 
 
 def niqe(final, params):
@@ -1448,92 +1422,20 @@ def niqe(final, params):
     out = torch.empty(Bn, device=dev, dtype=torch.float64)
     if Bn == 0:
         return out
-    nbytes = int(lib().bem_niqe_ws_bytes(Bn, h, w))
-    key = (str(dev), "ws", torch.cuda.current_stream(dev).cuda_stream)
-    ws = _niqe_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _niqe_cache[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = _scratch("niqe", dev, int(lib().bem_niqe_ws_bytes(Bn, h, w)), torch.uint8)
     check(lib().bem_niqe_f32(_p(final), _p(params.mu), _p(params.cov), _p(params.window), _p(tab), tab.shape[1], _p(wh), _p(ih), wh.shape[1],
                              _p(ww), _p(iw), ww.shape[1], _p(out), _p(ws), ws.numel(), Bn, h, w, _stream()), "niqe")
     return out
 
 
-# UIQM / UCIQE (basicsr/metrics/uciqe_uiqm.py as Enhancement/eval.py:255-260 calls them).  Host-built tables, kept on the device: per
-# (source length, target length) Pillow's fixed-point BICUBIC coefficients (Resample.c), and OpenCV 4.x's 8-bit RGB -> Lab tables
-# (color_lab.cpp, RGB2Lab_b).
-UIQM_WIDTH = 256
-UIQM_WINDOW = 10
-_uiqm_cache = {}
-
-
-def _pil_bicubic(x):
-    a = -0.5
-    if x < 0.0:
-        x = -x
-    if x < 1.0:
-        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * a
-    return 0.0
-
-
-def pil_resize_table(n_in, n_out):
-    """Pillow's BICUBIC resample of one axis, n_in -> n_out, in its 8-bit form (precompute_coeffs + normalize_coeffs_8bpc):
-    bounds (n_out, 2) int32 = first source index and tap count, weights (n_out, K) int32 with 22 fractional bits, zero past the taps."""
-    import math
-    import numpy as np
-    scale = n_in / n_out
-    fscale = max(scale, 1.0)
-    support = 2.0 * fscale
-    K = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((n_out, 2), np.int32)
-    kk = np.zeros((n_out, K), np.int32)
-    for o in range(n_out):
-        center = (o + 0.5) * scale
-        x0 = max(int(center - support + 0.5), 0)
-        n = min(int(center + support + 0.5), n_in) - x0
-        ss = 1.0 / fscale
-        ws = [_pil_bicubic((x + x0 - center + 0.5) * ss) for x in range(n)]
-        tot = 0.0
-        for v in ws:
-            tot += v
-        for x, v in enumerate(ws):
-            v = v / tot if tot != 0.0 else v
-            kk[o, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
-        bounds[o] = (x0, n)
-    return bounds, kk
-
-
-def lab_tables():
-    """OpenCV 4.x RGB2Lab_b tables as one int32 vector: sRGB gamma x 255 x 8 (256 entries), 2^15 (x < 0.008856 ? 7.787 x + 16/116 : cbrt x)
-    at x = i / (255 x 8) (3072), and the fixed-point matrix cvRound(4096 sRGB2XYZ_D65[i][j] / D65white[i]) (9, row-major, R G B order)."""
-    import numpy as np
-    x = np.arange(256) / 255.0
-    gamma = np.rint(np.where(x <= 0.04045, x / 12.92, ((x + 0.055) / 1.055) ** 2.4) * 255.0 * 8)
-    t = np.arange(3072) / (255.0 * 8)
-    cbrt = np.rint((1 << 15) * np.where(t < 0.008856, t * 7.787 + 16.0 / 116.0, np.cbrt(t)))
-    m = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])
-    coef = np.rint(4096 * m / np.array([0.950456, 1.0, 1.088754])[:, None])
-    return np.concatenate([gamma, cbrt, coef.ravel()]).astype(np.int32)
-
-
-def uiqm_resized_rows(h, w):
-    """eval.py:257: the resized image is (int(256 / w * h), 256)."""
-    return int(UIQM_WIDTH / w * h)
+# UIQM / UCIQE (basicsr/metrics/uciqe_uiqm.py as Enhancement/eval.py:255-260 calls them).  Their tables (bem.tables): per (source length,
+# target length) Pillow's BICUBIC coefficients, and OpenCV's 8-bit RGB -> Lab tables.
+UIQM_WINDOW = 10                    # UIQM_WIDTH (256) comes from bem.tables, whose builders read it
 
 
 def _uiqm_tables(device, h, w, Hr):
-    dev = str(device)
-    if (dev, "lab") not in _uiqm_cache:
-        _uiqm_cache[(dev, "lab")] = torch.from_numpy(lab_tables()).to(device)
-    rs = []
-    for n_in, n_out in ((w, UIQM_WIDTH), (h, Hr)):
-        k = (dev, "resize", n_in, n_out)
-        if k not in _uiqm_cache:
-            b, kk = pil_resize_table(n_in, n_out)
-            _uiqm_cache[k] = (torch.from_numpy(b).to(device), torch.from_numpy(kk).to(device))
-        rs.append(_uiqm_cache[k])
-    return _uiqm_cache[(dev, "lab")], rs[0], rs[1]
+    return (_tables("uiqm_lab", device, lab_tables),
+            *(_tables(("uiqm_resize", n_in, n_out), device, lambda: pil_resize_table(n_in, n_out)) for n_in, n_out in ((w, UIQM_WIDTH), (h, Hr))))
 
 
 def uiqm_uciqe(final, debug=False):
@@ -1558,11 +1460,7 @@ def uiqm_uciqe(final, debug=False):
     if Bn == 0:
         return (u1, u2, None) if debug else (u1, u2)
     tab, (bh, kh), (bv, kv) = _uiqm_tables(dev, h, w, Hr)
-    nbytes = int(lib().bem_uiqm_ws_bytes(Bn, h, w, Hr))
-    key = (str(dev), "ws", torch.cuda.current_stream(dev).cuda_stream)
-    ws = _uiqm_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _uiqm_cache[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = _scratch("uiqm", dev, int(lib().bem_uiqm_ws_bytes(Bn, h, w, Hr)), torch.uint8)
     check(lib().bem_uiqm_uciqe_f32(_p(final), _p(tab), _p(bh), _p(kh), kh.shape[1], _p(bv), _p(kv), kv.shape[1], _p(u1), _p(u2), _p(ws),
                                    ws.numel(), Bn, h, w, Hr, _stream()), "uiqm_uciqe")
     if not debug:
@@ -1836,7 +1734,6 @@ WGRAD_X6 = os.environ.get("BEM_WGRAD_X6", "1") != "0"      # 1x1 weight gradient
 # below this many pixels per launch the x6 form's fixed costs (one wave per SIMD, second reduction launch) lose to the f32-MFMA kernel:
 # Stage-I training (8 x 8 planes) 34.7 -> 23.8 ms per step
 WGRAD_X6_MIN_PIXELS = 16384
-_WGX_WS = {}                                               # per-device scratch of the x6 weight-gradient kernel (stream-ordered reuse)
 
 
 def _pw_wgrad_cost(dy, x1, x2, M, **_):
@@ -1873,10 +1770,7 @@ def pw_wgrad_(dy, x1, dw, x2=None, dbias=None, blk_rows=0, perm=(0, 1, 2, 3), dy
     a.dbias = dbias.data_ptr() if dbias is not None else 0
     a.B, a.L = B, L
     if WGRAD_X6 and L % 32 == 0 and B * L >= WGRAD_X6_MIN_PIXELS:
-        n = lib().bem_pw_wgrad_x6_ws_elems(M, C1 + C2, B, L)
-        ws = _WGX_WS.get(dw.device)
-        if ws is None or ws.numel() < n:
-            ws = _WGX_WS[dw.device] = torch.empty(max(n, 1 << 20), device=dw.device, dtype=torch.float32)
+        ws = _scratch("wgrad_x6", dw.device, max(lib().bem_pw_wgrad_x6_ws_elems(M, C1 + C2, B, L), 1 << 20), torch.float32)
         check(lib().bem_pw_wgrad_x6_f32(ctypes.byref(a), _p(ws), ws.numel(), _stream()), "pw_wgrad_x6")
     else:
         check(lib().bem_pw_wgrad_f32(ctypes.byref(a), _stream()), "pw_wgrad")

@@ -117,7 +117,7 @@ def test_ops_keeps_no_conv_weights():
         if depth < 3 and isinstance(o, (list, tuple, set)):
             return any(tensors_in(v, depth + 1) for v in o)
         return False
-    keep = {"_niqe_cache", "_uiqm_cache"}               # tables keyed by image size, not by weights
+    keep = {"_SCRATCH", "_TABLES"}                     # scratch buffers and tables keyed by image size, not by weights
     assert [n for n, o in vars(ops).items() if n not in keep and isinstance(o, (dict, list, tuple, set)) and tensors_in(o)] == []
     w = torch.zeros(4, 8, 3, 3)
     cw = ops.ConvWeight(w)

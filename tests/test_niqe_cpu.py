@@ -1,5 +1,5 @@
 """CPU: NIQE no-reference selection (eval.py --no_ref niqe).  The float64 restatement (tests/niqe_ref.py) against the reference's recorded
-features and scores (g13_niqe.npz), the host-built tables of bem.ops against the reference's own formulas (live, skipped without the
+features and scores (g13_niqe.npz), the host-built tables of bem.tables against the reference's own formulas (live, skipped without the
 reference tree), and the argument checks that come before any GPU call."""
 import importlib.util
 import os
@@ -88,13 +88,13 @@ def reference():
 
 
 def test_host_tables_match_reference(reference):
-    """bem.ops' gamma table and resize tables against the reference's formulas, live: the gamma ratios of estimate_aggd_param
+    """bem.tables' gamma table and resize tables against the reference's formulas, live: the gamma ratios of estimate_aggd_param
     (niqe.py:24-26,35-36,59) with scipy's gamma, and calculate_weights_indices (matlab_functions.py:16-81) with its padding."""
     import math
     from scipy.special import gamma
-    from bem import ops
+    from bem import tables
     niqe_mod, _, mf = reference
-    tab = ops.niqe_gamma_table()
+    tab = tables.niqe_gamma_table()
     gam = np.arange(0.2, 10.001, 0.001)
     rec = np.reciprocal(gam)
     assert tab.shape == (4, 9801) and np.array_equal(tab[0], gam)
@@ -108,7 +108,7 @@ def test_host_tables_match_reference(reference):
         a = niqe_mod.estimate_aggd_param(x)[0]
         assert a == R.aggd(x)[1]
     for n in (96, 192, 288, 384, 576, 1056):
-        wt, ix = ops.niqe_resize_table(n)
+        wt, ix = tables.niqe_resize_table(n)
         rw, ri, s0, _ = mf.calculate_weights_indices(n, math.ceil(n * 0.5), 0.5, "cubic", 4, True)
         assert np.array_equal(wt, rw.numpy()), n
         src = ri.numpy().astype(np.int64) - s0                # padded-array position -> 0-based source, then the symmetric fold

@@ -41,8 +41,7 @@ def _features(final, params):
     Bn, _, h, w = final.shape
     nb = (h // 96) * (w // 96)
     total = int(lib().bem_niqe_ws_bytes(Bn, h, w))
-    key = [k for k in ops._niqe_cache if k[0] == str(final.device) and k[1] == "ws"][0]
-    ws = ops._niqe_cache[key]
+    ws = ops._scratch("niqe", final.device, total, torch.uint8)         # the buffer the call just used: same stream, no larger request
     start = total - ((Bn * nb * 36 * 8 + 255) // 256) * 256
     feat = ws[start:start + Bn * nb * 36 * 8].view(torch.float64).reshape(Bn, nb, 36)
     return s, feat.cpu().numpy()

@@ -940,3 +940,39 @@ def test_x6_gemm_bias_epilogue_under_load(ops, cfg):
         out = ops.pw_gemm(x1, Wp, M, x2=x2, in_mode=mode, bias=dev(bias))
         bad = int(((out[0].double() - ref).abs() > 1e-4).sum())
         assert bad == 0, f"{cfg} launch {rep}: {bad} outputs off by more than 1e-4"
+
+
+def test_scratch_buffers_are_kept_per_stream(ops, monkeypatch):
+    """The two scratch buffers that outlive a call.  The x6 weight gradient (smallest shape: one 32-pixel chunk, one ragged tile) on the
+    current stream and on a second one: both against float64 at test_train_gpu.py::test_pw_wgrad's tolerance, from two scratch tensors.
+    NIQE twice on one stream: one workspace, bit-identical scores."""
+    import os
+    from conftest import GOLDEN
+    from bem.scorers import NiqeParams
+    monkeypatch.setattr(ops, "_SCRATCH", {})
+    monkeypatch.setattr(ops, "WGRAD_X6_MIN_PIXELS", 0)
+    B, M, K, L = 1, 8, 8, 32
+    g = torch.Generator().manual_seed(11)
+    dy, x = torch.randn(B, M, L, generator=g), torch.randn(B, K, L, generator=g)
+    ref = torch.einsum("bml,bkl->mk", dy.double(), x.double())
+    atol = 3e-6 * float(ref.abs().max()) * max(1.0, (B * L) ** 0.5 / 8)
+    dyd, xd = dev(dy), dev(x)
+    dw1 = ops.pw_wgrad_(dyd, xd, torch.zeros(M, K, device="cuda"))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        dw2 = ops.pw_wgrad_(dyd, xd, torch.zeros(M, K, device="cuda"))
+    side.synchronize()
+    close(dw1, ref, 0.0, atol, "dw on the current stream")
+    close(dw2, ref, 0.0, atol, "dw on the side stream")
+    bufs = {k: v for k, v in ops._SCRATCH.items() if k[0] == "wgrad_x6"}
+    assert {k[2] for k in bufs} == {torch.cuda.current_stream().cuda_stream, side.cuda_stream} and len(bufs) == 2
+    assert len({v.data_ptr() for v in bufs.values()}) == 2 and all(v.numel() == 1 << 20 for v in bufs.values())
+    params = NiqeParams.load(os.path.join(GOLDEN, "g13_niqe.npz"))
+    final = dev(torch.rand(2, 3, 96, 96, generator=g))
+    s1 = ops.niqe(final, params)
+    (key, ws), = [(k, v) for k, v in ops._SCRATCH.items() if k[0] == "niqe"]
+    s2 = ops.niqe(final, params)
+    assert [k for k in ops._SCRATCH if k[0] == "niqe"] == [key] and ops._SCRATCH[key] is ws
+    assert ops._scratch("niqe", final.device, ws.numel(), torch.uint8).data_ptr() == ws.data_ptr()
+    assert torch.equal(s1.view(torch.int64), s2.view(torch.int64))         # bit for bit (one 96 x 96 block scores NaN: see ops.niqe)

@@ -1,5 +1,5 @@
 """CPU: UIQM / UCIQE no-reference selection (eval.py --no_ref uiqm_uciqe).  The numpy restatement (tests/uiqm_ref.py) against the
-reference's recorded parts and choices (g16_uiqm.npz) and against the reference live (skipped without the reference tree); bem.ops'
+reference's recorded parts and choices (g16_uiqm.npz) and against the reference live (skipped without the reference tree); bem.tables'
 host-built tables against Pillow and against the restatement; the OpenCV Lab restatement against known anchors and an analytic
 CIE-Lab; the argument checks that come before any GPU call."""
 import importlib.util
@@ -67,15 +67,15 @@ def test_restatement_matches_reference_live(g13):
 
 @pytest.mark.parametrize("hw", [(400, 600), (193, 290), (256, 256), (600, 400), (120, 90), (45, 700), (31, 41)])
 def test_pil_resize_tables_bit_exact(hw):
-    """bem.ops' coefficient tables equal the restatement's, and the fixed-point two-pass resize with them equals PIL.Image.resize
+    """bem.tables' coefficient tables equal the restatement's, and the fixed-point two-pass resize with them equals PIL.Image.resize
     (BICUBIC) at eval.py:257's target size, down- and upsampling."""
     from PIL import Image
-    from bem import ops
+    from bem import tables
     h, w = hw
-    rows = ops.uiqm_resized_rows(h, w)
+    rows = tables.uiqm_resized_rows(h, w)
     assert rows == R.resized_size(h, w)[0] == int(256 / w * h)
     for n_in, n_out in ((w, 256), (h, rows)):
-        b, k = ops.pil_resize_table(n_in, n_out)
+        b, k = tables.pil_resize_table(n_in, n_out)
         rb, rk = R.pil_coeffs(n_in, n_out)
         assert np.array_equal(b, rb) and np.array_equal(k, rk)
         assert (b[:, 0] >= 0).all() and (b.sum(axis=1) <= n_in).all() and (b[:, 1] <= k.shape[1]).all()
@@ -87,9 +87,9 @@ def test_pil_resize_tables_bit_exact(hw):
 def test_lab_tables_and_anchors():
     """The restated cv2.cvtColor(RGB2LAB) on 8-bit data: white, black and the grey axis (a = b = 128), and the primaries' widely published
     cv2 outputs (recalled values, not recorded with cv2 here)."""
-    from bem import ops
+    from bem import tables
     g, c, m = R.lab_tables()
-    assert np.array_equal(ops.lab_tables(), np.concatenate([g, c, m.ravel()]).astype(np.int32))
+    assert np.array_equal(tables.lab_tables(), np.concatenate([g, c, m.ravel()]).astype(np.int32))
     anchors = {(255, 255, 255): (255, 128, 128), (0, 0, 0): (0, 128, 128), (255, 0, 0): (136, 208, 195), (0, 255, 0): (224, 42, 211),
                (0, 0, 255): (82, 207, 20)}
     for rgb, lab in anchors.items():
