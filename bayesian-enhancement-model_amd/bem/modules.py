@@ -208,12 +208,16 @@ class gdMlp(nn.Module):
         self.project_out = PwConv2d(hidden_features, out_features)
         self.act = act_layer()
 
-    def forward_fused(self, x, norm: LayerNorm2d):
-        """x + project_out(GELU(h1) * h2), h = dwconv(project_in(LN(x)))."""
+    def fused_supported(self, C):
+        """The whole branch runs as one kernel (ops.gdmlp_x6): deterministic leaves and a supported width."""
+        return isinstance(self.project_in, PwConv2d) and isinstance(self.dwconv, DwConv2d) and isinstance(self.project_out, PwConv2d) \
+            and ops.gdmlp_x6_supported(C, self.project_in.out_channels // 2)
+
+    def forward_fused(self, x, norm: LayerNorm2d, pre=None):
+        """x + project_out(GELU(h1) * h2), h = dwconv(project_in(LN(x))).  pre (ops.gdmlp_x6): the SS2D tail that forms x inside the kernel."""
         B, C = x.shape[0], x.shape[1]
         Hd = self.project_in.out_channels // 2
-        if isinstance(self.project_in, PwConv2d) and isinstance(self.dwconv, DwConv2d) and isinstance(self.project_out, PwConv2d) \
-                and ops.gdmlp_x6_supported(C, Hd):
+        if self.fused_supported(C):
             # the whole branch in one kernel (bem_gdmlp_x6_f32): neither the 2Hd-channel nor the Hd-channel tensor reaches HBM
             pi, dw, po = self.project_in, self.dwconv, self.project_out
 
@@ -225,7 +229,9 @@ class gdMlp(nn.Module):
                         ops.pack_pw_weight(po.weight.detach().reshape(po.out_channels, Hd).contiguous(), x6=True),
                         None if po.bias is None else po.bias.detach().contiguous())
             Wg, bg, w10, Wo, bo = ops.derived(self).get("gdmlp_x6", [t for t in (pi.weight, pi.bias, dw.weight, dw.bias, po.weight, po.bias) if t is not None], prep)
-            return ops.gdmlp_x6(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wg, bg, w10, Wo, bo, Hd)
+            return ops.gdmlp_x6(x, norm.weight.detach(), norm.bias.detach(), norm.eps, Wg, bg, w10, Wo, bo, Hd, pre=pre)
+        if pre is not None:
+            raise BemNativeError("gdMlp: the SS2D tail can be folded into the one-kernel branch only")
         return self.chain(x, norm)[0]
 
     def chain(self, x, norm: LayerNorm2d):
@@ -292,10 +298,16 @@ class SS2D(nn.Module):
                     self.Ds.detach().float().contiguous())
         return ops.derived(self).get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
 
-    def forward_fused(self, x, norm: LayerNorm2d, keep=False):
+    def tail_deferrable(self, C):
+        """out_norm + out_proj + residual can run inside the kernel of the block's gdMlp branch (bem_vss_back_x6_f32): deterministic
+        out_proj weights (a Bayesian leaf has one set per sample) and d_inner == d_model."""
+        return type(self.out_proj) is Linear2d and self.d_inner == C
+
+    def forward_fused(self, x, norm: LayerNorm2d, keep=False, defer_tail=False):
         """x + out_proj(out_norm(y0 + y1)), (y0, y1) = scan(SiLU(dw(in_proj(LN(x)))))  (vmamba.py:700-716 + 547-698), for every d_state.
         keep=True (the training forward, VSSBlockFn) returns (out, (t, xc, xd, xd1, y0, y1)): the intermediates the backward
-        reads, y0 / y1 row-major (B, Ci, H, W)."""
+        reads, y0 / y1 row-major (B, Ci, H, W).  defer_tail=True returns no output but the ``pre`` operands of ops.gdmlp_x6:
+        (y0, y1, out_norm weight, bias, eps, packed row-permuted out_proj weight, out_proj bias)."""
         B, C, H, W = x.shape
         Ci, R, N, L = self.d_inner, self.dt_rank, self.d_state, H * W
         M = R + 2 * N                                    # x_dbl rows per direction: [dt_0..dt_{R-1} | B_0..B_{N-1} | C_0..C_{N-1}]
@@ -330,8 +342,12 @@ class SS2D(nn.Module):
             else:
                 y0, y1 = ops.ss2d_scan(x0, x1, xd0v, xd1v, dtw, dtb, A, Ds)
             y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1.view(B, Ci, W, H))
-        Wp, b = self.out_proj.gemm_weights(B)
         on = self.out_norm
+        if defer_tail:
+            op = self.out_proj
+            Wpp = ops.derived(self).get("vss_back", [op.weight], lambda: ops.pack_vss_back_outproj(op.weight.detach()))
+            return y0, y1, on.weight.detach(), on.bias.detach(), on.eps, Wpp, (op.bias.detach() if op.bias is not None else None)
+        Wp, b = self.out_proj.gemm_weights(B)
         out = ops.pw_gemm(y0, Wp, _out_features(self.out_proj), x2=y1, in_mode=1,
                           ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
         return (out, (t, xc, xd, xd1, y0, y1)) if keep else out
@@ -362,6 +378,11 @@ class VSSBlock(nn.Module):
         if grad_mode(self):
             return ag.vssblock(self, x)
         x = x.contiguous()
+        C = x.shape[1]
+        # the SS2D tail inside the gdMlp kernel: x1 = x + out_proj(out_norm(y0 + y1)) is never written
+        if ops.USE_VSS_BACK and self.op.tail_deferrable(C) and self.mlp.fused_supported(C) \
+                and ops.vss_back_supported(C, self.mlp.project_in.out_channels // 2):
+            return self.mlp.forward_fused(x, self.norm2, pre=self.op.forward_fused(x, self.norm, defer_tail=True))
         x = self.op.forward_fused(x, self.norm)
         return self.mlp.forward_fused(x, self.norm2)
 

@@ -62,7 +62,8 @@ _KEYS = {
     # (HBM: 42 us at level 0) -- but its two GEMMs (2Hd x C and C x Hd per pixel) evaluated as six bf16 limb products are 242 GFLOP on the
     # matrix cores (97 us at the dense bf16 peak): the matrix pipe is the roofline that bounds it.  flops = 6 x the f32 GEMM flops
     # (what the x6 scheme must issue for the output pixels; halo and padding MFMAs are waste, not work).
-    "gdmlp_x6<3>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<3, 2, 2, false>", lambda C: 32 < C <= 48),
+    # In the eval step the level-0 launches carry the SS2D tail as well (``pre``): vss_back_x6_kernel, + y0, y1 in and the C x C out_proj GEMM.
+    "gdmlp_x6<3>": ("gdmlp_x6", "mfma_bf16", "vss_back_x6_kernel<3, 2, 2> (with the SS2D tail; gdmlp_x6_kernel<3, 2, 2, false> without)", lambda C: 32 < C <= 48),
     "gdmlp_x6<5>": ("gdmlp_x6", "mfma_bf16", "gdmlp_x6_kernel<5, 3, 1, false>", lambda C: 64 < C <= 80),
     "conv2d": ("conv2d", "mfma", "conv2d_kernel", None),
     "dwconv3x3": ("dwconv3x3", "hbm", "dwconv3x3_kernel", None),
@@ -591,16 +592,56 @@ def dw_gate_params10(dww, dwb, Hd):
     return torch.cat([w, b], 1).contiguous()
 
 
-def _gdmlp_x6_cost(x, Hd, **_):
+# The SS2D tail folded into the fused gdMlp kernel (bem_vss_back_x6_f32): a test reaches the two-kernel chain by switching it off.
+# C > 48 stays on the chain: the wider forms of the kernel spill in their prologue.
+USE_VSS_BACK = True
+
+
+def vss_back_supported(C, Hd):
+    return C <= 48 and C % 8 == 0 and Hd % 16 == 0
+
+
+def vss_back_rows(C):
+    """Row order of the out_proj operand of bem_vss_back_x6_f32, as a list over the 32 MT packed rows: the out_proj row (channel) that
+    packed row holds, or -1 for a zero row.  Accumulator register r of M-tile mt in lane half kh is packed row
+    32 mt + (r & 3) + 8 (r >> 2) + 4 kh; as slot s = 16 mt + r of the lane it must be channel 16 (s >> 3) + 8 kh + (s & 7), the
+    channel the lane holds there as the B operand of project_in."""
+    KB = (C + 15) // 16
+    MT = (8 * KB + 15) // 16
+    rows = [-1] * (32 * MT)
+    for mt in range(MT):
+        for kh in range(2):
+            for r in range(16):
+                s = 16 * mt + r
+                ch = 16 * (s >> 3) + 8 * kh + (s & 7)
+                if s < 8 * KB and ch < C:
+                    rows[32 * mt + (r & 3) + 8 * (r >> 2) + 4 * kh] = ch
+    return rows
+
+
+def pack_vss_back_outproj(W):
+    """(C, C) out_proj weight -> the x6-packed, row-permuted operand Wp_outproj of bem_vss_back_x6_f32."""
+    C = W.shape[0]
+    rows = torch.tensor(vss_back_rows(C), device=W.device)
+    Wz = torch.cat([W, W.new_zeros(1, W.shape[1])], 0)              # index -1 = the zero row
+    return pack_pw_weight(Wz[rows].contiguous(), x6=True)
+
+
+def _gdmlp_x6_cost(x, Hd, pre, **_):
     B, C, H, W = x.shape
-    return 8.0 * x.numel(), 6.0 * 2.0 * B * H * W * (2 * Hd * C + Hd * C)
+    nb, nf = 8.0 * x.numel(), 6.0 * 2.0 * B * H * W * (2 * Hd * C + Hd * C)
+    if pre is not None:                                             # + y0, y1 in and the C x C out_proj GEMM
+        nb, nf = nb + 8.0 * x.numel(), nf + 6.0 * 2.0 * B * H * W * C * C
+    return nb, nf
 
 
 @_bracket(_gdmlp_x6_cost, lambda x, **_: (x.shape[1],))
-def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, Hd):
+def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, Hd, *, pre=None):
     """x + project_out(GELU(h1) * h2) + b_o with [h1; h2] = dw3x3(project_in(LayerNorm2d(x))) in ONE kernel (bem_gdmlp_x6_f32).
     Wp_gate = pack_pw_weight(W_i[gate_interleave(Hd)], x6=True), bias_gate = b_i[gate_interleave(Hd)] (zeros without a bias);
-    dw10 = dw_gate_params10(...); Wp_out = pack_pw_weight(W_o, x6=True)."""
+    dw10 = dw_gate_params10(...); Wp_out = pack_pw_weight(W_o, x6=True).
+    pre = (y0, y1, on_w, on_b, on_eps, Wp_outproj, bias_outproj): x is the SS2D branch's input and the branch is applied to
+    x1 = x + out_proj(out_norm(y0 + y1)) + bias_outproj, formed inside the kernel (bem_vss_back_x6_f32; Wp_outproj = pack_vss_back_outproj(W_op))."""
     for n_, t in (("x", x), ("ln_w", ln_w), ("ln_b", ln_b), ("Wp_gate", Wp_gate), ("bias_gate", bias_gate), ("dw10", dw10), ("Wp_out", Wp_out)):
         _chk(t, n_)
     _chk(bias_out, "bias_out", optional=True)
@@ -613,6 +654,20 @@ def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, 
         raise ValueError("gdmlp_x6: parameter shapes")
     _chk_packed1("gdmlp_x6", (("Wp_gate", Wp_gate, 2 * Hd, C), ("Wp_out", Wp_out, C, Hd)))
     out = torch.empty_like(x)
+    if pre is not None:
+        y0, y1, on_w, on_b, on_eps, Wp_op, b_op = pre
+        for n_, t in (("y0", y0), ("y1", y1), ("on_w", on_w), ("on_b", on_b), ("Wp_outproj", Wp_op)):
+            _chk(t, n_)
+        _chk(b_op, "bias_outproj", optional=True)
+        if not vss_back_supported(C, Hd):
+            raise ValueError(f"gdmlp_x6 with pre: C = {C} (<= 48, % 8) not supported")
+        if y0.shape != x.shape or y1.shape != x.shape or on_w.numel() != C or on_b.numel() != C or (b_op is not None and b_op.numel() != C):
+            raise ValueError("gdmlp_x6 with pre: y0 / y1 must have the shape of x, out_norm and the out_proj bias C entries")
+        _chk_packed1("gdmlp_x6", (("Wp_outproj", Wp_op, 32 * ((8 * ((C + 15) // 16) + 15) // 16), C),))      # len(vss_back_rows(C)) rows
+        check(lib().bem_vss_back_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_gate), _p(bias_gate), _p(dw10), _p(Wp_out),
+                                        _p(bias_out), _p(out), B, C, Hd, H, W, _p(y0), _p(y1), _p(on_w), _p(on_b), float(on_eps),
+                                        _p(Wp_op), _p(b_op), _stream()), "gdmlp_x6")
+        return out
     check(lib().bem_gdmlp_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_gate), _p(bias_gate), _p(dw10), _p(Wp_out),
                                  _p(bias_out), _p(out), B, C, Hd, H, W, _stream()), "gdmlp_x6")
     return out

@@ -26,6 +26,12 @@
 //     the bias reads of phase A ahead of its T stores.
 //   * epilogue: + b_o + x (residual), 128-byte row segments per half-wave.
 // Two barriers per chunk.
+//
+// vss_back_x6_kernel is the same body behind another prologue: x is the input of the block's SS2D branch, and
+//     x1 = x + W_op * LayerNorm2d(y0 + y1) + b_op      (the SS2D tail, vmamba.py:700-716; y0, y1 the scan outputs)
+// takes the place of x above.  Each wave forms x1 of its halo blocks in registers (one more GEMM on the matrix cores, its rows permuted by
+// the host so that no value changes lanes); the tile's own pixels of x1 wait in `out` for the epilogue.  x1 is written and read by no
+// other kernel: 2 x 4 C P bytes and one launch less per block than the tail GEMM followed by gdmlp_x6_kernel.
 #include "bem_common.h"
 #include "x6_tile.h"
 
@@ -39,6 +45,19 @@ struct GdX {
     const float* dw10;          // depthwise taps + bias per gate channel: [Hd][10] (w1, w2) pairs, slot 9 = (b1, b2)
     int C, Hd, H, W, NCH, tx;
 };
+
+// The SS2D tail that vss_back_x6_kernel evaluates ahead of the branch: x1 = x + W_op LayerNorm2d(y0 + y1) + b_op  (vmamba.py:700-716)
+struct GdPre {
+    const float* y0; const float* y1; const float* on_w; const float* on_b; float on_eps;
+    const u32x4* Wop;           // out_proj rows in the order of ops.vss_back_rows, x6-packed [MTP][KB][3][64]
+    const float* bop; float bopmul;   // out_proj bias (an always-present array times zero when the layer has none)
+};
+
+// base[byte / 4] with a 32-bit byte offset: a wave-uniform base and one VGPR per address, where 64-bit per-lane addresses for the four
+// tensors of the fused prologue took two registers each (C H W < 2^30 is checked on the host)
+__device__ __forceinline__ float at_byte(const float* base, uint32_t byte) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte);
+}
 
 constexpr int GD_GS = 20;                            // dwords per pixel row of G (16 + 4: conflict-free b128 writes and reads)
 
@@ -58,8 +77,10 @@ __device__ __forceinline__ float gelu_gate1(float a, float b) {
     return fmaf(h, copysignf(r, a), h) * b;
 }
 
-template <int KBM, int MTO, int WOB, bool PL2>
-__global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
+// One tile of the branch: the body of both kernels below.  PRE = false: xn = LayerNorm2d(x) of the halo blocks and the residual come from k.x.
+// PRE = true: k.x is the SS2D branch's input and x1 (above) is formed first, on the halo as well -- every workgroup recomputes its own.
+template <int KBM, int MTO, int WOB, bool PL2, bool PRE>
+__device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
     constexpr int NPI = 3 * KBM, NPO = 3 * MTO;                                        // 1 KiB pieces of a W_i / W_o chunk
     __shared__ __attribute__((aligned(16))) f32x2 T[16 * XT_TS];                       // [gate channel c][halo pixel] = (h1 input, h2 input)
     __shared__ __attribute__((aligned(16))) float G[128 * GD_GS];                      // [tile pixel][16 gate channels (+4 pad)]
@@ -100,6 +121,18 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
         }
     };
     dma_in(0, 0);
+    // PRE: out_proj's packed rows (MTP M-tiles of 32: 16 accumulator registers per lane and tile take the lane's 8 KBM channels) travel the
+    // same way, once per workgroup, into T, which is dead until phase A of chunk 0 (18 KB at C <= 48 of T's 26 KB)
+    constexpr int MTP = (8 * KBM + 15) / 16, NPW = 3 * KBM * MTP;
+    static_assert(!PRE || NPW * 1024 <= (int)sizeof(T), "out_proj's rows must fit into T");
+    if (PRE) {
+        const uint32_t t_lds = lds_addr(T);
+#pragma unroll
+        for (int t = 0; t < (NPW + 3) / 4; ++t) {
+            const int p = wave + 4 * t;
+            if (p < NPW) glds16(pre.Wop + p * 64, voff, t_lds + p * 1024);
+        }
+    }
 
     // phase-C geometry: wave = tile row, lane (n, kh) = pixel n, k-half kh
     const int oy = y0 + wave, ox = x0 + n;
@@ -109,7 +142,8 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     const bool opix = oy < k.H && ox < k.W;
     const int64_t po = (int64_t)min(oy, k.H - 1) * k.W + min(ox, k.W - 1);
     auto load_res = [&]() {
-        const float* rb = xb + po;
+        // PRE: the residual is x1, which the prologue left at the tile's own pixels of out (this workgroup's stores, behind its barriers)
+        const float* rb = (PRE ? out + (int64_t)b * k.C * L : xb) + po;
 #pragma unroll
         for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
@@ -126,15 +160,31 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     int hpo[2];
     {
         float lnw[KBM][8], lnb[KBM][8];
+        auto load_ln = [&]() {
 #pragma unroll
-        for (int kb = 0; kb < KBM; ++kb)
+            for (int kb = 0; kb < KBM; ++kb)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int ch = 16 * kb + 8 * kh + e;
-                const float on = ch < k.C ? 1.f : 0.f;
-                lnw[kb][e] = k.ln_w[min(ch, k.C - 1)] * on;
-                lnb[kb][e] = k.ln_b[min(ch, k.C - 1)] * on;
+                for (int e = 0; e < 8; ++e) {
+                    const int ch = 16 * kb + 8 * kh + e;
+                    const float on = ch < k.C ? 1.f : 0.f;
+                    lnw[kb][e] = k.ln_w[min(ch, k.C - 1)] * on;
+                    lnb[kb][e] = k.ln_b[min(ch, k.C - 1)] * on;
+                }
+        };
+        if (!PRE) load_ln();
+        auto load_ln_pre = [&]() {                       // PRE fetches them per block (registers are short there), addressed like its tensors
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb) {
+                const int cb = 16 * kb + 8 * kh;
+                const float on = cb < k.C ? 1.f : 0.f;
+                const uint32_t cbc = cb < k.C ? cb : 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    lnw[kb][e] = at_byte(k.ln_w + e, 4u * cbc) * on;
+                    lnb[kb][e] = at_byte(k.ln_b + e, 4u * cbc) * on;
+                }
             }
+        };
         // PL2: every global load of the prologue is requested before the first value is used.  Measured in the eval step (HIP events of
         // bench.py, profiles/r03_gdmlp_insitu_variants.txt): 665 us against 651 us for one block after the other -- off
         float xr[2][KBM][8];
@@ -183,7 +233,134 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
                 split8(v, xl[i][kb][0], xl[i][kb][1], xl[i][kb][2]);
             }
         };
-        if (PL2) { load_block(0); load_block(1); norm_block(0); norm_block(1); }
+        // PRE: x1 of a halo block in load_block's layout.  out_norm(y0 + y1) with norm_block's arithmetic becomes the B operand; the packed
+        // row 32 mt + acc_row(r, kh) of W_op is channel 16 (s >> 3) + 8 kh + (s & 7), s = 16 mt + r (ops.vss_back_rows), so accumulator
+        // register s of a lane is the channel its xr[i][s >> 3][s & 7] holds: + bias + x there, no exchange between lanes.
+        // C % 8 == 0 here (host check): a lane's eight channels of a k-block are all inside C or all padding, and one address register per
+        // k-block serves the four tensors (wave-uniform bases, 32-bit byte offsets).
+        u32x4 yl[KBM][3];
+        const float* const y0b = pre.y0 + (int64_t)b * k.C * L;
+        const float* const y1b = pre.y1 + (int64_t)b * k.C * L;
+        const uint32_t L4 = 4u * (uint32_t)L;
+        auto tail_load = [&](int i) {
+            const int hp = min((wave + 4 * i) * 32 + n, XT_TS - 1);
+            hpo[i] = hp;
+            const int hy = hp / XT_HW, hx = hp - hy * XT_HW;
+            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+            const bool in = hp < XT_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < XT_NPB;
+            msk[i] = in ? 1.f : 0.f;
+            mbit[i] = in ? 0xffffffffu : 0u;
+            const int off = min(max(gy, 0), k.H - 1) * k.W + min(max(gx, 0), k.W - 1);
+            float ys[KBM][8];
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb) {
+                const int cb = 16 * kb + 8 * kh;
+                const bool von = cb < k.C;
+                const uint32_t a = 4u * (uint32_t)((von ? cb : 0) * L + off);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v = at_byte(y0b, a + e * L4) + at_byte(y1b, a + e * L4);
+                    ys[kb][e] = von ? v : 0.f;
+                }
+            }
+            const float inv = 1.f / (float)k.C;
+            float s = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += ys[kb][e];
+            s += __shfl_xor(s, 32, 64);
+            const float mean = s * inv;
+            float q = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = (16 * kb + 8 * kh < k.C) ? ys[kb][e] - mean : 0.f;
+                    q = fmaf(d, d, q);
+                }
+            q += __shfl_xor(q, 32, 64);
+            const float rstd = 1.f / sqrtf(q * inv + pre.on_eps);
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb) {
+                const int cb = 16 * kb + 8 * kh;
+                const float on = cb < k.C ? 1.f : 0.f;
+                const uint32_t cbc = cb < k.C ? cb : 0;
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = ((ys[kb][e] - mean) * rstd) * (at_byte(pre.on_w + e, 4u * cbc) * on) + at_byte(pre.on_b + e, 4u * cbc) * on;
+                split8(v, yl[kb][0], yl[kb][1], yl[kb][2]);
+            }
+        };
+        auto tail_gemm = [&](int i) {
+            const int hp = hpo[i];
+            const int hy = hp / XT_HW, hx = hp - hy * XT_HW;
+            // the tile's own pixels (inside the image): x1 goes to out, where the epilogue finds its residual
+            const bool ctr = mbit[i] != 0u && hy >= 1 && hy <= XT_TH && hx >= 1 && hx <= XT_TW;
+            const int off = min(max(y0 - 1 + hy, 0), k.H - 1) * k.W + min(max(x0 - 1 + hx, 0), k.W - 1);
+            float* const ob = out + (int64_t)b * k.C * L;
+            float xv[KBM][8];                                                          // the residual: requested ahead of the matrix work
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb) {
+                const int cb = 16 * kb + 8 * kh;
+                const uint32_t a = 4u * (uint32_t)((cb < k.C ? cb : 0) * L + off);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) xv[kb][e] = at_byte(xb, a + e * L4);
+            }
+#pragma unroll
+            for (int mt = 0; mt < MTP; ++mt) {
+                f32x16 hi = zero16(), lo = zero16();
+#pragma unroll
+                for (int kb = 0; kb < KBM; ++kb) {
+                    const u32x4* wp = reinterpret_cast<const u32x4*>(T) + (mt * KBM + kb) * 192 + lane;
+                    const u32x4 wl[3] = {wp[0], wp[64], wp[128]};
+                    mac6(wl, yl[kb], hi, lo);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int s = 16 * mt + r, kb = s >> 3, e = s & 7, cb = 16 * kb + 8 * kh;
+                    if (s < 8 * KBM) {
+                        const float v = (hi[r] + lo[r]) + at_byte(pre.bop + e, 4u * (uint32_t)(cb < k.C ? cb : 0)) * pre.bopmul + xv[kb][e];
+                        xr[i][kb][e] = cb < k.C ? v : 0.f;
+                    }
+                }
+            }
+            if (ctr) {
+#pragma unroll
+                for (int kb = 0; kb < KBM; ++kb) {
+                    const int cb = 16 * kb + 8 * kh;
+                    if (cb < k.C) {
+                        const uint32_t a = 4u * (uint32_t)(cb * L + off);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) *reinterpret_cast<float*>(reinterpret_cast<char*>(ob) + (a + e * L4)) = xr[i][kb][e];
+                    }
+                }
+            }
+        };
+        if (PRE) {
+            // one step after the other (sched_barrier): scheduled as one region the C <= 48 form spills 96 bytes
+            tail_load(0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                            // W_op has landed in T (the DMA is ahead of these loads)
+            __syncthreads();
+            __builtin_amdgcn_sched_barrier(0);
+            tail_gemm(0);
+            __builtin_amdgcn_sched_barrier(0);
+            load_ln_pre();
+            norm_block(0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (wave + 4 < XT_NPB) {                                                   // wave-uniform: wave 3 has one block
+                tail_load(1);
+                __builtin_amdgcn_sched_barrier(0);
+                tail_gemm(1);
+                __builtin_amdgcn_sched_barrier(0);
+                load_ln_pre();
+                norm_block(1);
+            } else {
+                msk[1] = 0.f; mbit[1] = 0u; hpo[1] = XT_TS - 1;
+#pragma unroll
+                for (int kb = 0; kb < KBM; ++kb) xl[1][kb][0] = xl[1][kb][1] = xl[1][kb][2] = u32x4{0u, 0u, 0u, 0u};
+            }
+        } else if (PL2) { load_block(0); load_block(1); norm_block(0); norm_block(1); }
         else { load_block(0); norm_block(0); load_block(1); norm_block(1); }
     }
 
@@ -310,18 +487,38 @@ __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __
     }
 }
 
-}  // namespace
 
-extern "C" int bem_gdmlp_x6_f32(const float* x, const float* ln_w, const float* ln_b, float ln_eps, const float* Wp_gate,
-                                const float* bias_gate, const float* dw_gate10, const float* Wp_out,
-                                const float* bias_out, float* out, int B, int C, int Hd, int H, int W, void* stream) {
-    BEM_REQUIRE(x && ln_w && ln_b && Wp_gate && bias_gate && dw_gate10 && Wp_out && out, "gdmlp_x6: null tensor");
+template <int KBM, int MTO, int WOB, bool PL2>
+__global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
+    gdmlp_x6_tile<KBM, MTO, WOB, PL2, false>(k, GdPre{}, bpo, bomul, out);
+}
+
+// The back half of a VSSBlock: the SS2D tail (out_norm + out_proj + bias + residual of the scan outputs y0, y1) and the gdMlp branch.
+// x1 is never a tensor: the halo blocks form it in registers, the tile's own pixels park it in out for the epilogue.
+template <int KBM, int MTO, int WOB>
+__global__ __launch_bounds__(256, 2) void vss_back_x6_kernel(GdX k, GdPre pre, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
+    gdmlp_x6_tile<KBM, MTO, WOB, false, true>(k, pre, bpo, bomul, out);
+}
+
+// checks and launch of both entry points; pre = nullptr: the gdMlp branch alone
+int gd_launch(const char* op, const float* x, const float* ln_w, const float* ln_b, float ln_eps, const float* Wp_gate, const float* bias_gate,
+              const float* dw_gate10, const float* Wp_out, const float* bias_out, float* out, int B, int C, int Hd, int H, int W,
+              const GdPre* pre, void* stream) {
+    BEM_REQUIRE(x && ln_w && ln_b && Wp_gate && bias_gate && dw_gate10 && Wp_out && out, "%s: null tensor", op);
     BEM_REQUIRE(B >= 0 && B <= 65535 && C > 0 && C <= 80 && Hd > 0 && Hd % 16 == 0 && H > 0 && W > 0,
-                "gdmlp_x6: needs C <= 80 and Hd %% 16 == 0 (got C = %d, Hd = %d)", C, Hd);
+                "%s: needs C <= 80 and Hd %% 16 == 0 (got C = %d, Hd = %d)", op, C, Hd);
     BEM_REQUIRE((((uintptr_t)Wp_gate | (uintptr_t)Wp_out | (uintptr_t)bias_gate | (uintptr_t)dw_gate10) & 15) == 0,
-                "gdmlp_x6: packed weights, bias pairs and depthwise parameters must be 16-byte aligned");
-    BEM_REQUIRE(x != out, "gdmlp_x6: in-place operation is not supported (halo reads)");
-    BEM_REQUIRE((int64_t)C * H * W < (1ll << 31), "gdmlp_x6: plane set too large for 32-bit offsets");
+                "%s: packed weights, bias pairs and depthwise parameters must be 16-byte aligned", op);
+    BEM_REQUIRE(x != out, "%s: in-place operation is not supported (halo reads)", op);
+    BEM_REQUIRE((int64_t)C * H * W < (1ll << 31), "%s: plane set too large for 32-bit offsets", op);
+    if (pre) {
+        BEM_REQUIRE(pre->y0 && pre->y1 && pre->on_w && pre->on_b && pre->Wop, "%s: null tensor", op);
+        BEM_REQUIRE(((uintptr_t)pre->Wop & 15) == 0, "%s: packed out_proj weights must be 16-byte aligned", op);
+        BEM_REQUIRE(out != pre->y0 && out != pre->y1, "%s: out must not be y0 or y1 (halo reads)", op);
+        BEM_REQUIRE((int64_t)C * H * W < (1ll << 30), "%s: plane set too large for 32-bit byte offsets", op);
+        // wider forms spill in the prologue (<4, 2, 2> 56 bytes, <5, 3, 1> 632 bytes at the 256-register budget): those blocks run the two kernels
+        BEM_REQUIRE(C % 8 == 0 && C <= 48, "%s: needs C %% 8 == 0 and C <= 48 (got C = %d)", op, C);
+    }
     if (B == 0) return BEM_OK;
     GdX k;
     k.x = x; k.ln_w = ln_w; k.ln_b = ln_b; k.ln_eps = ln_eps;
@@ -335,10 +532,36 @@ extern "C" int bem_gdmlp_x6_f32(const float* x, const float* ln_w, const float* 
     hipStream_t s = (hipStream_t)stream;
     const int KB = cdiv(C, 16);
     // two workgroups per CU in every variant (LDS: T 26 KB + G 10 KB + two W_i buffers + one or two W_o buffers <= 80 KB)
-    if (KB == 1) gdmlp_x6_kernel<1, 1, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
+    if (pre) {
+        if (KB == 1) vss_back_x6_kernel<1, 1, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
+        else if (KB == 2) vss_back_x6_kernel<2, 1, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
+        else vss_back_x6_kernel<3, 2, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
+    }
+    else if (KB == 1) gdmlp_x6_kernel<1, 1, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     else if (KB == 2) gdmlp_x6_kernel<2, 1, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     else if (KB == 3) gdmlp_x6_kernel<3, 2, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     else if (KB == 4) gdmlp_x6_kernel<4, 2, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     else gdmlp_x6_kernel<5, 3, 1, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
-    return bem_check_launch("gdmlp_x6");
+    return bem_check_launch(op);
+}
+
+}  // namespace
+
+extern "C" int bem_gdmlp_x6_f32(const float* x, const float* ln_w, const float* ln_b, float ln_eps, const float* Wp_gate,
+                                const float* bias_gate, const float* dw_gate10, const float* Wp_out,
+                                const float* bias_out, float* out, int B, int C, int Hd, int H, int W, void* stream) {
+    return gd_launch("gdmlp_x6", x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw_gate10, Wp_out, bias_out, out, B, C, Hd, H, W, nullptr, stream);
+}
+
+extern "C" int bem_vss_back_x6_f32(const float* x, const float* ln_w, const float* ln_b, float ln_eps, const float* Wp_gate,
+                                   const float* bias_gate, const float* dw_gate10, const float* Wp_out,
+                                   const float* bias_out, float* out, int B, int C, int Hd, int H, int W,
+                                   const float* y0, const float* y1, const float* on_w, const float* on_b, float on_eps,
+                                   const float* Wp_outproj, const float* bias_outproj, void* stream) {
+    GdPre pre;
+    pre.y0 = y0; pre.y1 = y1; pre.on_w = on_w; pre.on_b = on_b; pre.on_eps = on_eps;
+    pre.Wop = reinterpret_cast<const u32x4*>(Wp_outproj);
+    pre.bop = bias_outproj ? bias_outproj : ln_w;
+    pre.bopmul = bias_outproj ? 1.f : 0.f;
+    return gd_launch("vss_back_x6", x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw_gate10, Wp_out, bias_out, out, B, C, Hd, H, W, &pre, stream);
 }

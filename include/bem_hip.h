@@ -413,6 +413,20 @@ int bem_gdmlp_x6_f32(const float* x, const float* ln_w, const float* ln_b, float
                      const float* bias_gate, const float* dw_gate10, const float* Wp_out,
                      const float* bias_out, float* out, int B, int C, int Hd, int H, int W, void* stream);
 
+/* The back half of a VSSBlock in one kernel: the SS2D tail (vmamba.py:700-716 after the scan) and the gdMlp branch above,
+ *   x1 = x + W_op LayerNorm2d(y0 + y1) + b_op,   out = x1 + W_o (GELU(h[0:Hd]) * h[Hd:2Hd]) + b_o,   h = dw3x3(W_i LayerNorm2d(x1) + b_i) + b_dw.
+ * x1 is never a tensor: every tile forms it on its halo as well, and parks its own pixels in out for the residual.  The first sixteen
+ * arguments are those of bem_gdmlp_x6_f32, x now the SS2D branch's input; y0 / y1 (B,C,H,W) the two scan outputs (d_inner == C), on_w / on_b (C)
+ * and on_eps the out_norm parameters, bias_outproj (C) | NULL.  C <= 48, C % 8 == 0, C H W < 2^30; out differs from x, y0 and y1.
+ * Wp_outproj = bem_pack_pw_weight_x6 of a (32 MT, C) matrix, MT = ceil(ceil(C / 16) / 2), whose row 32 mt + (r & 3) + 8 (r >> 2) + 4 kh
+ * (r < 16, kh < 2) is W_op[16 (s >> 3) + 8 kh + (s & 7)] with s = 16 mt + r, and zero where s >= 8 ceil(C / 16) or that channel is >= C
+ * (bem.ops.vss_back_rows): the accumulator register of a lane then holds the channel the lane needs as the next GEMM's operand.  16-byte aligned. */
+int bem_vss_back_x6_f32(const float* x, const float* ln_w, const float* ln_b, float ln_eps, const float* Wp_gate,
+                        const float* bias_gate, const float* dw_gate10, const float* Wp_out,
+                        const float* bias_out, float* out, int B, int C, int Hd, int H, int W,
+                        const float* y0, const float* y1, const float* on_w, const float* on_b, float on_eps,
+                        const float* Wp_outproj, const float* bias_outproj, void* stream);
+
 /* SS2D front half in one kernel (vmamba.py:700-716 up to the scan, with the block's norm :1326):
  *   xc (B,C,H,W) = SiLU(dw3x3(W_in LayerNorm2d(x) + b_in) + b_dw),   xd (B,Mx,H*W) = W_x xc  (Mx = 4 (R + 2): the x_dbl rows of all four directions).
  * The in_proj output exists only as a 4 x 32 pixel tile (+ halo) in LDS.  x (B,C,H,W) with C <= 48, C % 8 == 0, xc != x; ln_w / ln_b (C);
