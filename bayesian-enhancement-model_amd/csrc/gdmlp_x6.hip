@@ -53,13 +53,20 @@ struct GdPre {
     const float* bop; float bopmul;   // out_proj bias (an always-present array times zero when the layer has none)
 };
 
-// base[byte / 4] with a 32-bit byte offset: a wave-uniform base and one VGPR per address, where 64-bit per-lane addresses for the four
-// tensors of the fused prologue took two registers each (C H W < 2^30 is checked on the host)
-__device__ __forceinline__ float at_byte(const float* base, uint32_t byte) {
+// base[byte / 4] with a 32-bit byte offset: a wave-uniform base and one VGPR per address, where 64-bit per-lane addresses took two
+// registers and a 64-bit add each.  Every tensor access of the tile goes through these two: OFF = uint32_t where the host has checked
+// C H W < 2^30, OFF = uint64_t (the same source, 64-bit arithmetic) in the *_wide entry points for larger planes.
+template <typename OFF>
+__device__ __forceinline__ float at_byte(const float* base, OFF byte) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte);
+}
+template <typename OFF>
+__device__ __forceinline__ void put_byte(float* base, OFF byte, float v) {
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte) = v;
 }
 
 constexpr int GD_GS = 20;                            // dwords per pixel row of G (16 + 4: conflict-free b128 writes and reads)
+constexpr bool GD_LO_PERSIST = true;                 // see LOP in gdmlp_x6_tile; false restores the per-chunk join (bit-identical to it)
 
 // GELU(a) * b (erf by Abramowitz & Stegun 7.1.26 on the hardware rcp / exp2, as bem_gelu_fast).  Scalar f32 instructions on purpose:
 // on gfx950 a v_pk_*_f32 instruction does not overlap with another wave's MFMAs on the same SIMD, plain v_fma_f32 / v_exp_f32 do
@@ -79,7 +86,10 @@ __device__ __forceinline__ float gelu_gate1(float a, float b) {
 
 // One tile of the branch: the body of both kernels below.  PRE = false: xn = LayerNorm2d(x) of the halo blocks and the residual come from k.x.
 // PRE = true: k.x is the SS2D branch's input and x1 (above) is formed first, on the halo as well -- every workgroup recomputes its own.
-template <int KBM, int MTO, int WOB, bool PL2, bool PRE>
+// The launcher picks KBM = ceil(C / 16): channels below 16 (KBM - 1) exist in every call of an instantiation and rows from 16 KBM on in
+// none, so only the last k-block / the last 16 output rows carry clamps, selects and store predicates (the tests on kb and on the row of
+// lane half 0 are constants in the unrolled loops).
+template <int KBM, int MTO, int WOB, bool PL2, bool PRE, typename OFF = uint32_t>
 __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
     constexpr int NPI = 3 * KBM, NPO = 3 * MTO;                                        // 1 KiB pieces of a W_i / W_o chunk
     __shared__ __attribute__((aligned(16))) f32x2 T[16 * XT_TS];                       // [gate channel c][halo pixel] = (h1 input, h2 input)
@@ -140,16 +150,23 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
     // ahead of the last phase C
     f32x16 rs[MTO];
     const bool opix = oy < k.H && ox < k.W;
-    const int64_t po = (int64_t)min(oy, k.H - 1) * k.W + min(ox, k.W - 1);
+    const OFF L4 = (OFF)4 * (OFF)L;
+    // byte offset of (row 4 kh, this lane's pixel) in an image, and of the pixel in the last row C - 1 (the clamp of the last 16 rows)
+    const OFF pix4 = (OFF)4 * (OFF)(min(oy, k.H - 1) * k.W + min(ox, k.W - 1));
+    const OFF po4 = pix4 + (OFF)(4 * kh) * L4, pomax = pix4 + (OFF)(k.C - 1) * L4;
     auto load_res = [&]() {
         // PRE: the residual is x1, which the prologue left at the tile's own pixels of out (this workgroup's stores, behind its barriers)
-        const float* rb = (PRE ? out + (int64_t)b * k.C * L : xb) + po;
+        const float* rb = PRE ? out + (int64_t)b * k.C * L : xb;
 #pragma unroll
         for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = min(acc_row(r, kh, 32 * mt), k.C - 1);
-                rs[mt][r] = fmaf(bpo[row], bomul, rb[(int64_t)row * L]);
+                const int ru = acc_row(r, 0, 32 * mt);                                 // the row of lane half 0; + 4 kh is in po4
+                if (ru + 4 <= 16 * (KBM - 1)) rs[mt][r] = fmaf(at_byte(bpo + ru, (uint32_t)(16 * kh)), bomul, at_byte(rb, po4 + (OFF)ru * L4));
+                else if (ru < 16 * KBM) {
+                    const int row = min(ru + 4 * kh, k.C - 1);
+                    rs[mt][r] = fmaf(at_byte(bpo, (uint32_t)(4 * row)), bomul, at_byte(rb, min(po4 + (OFF)ru * L4, pomax)));
+                }                                                                      // rows from 16 KBM on are never stored
             }
     };
 
@@ -166,9 +183,15 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int ch = 16 * kb + 8 * kh + e;
-                    const float on = ch < k.C ? 1.f : 0.f;
-                    lnw[kb][e] = k.ln_w[min(ch, k.C - 1)] * on;
-                    lnb[kb][e] = k.ln_b[min(ch, k.C - 1)] * on;
+                    if (kb < KBM - 1) {
+                        lnw[kb][e] = at_byte(k.ln_w + 16 * kb + e, (uint32_t)(32 * kh));
+                        lnb[kb][e] = at_byte(k.ln_b + 16 * kb + e, (uint32_t)(32 * kh));
+                    } else {
+                        const float on = ch < k.C ? 1.f : 0.f;
+                        const uint32_t c4 = 4u * (uint32_t)min(ch, k.C - 1);
+                        lnw[kb][e] = at_byte(k.ln_w, c4) * on;
+                        lnb[kb][e] = at_byte(k.ln_b, c4) * on;
+                    }
                 }
         };
         if (!PRE) load_ln();
@@ -176,8 +199,9 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
             for (int kb = 0; kb < KBM; ++kb) {
                 const int cb = 16 * kb + 8 * kh;
-                const float on = cb < k.C ? 1.f : 0.f;
-                const uint32_t cbc = cb < k.C ? cb : 0;
+                const bool von = kb < KBM - 1 || cb < k.C;
+                const float on = von ? 1.f : 0.f;
+                const uint32_t cbc = von ? cb : 0;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     lnw[kb][e] = at_byte(k.ln_w + e, 4u * cbc) * on;
@@ -196,14 +220,18 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
             const bool in = hp < XT_NPH && gy >= 0 && gy < k.H && gx >= 0 && gx < k.W && (wave + 4 * i) < XT_NPB;
             msk[i] = in ? 1.f : 0.f;
             mbit[i] = in ? 0xffffffffu : 0u;
-            const int off = min(max(gy, 0), k.H - 1) * k.W + min(max(gx, 0), k.W - 1);
+            // one offset per lane (channel 8 kh of the pixel); the channel steps (16 kb + e) L4 are wave-uniform
+            const OFF off4 = (OFF)4 * (OFF)(min(max(gy, 0), k.H - 1) * k.W + min(max(gx, 0), k.W - 1));
+            const OFF a = off4 + (OFF)(8 * kh) * L4, amax = off4 + (OFF)(k.C - 1) * L4;
 #pragma unroll
             for (int kb = 0; kb < KBM; ++kb)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const int ch = 16 * kb + 8 * kh + e;
-                    const float v = xb[(int64_t)min(ch, k.C - 1) * L + off];
-                    xr[i][kb][e] = ch < k.C ? v : 0.f;
+                    if (kb < KBM - 1) xr[i][kb][e] = at_byte(xb, a + (OFF)(16 * kb + e) * L4);
+                    else {
+                        const float v = at_byte(xb, min(a + (OFF)(16 * kb + e) * L4, amax));
+                        xr[i][kb][e] = 16 * kb + 8 * kh + e < k.C ? v : 0.f;
+                    }
                 }
         };
         auto norm_block = [&](int i) {
@@ -220,7 +248,7 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
             for (int kb = 0; kb < KBM; ++kb)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float d = (16 * kb + 8 * kh + e < k.C) ? xr[i][kb][e] - mean : 0.f;
+                    const float d = (kb < KBM - 1 || 16 * kb + 8 * kh + e < k.C) ? xr[i][kb][e] - mean : 0.f;
                     q = fmaf(d, d, q);
                 }
             q += __shfl_xor(q, 32, 64);
@@ -241,7 +269,6 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
         u32x4 yl[KBM][3];
         const float* const y0b = pre.y0 + (int64_t)b * k.C * L;
         const float* const y1b = pre.y1 + (int64_t)b * k.C * L;
-        const uint32_t L4 = 4u * (uint32_t)L;
         auto tail_load = [&](int i) {
             const int hp = min((wave + 4 * i) * 32 + n, XT_TS - 1);
             hpo[i] = hp;
@@ -255,7 +282,7 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
             for (int kb = 0; kb < KBM; ++kb) {
                 const int cb = 16 * kb + 8 * kh;
-                const bool von = cb < k.C;
+                const bool von = kb < KBM - 1 || cb < k.C;
                 const uint32_t a = 4u * (uint32_t)((von ? cb : 0) * L + off);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -276,7 +303,7 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
             for (int kb = 0; kb < KBM; ++kb)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float d = (16 * kb + 8 * kh < k.C) ? ys[kb][e] - mean : 0.f;
+                    const float d = (kb < KBM - 1 || 16 * kb + 8 * kh < k.C) ? ys[kb][e] - mean : 0.f;
                     q = fmaf(d, d, q);
                 }
             q += __shfl_xor(q, 32, 64);
@@ -284,8 +311,9 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
             for (int kb = 0; kb < KBM; ++kb) {
                 const int cb = 16 * kb + 8 * kh;
-                const float on = cb < k.C ? 1.f : 0.f;
-                const uint32_t cbc = cb < k.C ? cb : 0;
+                const bool von = kb < KBM - 1 || cb < k.C;
+                const float on = von ? 1.f : 0.f;
+                const uint32_t cbc = von ? cb : 0;
                 float v[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = ((ys[kb][e] - mean) * rstd) * (at_byte(pre.on_w + e, 4u * cbc) * on) + at_byte(pre.on_b + e, 4u * cbc) * on;
@@ -303,7 +331,7 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
             for (int kb = 0; kb < KBM; ++kb) {
                 const int cb = 16 * kb + 8 * kh;
-                const uint32_t a = 4u * (uint32_t)((cb < k.C ? cb : 0) * L + off);
+                const uint32_t a = 4u * (uint32_t)((kb < KBM - 1 || cb < k.C ? cb : 0) * L + off);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) xv[kb][e] = at_byte(xb, a + e * L4);
             }
@@ -320,8 +348,9 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
                 for (int r = 0; r < 16; ++r) {
                     const int s = 16 * mt + r, kb = s >> 3, e = s & 7, cb = 16 * kb + 8 * kh;
                     if (s < 8 * KBM) {
-                        const float v = (hi[r] + lo[r]) + at_byte(pre.bop + e, 4u * (uint32_t)(cb < k.C ? cb : 0)) * pre.bopmul + xv[kb][e];
-                        xr[i][kb][e] = cb < k.C ? v : 0.f;
+                        const bool von = kb < KBM - 1 || cb < k.C;
+                        const float v = (hi[r] + lo[r]) + at_byte(pre.bop + e, 4u * (uint32_t)(von ? cb : 0)) * pre.bopmul + xv[kb][e];
+                        xr[i][kb][e] = von ? v : 0.f;
                     }
                 }
             }
@@ -329,10 +358,10 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 #pragma unroll
                 for (int kb = 0; kb < KBM; ++kb) {
                     const int cb = 16 * kb + 8 * kh;
-                    if (cb < k.C) {
+                    if (kb < KBM - 1 || cb < k.C) {
                         const uint32_t a = 4u * (uint32_t)(cb * L + off);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) *reinterpret_cast<float*>(reinterpret_cast<char*>(ob) + (a + e * L4)) = xr[i][kb][e];
+                        for (int e = 0; e < 8; ++e) put_byte(ob, a + e * L4, xr[i][kb][e]);
                     }
                 }
             }
@@ -368,11 +397,18 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
     const int wb_lds = 2 * kh * XT_HW + n;
     const int c_lo = 4 * wave;
 
-    f32x16 oh[MTO];
+    // project_out accumulators.  LOP: the small products of all chunks stay in `ol` and meet `oh` once, in the epilogue (mac6's design; 20
+    // VALU instructions less per chunk, 16 MTO registers more).  The three-row-block form has no registers to spare and joins per chunk.
+    constexpr bool LOP = GD_LO_PERSIST && MTO <= 2;
+    constexpr bool A2B = KBM <= 3;                     // phase A of both halo blocks in one pass over W_i: 32 more live accumulator registers
+    f32x16 oh[MTO], ol[MTO];                                                           // ol is dead without LOP
 #pragma unroll
     for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) oh[mt][r] = 0.f;
+        for (int r = 0; r < 16; ++r) {
+            oh[mt][r] = 0.f;
+            if (LOP) ol[mt][r] = 0.f;
+        }
 
     auto phase_c = [&](const u32x4* Wo) {
         const float* gp = G + (wave * 32 + n) * GD_GS + 8 * kh;
@@ -384,11 +420,14 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
         for (int mt = 0; mt < MTO; ++mt) {
             const u32x4* wp = Wo + mt * 192 + lane;
             const u32x4 wl[3] = {wp[0], wp[64], wp[128]};
-            f32x16 lo;
+            if constexpr (LOP) mac6(wl, gl, oh[mt], ol[mt]);
+            else {
+                f32x16 lo;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) lo[r] = 0.f;
-            mac6(wl, gl, oh[mt], lo);
-            oh[mt] += lo;
+                for (int r = 0; r < 16; ++r) lo[r] = 0.f;
+                mac6(wl, gl, oh[mt], lo);
+                oh[mt] += lo;
+            }
         }
     };
 
@@ -404,34 +443,59 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
         if (WOB == 2) dma_out(j, cur);
         const u32x4* const Wi = Wis[cur];
         // ---- phase A (chunk j) and phase C (chunk j - 1): matrix-core work
+        // accumulator rows 2(q&1) + 8(q>>1) + 4kh (+1) are the (h1, h2) inputs of gate channel c = (q&1) + 4(q>>1) + 2kh:
+        // the small-product accumulator starts from the channel's bias pair (zero outside the image: the conv pads t with zeros)
+        auto a_init = [&](int i, f32x16& hi, f32x16& lo) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (wave + 4 * i < XT_NPB) {                                               // wave-uniform
-                // accumulator rows 2(q&1) + 8(q>>1) + 4kh (+1) are the (h1, h2) inputs of gate channel c = (q&1) + 4(q>>1) + 2kh:
-                // the small-product accumulator starts from the channel's bias pair (zero outside the image: the conv pads t with zeros)
-                f32x16 hi, lo;
+            for (int q = 0; q < 8; ++q) {
+                const f32x2 bp = Bss[cur][(q & 1) + 4 * (q >> 1) + 2 * kh];
+                lo[2 * q] = bitsf(fbits(bp[0]) & mbit[i]);
+                lo[2 * q + 1] = bitsf(fbits(bp[1]) & mbit[i]);
+                hi[2 * q] = hi[2 * q + 1] = 0.f;
+            }
+        };
+        auto a_mac = [&](const u32x4 (&wl)[3], const u32x4 (&x)[3], f32x16& hi, f32x16& lo) {
+            hi = mfma16(wl[0], x[0], hi);
+            lo = mfma16(wl[0], x[2], lo);
+            lo = mfma16(wl[2], x[0], lo);
+            lo = mfma16(wl[1], x[1], lo);
+            lo = mfma16(wl[0], x[1], lo);
+            lo = mfma16(wl[1], x[0], lo);
+        };
+        auto a_store = [&](int i, const f32x16& hi, const f32x16& lo) {
+            f32x2* tp = T + 2 * kh * XT_TS + hpo[i];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const f32x2 bp = Bss[cur][(q & 1) + 4 * (q >> 1) + 2 * kh];
-                    lo[2 * q] = bitsf(fbits(bp[0]) & mbit[i]);
-                    lo[2 * q + 1] = bitsf(fbits(bp[1]) & mbit[i]);
-                    hi[2 * q] = hi[2 * q + 1] = 0.f;
+            for (int q = 0; q < 8; ++q)
+                tp[((q & 1) + 4 * (q >> 1)) * XT_TS] = f32x2{hi[2 * q] + lo[2 * q], hi[2 * q + 1] + lo[2 * q + 1]};
+        };
+        if (A2B && wave + 4 < XT_NPB) {                                                // wave-uniform: waves 0 .. 2 own two blocks
+            // both blocks per k-block: the W_i limbs are read from LDS once (each accumulator sees its products in the order it always did)
+            f32x16 hi0, lo0, hi1, lo1;
+            a_init(0, hi0, lo0);
+            a_init(1, hi1, lo1);
+#pragma unroll
+            for (int kb = 0; kb < KBM; ++kb) {
+                const u32x4* wp = Wi + kb * 192 + lane;
+                const u32x4 wl[3] = {wp[0], wp[64], wp[128]};
+                a_mac(wl, xl[0][kb], hi0, lo0);
+                a_mac(wl, xl[1][kb], hi1, lo1);
+            }
+            a_store(0, hi0, lo0);
+            a_store(1, hi1, lo1);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (wave + 4 * i < XT_NPB) {                                           // wave-uniform
+                    f32x16 hi, lo;
+                    a_init(i, hi, lo);
+#pragma unroll
+                    for (int kb = 0; kb < KBM; ++kb) {
+                        const u32x4* wp = Wi + kb * 192 + lane;
+                        const u32x4 wl[3] = {wp[0], wp[64], wp[128]};
+                        a_mac(wl, xl[i][kb], hi, lo);
+                    }
+                    a_store(i, hi, lo);
                 }
-#pragma unroll
-                for (int kb = 0; kb < KBM; ++kb) {
-                    const u32x4* wp = Wi + kb * 192 + lane;
-                    const u32x4 wl[3] = {wp[0], wp[64], wp[128]};
-                    hi = mfma16(wl[0], xl[i][kb][0], hi);
-                    lo = mfma16(wl[0], xl[i][kb][2], lo);
-                    lo = mfma16(wl[2], xl[i][kb][0], lo);
-                    lo = mfma16(wl[1], xl[i][kb][1], lo);
-                    lo = mfma16(wl[0], xl[i][kb][1], lo);
-                    lo = mfma16(wl[1], xl[i][kb][0], lo);
-                }
-                f32x2* tp = T + 2 * kh * XT_TS + hpo[i];
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    tp[((q & 1) + 4 * (q >> 1)) * XT_TS] = f32x2{hi[2 * q] + lo[2 * q], hi[2 * q + 1] + lo[2 * q + 1]};
             }
         }
         if (j) phase_c(Wos[(j - 1) & (WOB - 1)]);
@@ -475,14 +539,18 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
     phase_c(Wos[(k.NCH - 1) & (WOB - 1)]);
 
     // ---- epilogue: + bias + residual, rows acc_row(r, kh) of each M-tile, 128-byte segments per half-wave
-    if (opix) {
-        float* ob = out + (int64_t)b * k.C * L + po;
+    if (opix) {                                                                        // one exec mask for the rows every call has
+        float* ob = out + (int64_t)b * k.C * L;
 #pragma unroll
         for (int mt = 0; mt < MTO; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = acc_row(r, kh, 32 * mt);
-                if (row < k.C) ob[(int64_t)row * L] = oh[mt][r] + rs[mt][r];
+                const int ru = acc_row(r, 0, 32 * mt);
+                const float v = (LOP ? oh[mt][r] + ol[mt][r] : oh[mt][r]) + rs[mt][r];
+                if (ru + 4 <= 16 * (KBM - 1)) put_byte(ob, po4 + (OFF)ru * L4, v);
+                else if (ru < 16 * KBM) {
+                    if (ru + 4 * kh < k.C) put_byte(ob, po4 + (OFF)ru * L4, v);
+                }
             }
     }
 }
@@ -491,6 +559,13 @@ __device__ __forceinline__ void gdmlp_x6_tile(const GdX& k, const GdPre& pre, co
 template <int KBM, int MTO, int WOB, bool PL2>
 __global__ __launch_bounds__(256, 2) void gdmlp_x6_kernel(GdX k, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
     gdmlp_x6_tile<KBM, MTO, WOB, PL2, false>(k, GdPre{}, bpo, bomul, out);
+}
+
+// Planes of 2^30 .. 2^31 elements per image: the same body with 64-bit byte offsets.  One workgroup per CU, so that the address pairs
+// cost no scratch in any form.
+template <int KBM, int MTO, int WOB>
+__global__ __launch_bounds__(256, 1) void gdmlp_x6_wide_kernel(GdX k, const float* __restrict__ bpo, float bomul, float* __restrict__ out) {
+    gdmlp_x6_tile<KBM, MTO, WOB, false, false, uint64_t>(k, GdPre{}, bpo, bomul, out);
 }
 
 // The back half of a VSSBlock: the SS2D tail (out_norm + out_proj + bias + residual of the scan outputs y0, y1) and the gdMlp branch.
@@ -510,7 +585,7 @@ int gd_launch(const char* op, const float* x, const float* ln_w, const float* ln
     BEM_REQUIRE((((uintptr_t)Wp_gate | (uintptr_t)Wp_out | (uintptr_t)bias_gate | (uintptr_t)dw_gate10) & 15) == 0,
                 "%s: packed weights, bias pairs and depthwise parameters must be 16-byte aligned", op);
     BEM_REQUIRE(x != out, "%s: in-place operation is not supported (halo reads)", op);
-    BEM_REQUIRE((int64_t)C * H * W < (1ll << 31), "%s: plane set too large for 32-bit offsets", op);
+    BEM_REQUIRE((int64_t)C * H * W < (1ll << 31), "%s: plane set too large for 32-bit offsets", op);   // pixel indices are int; bytes: OFF
     if (pre) {
         BEM_REQUIRE(pre->y0 && pre->y1 && pre->on_w && pre->on_b && pre->Wop, "%s: null tensor", op);
         BEM_REQUIRE(((uintptr_t)pre->Wop & 15) == 0, "%s: packed out_proj weights must be 16-byte aligned", op);
@@ -536,6 +611,13 @@ int gd_launch(const char* op, const float* x, const float* ln_w, const float* ln
         if (KB == 1) vss_back_x6_kernel<1, 1, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
         else if (KB == 2) vss_back_x6_kernel<2, 1, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
         else vss_back_x6_kernel<3, 2, 2><<<grid, 256, 0, s>>>(k, *pre, bpop, bomul, out);
+    }
+    else if ((int64_t)C * H * W >= (1ll << 30)) {
+        if (KB == 1) gdmlp_x6_wide_kernel<1, 1, 2><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
+        else if (KB == 2) gdmlp_x6_wide_kernel<2, 1, 2><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
+        else if (KB == 3) gdmlp_x6_wide_kernel<3, 2, 2><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
+        else if (KB == 4) gdmlp_x6_wide_kernel<4, 2, 2><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
+        else gdmlp_x6_wide_kernel<5, 3, 1><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     }
     else if (KB == 1) gdmlp_x6_kernel<1, 1, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);
     else if (KB == 2) gdmlp_x6_kernel<2, 1, 2, false><<<grid, 256, 0, s>>>(k, bpop, bomul, out);

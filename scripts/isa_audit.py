@@ -44,7 +44,6 @@ ALLOW_SCRATCH = {
     r"pw_x6_stream_kernel<2, 2, (true|false), false,": "VEC = false: odd plane sizes only (tests, ragged crops)",
     r"pw_x6_stream_kernel<2, 2, true, true, true>": "sum input + LayerNorm at K > 160: not reached by the shipped widths (n_feat 40: K <= 160 uses the resident kernel)",
     r"ss2d_scan_bwd_kernel<1024, 4>": "general-L fallback of the scan backward (ragged planes); the shipped plane sizes use ss2d_scan_bwd_rows_kernel",
-    r"gdmlp_x6_kernel<5, 3, 1, false>": "C = 80 form (x limbs of two halo blocks = 120 registers) at the 256-register budget of two workgroups per CU: 8 B (44 B until the kernel body became gdmlp_x6_tile)",
     r"wgrad_kernel<3, 2":"checked separately: launch bound (256, 1) gives it 512 registers",
 }
 
