@@ -19,8 +19,16 @@ scores every candidate with UIQM and UCIQE on the device (bem.ops.uiqm_uciqe) an
 ``alexnet-owt-7be5be79.pth`` of torchvision and ``alex.pth`` of the lpips package, are data and not shipped here: ``--lpips_weights DIR``, the
 environment variable BEM_LPIPS_WEIGHTS or experiments/pretrained_models/ names the directory holding them.  Scoring happens after the
 candidates are gathered, so every mode works on the sample-sharded ``torchrun`` path.
+``--sample_chunk K`` runs the samples of an image K at a time (BEMPipeline.enhance(sample_chunk=K): the memory knob for many samples of
+large images; every chunk draws under a fresh Philox epoch, so the N samples differ from the single batch's with the same seed);
+``--sample_chunk auto`` measures one one-sample forward per image size and picks the largest K whose estimate stays under half the free
+memory.  ``--uncertainty`` writes ``<result_dir>/<dataset>/std/<image>.png``, the per-pixel standard deviation of the N candidates as
+8-bit grey (``rint(255 min(1, mean_c(std) / --std_white))``; the std of a [0,1] variable is at most 0.5 and a fixed scale keeps images
+comparable), and ``Mean_pred_std``.  ``--keep_best`` keeps only the running best candidate of an image (single-score rules: PSNR at
+``--psnr_weight 1``, ``--no_ref clip`` / ``niqe``).  ``--sample_chunk`` and ``--keep_best`` do not run on the sample-sharded path.
 Output: ``<result_dir>/<dataset>/<image>.png`` (the selected candidate) and ``result.txt`` with the reference's summary lines
-(``Best_lpips`` after the PSNR / SSIM lines, then ``Best_NIQE``, then ``Best_UIQM`` and ``Best_UCIQE``, eval.py:339-355)."""
+(``Best_lpips`` after the PSNR / SSIM lines, then ``Best_NIQE``, then ``Best_UIQM`` and ``Best_UCIQE``, eval.py:339-355; ``Mean_pred_std``
+last)."""
 import argparse
 import os
 import sys
@@ -55,7 +63,13 @@ def get_parser():
     p.add_argument("--lpips", action="store_true", help="True to compute LPIPS")
     p.add_argument("--lpips_weights", default="", type=str, help="directory holding alexnet-owt-7be5be79.pth and alex.pth, for --lpips")
     p.add_argument("--deterministic", action="store_true", help="Use deterministic mode")
-    p.add_argument("--parallel_num", default=1, type=int, help="accepted for compatibility: all samples of an image run as one batch")
+    p.add_argument("--parallel_num", default=1, type=int, help="accepted for compatibility and ignored: all samples of an image run as one "
+                   "batch unless --sample_chunk says otherwise")
+    p.add_argument("--sample_chunk", default="", type=str, metavar="K|auto", help="run the samples of an image K at a time (the memory knob); "
+                   "'auto' measures one sample and picks K; default: all samples as one batch")
+    p.add_argument("--uncertainty", action="store_true", help="write the per-pixel std of the samples to <result_dir>/<dataset>/std/ and report its mean")
+    p.add_argument("--std_white", default=0.25, type=float, help="the std that --uncertainty's grey images show as white")
+    p.add_argument("--keep_best", action="store_true", help="keep only the running best candidate of an image (single-score selection rules)")
     p.add_argument("--seed", default=287128, type=int, help="fix random seed to reproduce consistent results")
     p.add_argument("--clip_prompts", nargs="+", default=["brightness", "noisiness", "quality"])
     return p
@@ -82,8 +96,48 @@ def load_params(net, path):
     net.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()})      # eval.py:98-100 (strict)
 
 
+def save_std(path, std_3hw, white):
+    """--uncertainty's picture of one image: 8-bit grey, rint(255 min(1, mean_c(std) / white))."""
+    from PIL import Image
+    g = np.minimum(1.0, std_3hw.mean(axis=0) / white)
+    Image.fromarray(np.rint(255.0 * g).astype(np.uint8), mode="L").save(path)
+
+
+def auto_sample_chunk(pipe, img, tgt, num_samples, **kw):
+    """--sample_chunk auto: one extra forward of ONE sample of this image (its draws are not used), the peak of allocated memory around it
+    and the memory that is free now.  That forward's whole peak is counted once per sample of a chunk -- the per-image part with it, so
+    the estimate K x peak is on the high side -- and K is the largest chunk whose estimate stays under HALF the free memory (a safety cap, not
+    a tuned number).  A second cap keeps K x peak under 2^33 bytes: no tensor of the one-sample forward is larger than its peak, so no
+    tensor of a chunk then holds 2^31 elements or more -- sizes no test covers; an explicit ``--sample_chunk K`` is the way past it.
+    Returns (K, bytes per sample)."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    pipe.enhance(img, tgt, 1, sync=False, keep="best", **kw)
+    torch.cuda.synchronize()
+    per = max(torch.cuda.max_memory_allocated() - before, 1)
+    free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()     # the allocator's cache is free too
+    return max(1, min(num_samples, int(free // 2 // per), (2**33 - 1) // per)), per
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    # --sample_chunk / --keep_best / --uncertainty: checked before any option-file, model or device work
+    chunk = None
+    if args.sample_chunk not in ("", "auto"):
+        try:
+            chunk = int(args.sample_chunk)
+        except ValueError:
+            raise SystemExit(f"--sample_chunk: expected a number of samples or 'auto', got {args.sample_chunk!r}")
+        if chunk < 1:
+            raise SystemExit(f"--sample_chunk: a chunk holds at least 1 sample, got {chunk}")
+    if (args.sample_chunk or args.keep_best) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(("--sample_chunk" if args.sample_chunk else "--keep_best") + ": not available on the sample-sharded multi-GPU path")
+    if args.keep_best and (args.no_ref == "uiqm_uciqe" or (not args.no_ref and args.target_dir and args.psnr_weight != 1.0)):
+        raise SystemExit("--keep_best: a two-score weighted rule (" + ("--no_ref uiqm_uciqe" if args.no_ref else f"--psnr_weight {args.psnr_weight}")
+                         + ") normalises by the maximum over all samples and cannot be decided chunk by chunk")
+    if args.uncertainty and not (np.isfinite(args.std_white) and args.std_white > 0):
+        raise SystemExit(f"--std_white: must be a positive std, got {args.std_white}")
     if args.lpips:
         # checked before any option-file, model or device work
         if not args.target_dir:
@@ -129,7 +183,7 @@ def main(argv=None):
     # scale from the Stage-I option file, noise level from the Stage-II one, default 0 (eval.py:174-176,207)
     pipe = BEMPipeline(net, cond_net, opt.get("condition", {}).get("scale_down", 16), cond_opt.get("condition", {}).get("noise_level", 0))
     result_dir = os.path.join(args.result_dir, args.dataset)
-    os.makedirs(result_dir, exist_ok=True)
+    os.makedirs(os.path.join(result_dir, "std") if args.uncertainty else result_dir, exist_ok=True)
     names = sorted(f for f in os.listdir(args.input_dir) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
     if args.no_ref == "clip":
         scorer = make_clip_scorer(args.clip_prompts)
@@ -140,6 +194,7 @@ def main(argv=None):
     else:
         scorer = FullReference(args.psnr_weight) if args.target_dir else None
     psnr, ssim, mc_psnr, mc_ssim, niqe, uiqm, uciqe, lpips_ = [], [], [], [], [], [], [], []
+    pred_std, auto_chunks = [], {}          # --uncertainty: mean std per image; --sample_chunk auto: image size -> chunk
     loss_fn = None
     if args.lpips and rank == 0:          # every rank holds the gathered best image: one computes the metric
         from bem.lpips import LPIPS
@@ -151,9 +206,19 @@ def main(argv=None):
             tgt = None
             if args.target_dir:
                 tgt = torch.from_numpy(load_rgb(os.path.join(args.target_dir, name))).permute(2, 0, 1)[None].cuda()
+            if args.sample_chunk == "auto" and not args.deterministic and tuple(img.shape[2:]) not in auto_chunks:
+                K, per = auto_sample_chunk(pipe, img, tgt, args.num_samples, gt_mean=args.GT_mean, seed=args.seed + i)
+                auto_chunks[tuple(img.shape[2:])] = K
+                print(f"--sample_chunk auto: {img.shape[2]}x{img.shape[3]}: {per / 2**20:.1f} MiB per sample, {K} samples per chunk")
             r = pipe.enhance(img, tgt, args.num_samples, gt_mean=args.GT_mean, deterministic=args.deterministic, scorer=scorer,
-                             monte_carlo=args.Monte_Carlo, seed=args.seed + i, shard=(rank, world) if world > 1 else None)
+                             monte_carlo=args.Monte_Carlo, seed=args.seed + i, shard=(rank, world) if world > 1 else None,
+                             sample_chunk=auto_chunks.get(tuple(img.shape[2:]), chunk), uncertainty=args.uncertainty,
+                             keep="best" if args.keep_best else "all")
             best = r["best_images"]
+            if args.uncertainty:
+                pred_std.append(float(r["std_mean"][0]))
+                if rank == 0:
+                    save_std(os.path.join(result_dir, "std", os.path.splitext(name)[0] + ".png"), r["std"][0].cpu().numpy(), args.std_white)
             if args.no_ref == "niqe":
                 niqe.append(float(r["scores"][r["best"][0]]))          # the chosen sample's score (eval.py:273-275)
             elif args.no_ref == "uiqm_uciqe":
@@ -175,7 +240,8 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank != 0:
-        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir)
+        return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir,
+                    **(dict(pred_std=pred_std) if args.uncertainty else {}))
     print(f"running time: {time.perf_counter() - t0:.4f} sec")
     with open(os.path.join(result_dir, "result.txt"), "w") as f:
         if args.target_dir:
@@ -196,7 +262,11 @@ def main(argv=None):
             for label, vals in (("Best_UIQM", uiqm), ("Best_UCIQE", uciqe)):
                 line = f"{label}: {np.mean(vals):.4f}"
                 print(line); f.write(line + " \n")
-    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir)
+        if args.uncertainty:
+            line = f"Mean_pred_std: {np.mean(pred_std):.4f}"
+            print(line); f.write(line + " \n")
+    return dict(psnr=psnr, ssim=ssim, mc_psnr=mc_psnr, mc_ssim=mc_ssim, niqe=niqe, uiqm=uiqm, uciqe=uciqe, lpips=lpips_, result_dir=result_dir,
+                    **(dict(pred_std=pred_std) if args.uncertainty else {}))
 
 
 if __name__ == "__main__":

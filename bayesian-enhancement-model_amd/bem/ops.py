@@ -1449,6 +1449,112 @@ def mc_mean(raw, target, samples_per_image, h, w, gt_mean):
     return out
 
 
+class McState:
+    """The state planes of the streamed Monte-Carlo statistics of one ``enhance`` call, all (B,3,h,w) f32 and zero before the first chunk:
+    ``sum`` (of the clamped raw outputs; ``mean=True``) and / or ``mean`` and ``m2`` (Welford's running mean and sum of squared
+    deviations of the finished candidates; ``spread=True``).  ``n`` counts the samples per image accumulated so far."""
+
+    def __init__(self, B, h, w, device, mean=False, spread=False):
+        if B > _GRID_MAX:
+            raise ValueError(f"McState: at most {_GRID_MAX} images per call, got {B}")
+        if B < 0 or h < 1 or w < 1:
+            raise ValueError("McState: shapes")
+        self.B, self.h, self.w, self.n = B, h, w, 0
+        planes = torch.zeros((1 if mean else 0) + (2 if spread else 0), B, 3, h, w, device=device, dtype=torch.float32)
+        self.sum = planes[0] if mean else None
+        self.mean, self.m2 = (planes[-2], planes[-1]) if spread else (None, None)
+
+
+def _mc_accum_cost(state, raw, final, samples_per_image, **_):
+    per = 4.0 * state.B * 3 * state.h * state.w
+    return ((samples_per_image + 2) * per if raw is not None else 0.0) + ((samples_per_image + 4) * per if final is not None else 0.0), 0.0
+
+
+@_bracket(_mc_accum_cost)
+def mc_accum(state, raw=None, final=None, samples_per_image=1):
+    """One chunk of ``samples_per_image`` samples of every image into ``state``, in sample order: raw (B*Nc,3,Hp,Wp) into ``state.sum`` (the
+    additions mc_mean performs), final (B*Nc,3,h,w) into ``state.mean`` / ``state.m2``.  Either may be None where the state has no plane for
+    it.  Any split of the N samples into chunks leaves the same bits.  B <= 65535."""
+    B, h, w, Nc = state.B, state.h, state.w, samples_per_image
+    if raw is None and final is None:
+        raise ValueError("mc_accum: neither raw outputs nor candidates")
+    if (raw is not None and state.sum is None) or (final is not None and state.mean is None):
+        raise ValueError("mc_accum: the state has no plane for this input")
+    _chk(raw, "raw", optional=True); _chk(final, "final", optional=True)
+    Hp, Wp = (h, w) if raw is None else tuple(raw.shape[2:])
+    for t, shape, name in ((raw, (B * Nc, 3, Hp, Wp), "raw"), (final, (B * Nc, 3, h, w), "final")):
+        if t is not None and (Nc < 1 or tuple(t.shape) != shape or not (h <= Hp and w <= Wp)):
+            raise ValueError(f"mc_accum: {name} {tuple(t.shape)} is not {Nc} samples of {B} images of {h}x{w}")
+    check(lib().bem_mc_accum_f32(_p(raw), _p(final), _p(state.sum), _p(state.mean), _p(state.m2), B, Nc, state.n, Hp, Wp, h, w, _stream()),
+          "mc_accum")
+    state.n += Nc
+
+
+def _mc_finish_cost(state, mean, spread, **_):
+    per = 4.0 * state.B * 3 * state.h * state.w
+    return (2 * per if mean else 0.0) + (2 * per if spread else 0.0), 0.0
+
+
+@_bracket(_mc_finish_cost)
+def mc_finish(state, target=None, gt_mean=False, mean=True, spread=False):
+    """What ``state`` holds after its ``state.n`` samples: ``mean`` -> mc (B,3,h,w), bit for bit mc_mean of the same raw outputs; ``spread`` ->
+    the unbiased per-pixel std of the candidates (B,3,h,w), zeros for one sample, and its mean per image (B) f64 (fixed summation order).
+    Returns (mc | None, std | None, std_mean | None)."""
+    _chk(target, "target", optional=True)
+    B, h, w = state.B, state.h, state.w
+    if state.n < 1:
+        raise ValueError("mc_finish: no samples accumulated")
+    if (mean and state.sum is None) or (spread and state.m2 is None) or not (mean or spread):
+        raise ValueError("mc_finish: the state has no plane for what is asked")
+    gt_mean = bool(gt_mean and mean)
+    if gt_mean and (target is None or tuple(target.shape) != (B, 3, h, w)):
+        raise ValueError("mc_finish: shapes")
+    dev = (state.sum if mean else state.m2).device
+    mc = torch.empty(B, 3, h, w, device=dev, dtype=torch.float32) if mean else None
+    sd = torch.empty(B, 3, h, w, device=dev, dtype=torch.float32) if spread else None
+    sm = torch.empty(B, device=dev, dtype=torch.float64) if spread else None
+    ws = torch.empty(258 * B, device=dev, dtype=torch.float64)
+    check(lib().bem_mc_finish_f32(_p(state.sum if mean else None), _p(state.m2 if spread else None), _p(target if gt_mean else None), _p(mc),
+                                  _p(sd), _p(sm), _p(ws), B, state.n, h, w, int(gt_mean), _stream()), "mc_finish")
+    return mc, sd, sm
+
+
+class BestState:
+    """The running choice of a streamed single-score selection: best (B) int32, score (B), images (B,3,h,w) | None, over ``n`` samples."""
+
+    def __init__(self, B, image_shape, device, rule):
+        if rule not in ("max", "min"):
+            raise ValueError(f"select_merge: rule {rule!r} cannot be decided chunk by chunk ('max' or 'min')")
+        if B > _GRID_MAX:
+            raise ValueError(f"select_merge: at most {_GRID_MAX} images per call, got {B}")
+        self.B, self.rule, self.n = B, rule, 0
+        self.best = torch.zeros(B, device=device, dtype=torch.int32)
+        self.score = torch.zeros(B, device=device, dtype=torch.float32)
+        self.images = torch.zeros((B,) + tuple(image_shape), device=device, dtype=torch.float32) if image_shape is not None else None
+        self.pick = torch.empty(B, device=device, dtype=torch.int32)
+
+
+def _select_merge_cost(state, final, **_):
+    return (8.0 * state.images.numel() if state.images is not None else 0.0), 0.0
+
+
+@_bracket(_select_merge_cost)
+def select_merge(state, final, scores, samples_per_image):
+    """Folds one chunk -- scores (B*Nc), final (B*Nc,3,h,w) | None, row = image*Nc + sample, chunks in sample order -- into the running
+    choice: it changes only where the chunk holds a strictly better score (f64 comparison), so the result equals select_scores with
+    the same rule over all samples at once, first index on ties."""
+    _chk(scores, "scores"); _chk(final, "final", optional=True)
+    B, Nc = state.B, samples_per_image
+    if Nc < 1 or scores.numel() != B * Nc:
+        raise ValueError(f"select_merge: {scores.numel()} scores are not {Nc} samples of {B} images")
+    if (final is None) != (state.images is None) or (final is not None and tuple(final.shape) != (B * Nc,) + tuple(state.images.shape[1:])):
+        raise ValueError("select_merge: shapes")
+    check(lib().bem_select_merge_f32(_p(final), _p(scores), {"max": 1, "min": 2}[state.rule], _p(state.best), _p(state.score), _p(state.images),
+                                     _p(state.pick), B, Nc, state.n, (state.images[0].numel() if final is not None and B else 0), _stream()),
+          "select_merge")
+    state.n += Nc
+
+
 # NIQE (basicsr/metrics/niqe.py as Enhancement/eval.py:248-254 calls it).  Its tables (bem.tables): the AGGD shape grid, and per cropped
 # length the weights and source indices of the x0.5 resize.
 NIQE_BLOCK = 96

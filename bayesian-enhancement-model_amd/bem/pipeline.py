@@ -3,7 +3,8 @@
 Differences from the reference driver that do not change results:
   * all (image, sample) pairs of a call go through Stage-I and Stage-II as ONE batch -- every pair has
     its own Bayesian weight sample (per-batch-element weights in the GEMM / depthwise kernels), which is
-    what the reference's B=1 loop draws (eval.py:199-211);
+    what the reference's B=1 loop draws (eval.py:199-211); ``enhance(sample_chunk=K)`` cuts that batch into forwards of K samples per
+    image where memory asks for it, with the mean and the spread of the N predictions streamed over the chunks;
   * Stage-I outputs never leave the GPU (the reference copies every sample D2H and back, eval.py:211,219);
   * decomp(image) is evaluated once per image and shared by its N samples (it does not depend on the sample) -- and, depending on nothing
     Stage I produces, on a second HIP stream beside it: Stage I is ~160 kernels on H/16 x W/16 planes that occupy a few CUs each, the
@@ -12,6 +13,7 @@ Differences from the reference driver that do not change results:
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -29,14 +31,43 @@ class BEMPipeline:
         self._side = None          # second stream for decomp(image), created on first use
 
     @torch.no_grad()
+    def per_image(self, imgs, targets, gt_mean: bool, img_down: Optional[torch.Tensor] = None):
+        """What a call computes from the images alone, once however many sample forwards follow: the reflect-padded image, its 1/scale
+        resize (Stage I's input), decomp(image) with the image half of Stage II's first convs (on the side stream where there is one;
+        the first sample forward joins it) and the targets' channel means."""
+        h, w = imgs.shape[-2:]
+        f = 4 * self.scale
+        Hp = (((h + f) // f) * f) if h % f else h                                # _padimg_np, eval.py:146-153
+        Wp = (((w + f) // f) * f) if w % f else w
+        pi = SimpleNamespace(hoist=hasattr(self.net2, "forward_decomposed"), d_img=None, p_img=None, side=None)
+        pi.pad = pad = ops.pad_reflect(imgs.contiguous(), Hp, Wp)
+        pi.img_down = ops.resize_down(pad, self.scale) if img_down is None else img_down
+        if pi.hoist and os.environ.get("BEM_DECOMP_OVERLAP", "1") != "0":
+            if self._side is None or self._side.device != pad.device:
+                self._side = torch.cuda.Stream(device=pad.device)
+            pi.side = self._side
+            pi.side.wait_stream(torch.cuda.current_stream())                     # pad is ready
+            with torch.cuda.stream(pi.side):
+                pi.d_img = self.net2.decompose(pad, 0)                           # once per image, beside Stage I
+                pi.p_img = self.net2.first_conv_image(pi.d_img)                  # the image half of the two first convs likewise
+            pad.record_stream(pi.side)
+        elif pi.hoist:
+            pi.d_img = self.net2.decompose(pad, 0)                               # once per image
+            pi.p_img = self.net2.first_conv_image(pi.d_img)
+        pi.tmean = ops.plane_mean(targets.contiguous()) if (gt_mean and targets is not None) else None
+        return pi
+
+    @torch.no_grad()
     def candidates(self, imgs, targets, num_samples: int, gt_mean: bool, deterministic: bool = False,
                    eps: Optional[Dict[str, torch.Tensor]] = None, noise: Optional[torch.Tensor] = None,
                    img_down: Optional[torch.Tensor] = None, seed: int = 0, rank: int = 0, sample_offset: int = 0,
-                   total_samples: Optional[int] = None):
+                   total_samples: Optional[int] = None, per_image=None):
         """imgs (B,3,h,w) in [0,1] on the GPU, targets (B,3,h,w) or None.
         Returns dict(conds (B*N,3,hd,wd), raw (B*N,3,Hp,Wp), final (B*N,3,h,w), psnr (B*N)); row = image*N + sample.
         ``sample_offset`` / ``total_samples``: this call draws samples [offset, offset + num_samples) of ``total_samples`` per image
-        (sample-major multi-GPU sharding, bem.dist): injected ``eps`` / ``noise`` are given for ALL (image, sample) rows and sliced here."""
+        (sample-major multi-GPU sharding, bem.dist; the chunks of ``enhance(sample_chunk=...)``): injected ``eps`` / ``noise`` are given for
+        ALL (image, sample) rows and sliced here.  ``per_image``: ``self.per_image(imgs, targets, gt_mean)`` where the caller has it already
+        (one call per image batch serves every chunk)."""
         from basicsr.bayesian import set_prediction_type
         B, _, h, w = imgs.shape
         N = 1 if deterministic else num_samples
@@ -47,42 +78,26 @@ class BEMPipeline:
                 eps = {k_: v.index_select(0, rows) for k_, v in eps.items()}
             if noise is not None:
                 noise = noise.index_select(0, rows)
-        f = 4 * self.scale
-        Hp = (((h + f) // f) * f) if h % f else h                                # _padimg_np, eval.py:146-153
-        Wp = (((w + f) // f) * f) if w % f else w
-        pad = ops.pad_reflect(imgs.contiguous(), Hp, Wp)
-        if img_down is None:
-            img_down = ops.resize_down(pad, self.scale)
-        hd, wd = img_down.shape[-2:]
-        x1 = img_down[:, None].expand(B, N, 3, hd, wd).reshape(B * N, 3, hd, wd)  # (B*N,3,hd,wd): row = image*N + sample
-        hoist = hasattr(self.net2, "forward_decomposed")
-        d_img, p_img, main = None, None, torch.cuda.current_stream()
-        if hoist and os.environ.get("BEM_DECOMP_OVERLAP", "1") != "0":
-            if self._side is None or self._side.device != pad.device:
-                self._side = torch.cuda.Stream(device=pad.device)
-            self._side.wait_stream(main)                                         # pad is ready
-            with torch.cuda.stream(self._side):
-                d_img = self.net2.decompose(pad, 0)                              # once per image, beside Stage I
-                p_img = self.net2.first_conv_image(d_img)                        # the image half of the two first convs likewise
-            pad.record_stream(self._side)
+        pi = per_image if per_image is not None else self.per_image(imgs, targets, gt_mean, img_down)
+        pad, Hp, Wp = pi.pad, pi.pad.shape[-2], pi.pad.shape[-1]
+        hd, wd = pi.img_down.shape[-2:]
+        x1 = pi.img_down[:, None].expand(B, N, 3, hd, wd).reshape(B * N, 3, hd, wd)  # (B*N,3,hd,wd): row = image*N + sample
         set_prediction_type(self.net1, deterministic)
         with sampling(None if deterministic else SampleCtx(B * N, eps, seed, rank=rank)) as ctx:
             pred = self.net1(x1)[-1]
-        tmean = ops.plane_mean(targets.contiguous()) if (gt_mean and targets is not None) else None
         if noise is None and self.noise_level:
             # torch.randn_like of eval.py:209: its own key space (bit 62 of the stream id), per rank and per forward
             noise = ops.randn(tuple(pred.shape), pred.device, seed, (1 << 62) | (rank << 44) | SampleCtx._epoch)
-        conds = ops.cond_postproc(pred, tmean, noise if self.noise_level else None, N, self.noise_level)
-        if hoist:
-            if d_img is None:
-                d_img = self.net2.decompose(pad, 0)                              # once per image
-                p_img = self.net2.first_conv_image(d_img)
-            else:
-                main.wait_stream(self._side)
-                for t in [d_img] + p_img:
+        conds = ops.cond_postproc(pred, pi.tmean, noise if self.noise_level else None, N, self.noise_level)
+        if pi.hoist:
+            if pi.side is not None:                                              # first sample forward of this image batch
+                main = torch.cuda.current_stream()
+                main.wait_stream(pi.side)
+                for t in [pi.d_img] + pi.p_img:
                     t.record_stream(main)                                        # allocated on the side stream, consumed (and freed) on this one
+                pi.side = None
             d_cond = self.net2.decompose_cond(conds, self.scale)                 # decomp of the enlarged condition, which is never formed
-            raw = self.net2.forward_decomposed(d_img, d_cond, None if N == 1 else N, p_img=p_img)
+            raw = self.net2.forward_decomposed(pi.d_img, d_cond, None if N == 1 else N, p_img=pi.p_img)
         else:
             cond_up = ops.bilinear_up(conds, self.scale)                         # (B*N,3,Hp,Wp)
             # Stage-II archs without a separable decomposition stage (DecompDualBranch, the *2 / *DD / SingleBranch siblings): the
@@ -105,12 +120,63 @@ class BEMPipeline:
         return rel.index(max(rel))
 
     @torch.no_grad()
-    def enhance(self, imgs, targets, num_samples, gt_mean=True, deterministic=False, sync=True, scorer=None, monte_carlo=False, shard=None, **kw):
+    def enhance(self, imgs, targets, num_samples, gt_mean=True, deterministic=False, sync=True, scorer=None, monte_carlo=False, shard=None,
+                sample_chunk=None, uncertainty=False, keep="all", **kw):
         """candidates + per-image selection.  Default selection = the full-reference PSNR rule (first maximum of psnr / max(psnr),
         eval.py:284-285) on the device; ``scorer`` (bem.scorers) switches to the PSNR/SSIM-weighted rule or a no-reference
         scorer (eval.py:268-281).  ``monte_carlo``: also returns the Monte-Carlo mean prediction (eval.py:224-225,308-314) with its
-        PSNR / SSIM.  With ``sync=False`` nothing is copied to the host."""
-        if shard is not None and shard[1] > 1 and not deterministic:
+        PSNR / SSIM.  With ``sync=False`` nothing is copied to the host.
+
+        ``sample_chunk=K``: the N samples of every image run as ceil(N / K) forwards of at most K samples (the memory knob; None or
+        K >= N is the single batch).  The image-only work runs once, ``final`` / ``psnr`` / ``conds`` are assembled in the single batch's row
+        order (image*N + sample) and scored once; the raw outputs are never all resident (``raw`` is not returned, the Monte-Carlo mean is
+        streamed: ops.mc_accum / mc_finish, the same bits as ops.mc_mean).  Every chunk is a forward of its own with a fresh Philox epoch
+        for the weights and the condition noise, as two successive calls have: a chunked run draws a different, equally distributed set
+        of N samples than the single batch with the same seed.  Injected ``eps`` / ``noise`` rows are consumed exactly as by the single batch.
+        ``uncertainty``: adds ``std`` (B,3,h,w), the unbiased per-pixel standard deviation of the N candidates (zeros for N = 1, so in
+        deterministic mode), and ``std_mean`` (B) f64, its mean per image; chunked or not.
+        ``keep='best'``: every chunk's candidates are dropped once scored; no ``final`` / ``conds`` / ``raw``, only ``best``, ``best_images``,
+        ``best_psnr`` and the score vectors.  The choice is merged chunk by chunk (ops.select_merge), which a single-score rule allows: the
+        default PSNR rule, FullReference(1.0) (PSNR >= 0, so dividing by the maximum changes no comparison) and the 'max' / 'min' rules.
+        The two-score weighted rules normalise by maxima over all N and raise ValueError; so does UiqmUciqe at weight 1.0 or 0.0, which
+        is not a single-score rule here: it divides by max(s1), whose sign (UIQM may be negative) turns the order round, and the other
+        score still enters as 0 * s2 / max(s2), NaN where that is -- cases select_scores defines and a running maximum would not follow.
+        ``shard`` together with ``sample_chunk`` or ``keep='best'`` raises ValueError: chunking a rank's block is not built."""
+        N = 1 if deterministic else num_samples
+        if keep not in ("all", "best"):
+            raise ValueError(f"enhance: keep must be 'all' or 'best', got {keep!r}")
+        if sample_chunk is not None and (sample_chunk != int(sample_chunk) or sample_chunk < 1):
+            raise ValueError(f"enhance: sample_chunk must be None or a number of samples >= 1, got {sample_chunk!r}")
+        if shard is not None and shard[1] > 1 and (sample_chunk is not None or keep == "best"):
+            raise ValueError("enhance: shard together with sample_chunk" + (" / keep='best'" if keep == "best" else "") + " is not supported")
+        K = N if sample_chunk is None else min(int(sample_chunk), N)
+        streamed = K < N or keep == "best"
+        B, _, h, w = imgs.shape
+        tg = None if targets is None else targets.contiguous()
+        stats = ops.McState(B, h, w, imgs.device, mean=monte_carlo and streamed, spread=uncertainty) if (uncertainty or (monte_carlo and streamed)) else None
+        run = ops.BestState(B, (3, h, w), imgs.device, _online_rule(scorer)) if keep == "best" else None
+        if streamed:
+            pi = self.per_image(imgs, targets, gt_mean, kw.pop("img_down", None))
+            r = {}
+            for lo in range(0, N, K):
+                n = min(K, N - lo)
+                c = self.candidates(imgs, targets, n, gt_mean, deterministic, sample_offset=lo, total_samples=N, per_image=pi, **kw)
+                if stats is not None:
+                    ops.mc_accum(stats, c["raw"] if monte_carlo else None, c["final"] if uncertainty else None, n)
+                if run is not None:
+                    s1 = c["psnr"] if scorer is None else scorer.scores(c["final"], targets, n, psnr=c["psnr"])[0].contiguous()
+                    ops.select_merge(run, c["final"], s1, n)
+                    c = dict(psnr=c["psnr"]) if scorer is None else dict(psnr=c["psnr"], scores=s1)
+                else:
+                    c = {k_: c[k_] for k_ in ("final", "psnr", "conds")}
+                for k_, t in c.items():                                          # into the single batch's row order, chunk by chunk
+                    if k_ not in r:
+                        r[k_] = t.new_empty((B, N) + tuple(t.shape[1:]))
+                    r[k_][:, lo:lo + n] = t.view((B, n) + tuple(t.shape[1:]))
+                del c
+            r = {k_: t.flatten(0, 1) for k_, t in r.items()}
+            r["N"] = N
+        elif shard is not None and shard[1] > 1 and not deterministic:
             # sample-major multi-GPU form (bem.dist): this rank draws its block of the N samples of every image, one RCCL all-gather per
             # tensor brings candidates, scores (and raw outputs for the Monte-Carlo mean) back into the unsharded (image, sample) order
             from . import dist as bdist
@@ -128,8 +194,12 @@ class BEMPipeline:
         else:
             r = self.candidates(imgs, targets, num_samples, gt_mean, deterministic, **kw)
         N = r["N"]
-        h, w = imgs.shape[-2:]
-        if scorer is not None:
+        if run is not None:
+            best, img, bp = run.best, run.images, run.score
+            if scorer is not None:
+                bp = ops.select_scores(None, r["psnr"], N, rule="max")[1] if targets is None else _gather(r["psnr"], best, N)
+                r["scores2"] = None
+        elif scorer is not None:
             sel = scorer.select(r["final"], targets, N, psnr=r["psnr"])
             best, img = sel["best"], sel["best_images"]
             bp = ops.select_scores(None, r["psnr"], N, rule="max")[1] if targets is None else _gather(r["psnr"], best, N)
@@ -141,14 +211,30 @@ class BEMPipeline:
                 img = r["final"][::N].contiguous()
         r.update(best=best, best_images=img, best_psnr=bp)
         if monte_carlo:
-            mc = ops.mc_mean(r["raw"], None if targets is None else targets.contiguous(), N, h, w, bool(gt_mean and targets is not None))
+            gm = bool(gt_mean and targets is not None)
+            mc = ops.mc_finish(stats, tg, gm, mean=True)[0] if streamed else ops.mc_mean(r["raw"], tg, N, h, w, gm)
             r["mc"] = mc
             if targets is not None:
-                _, r["mc_psnr"] = ops.candidate_finalize(mc, targets.contiguous(), 1, h, w, False)
-                r["mc_ssim"] = ops.ssim(mc, targets.contiguous(), 1) if min(h, w) > 10 else None
+                _, r["mc_psnr"] = ops.candidate_finalize(mc, tg, 1, h, w, False)
+                r["mc_ssim"] = ops.ssim(mc, tg, 1) if min(h, w) > 10 else None
+        if uncertainty:
+            if not streamed:
+                ops.mc_accum(stats, None, r["final"], N)
+            _, r["std"], r["std_mean"] = ops.mc_finish(stats, mean=False, spread=True)
         if sync:
             r["best"], r["best_psnr"] = best.cpu().tolist(), bp.cpu().tolist()
         return r
+
+
+def _online_rule(scorer):
+    """The 'max' / 'min' rule by which ``enhance(keep='best')`` can merge the scorer's choice chunk by chunk, or ValueError."""
+    from .scorers import FullReference
+    if scorer is None or (type(scorer) is FullReference and scorer.weight == 1.0):
+        return "max"                       # PSNR >= 0: psnr / max(psnr) orders the candidates as psnr does
+    if scorer.rule in ("max", "min"):
+        return scorer.rule
+    raise ValueError(f"enhance: keep='best' cannot follow the {scorer.rule!r} rule of {type(scorer).__name__} (weight {scorer.weight}): it "
+                     f"normalises by maxima over all N samples; use keep='all'")
 
 
 def _gather(v, best, N):

@@ -129,15 +129,17 @@ __global__ void select_best_kernel(const float* __restrict__ psnr, int* __restri
 }
 
 __global__ void gather_best_kernel(const float* __restrict__ cand, const int* __restrict__ best, float* __restrict__ out, int N, int64_t chw4) {
-    const int b = blockIdx.y;
-    const float4* src = reinterpret_cast<const float4*>(cand) + ((int64_t)b * N + best[b]) * chw4;
+    const int b = blockIdx.y, k = best[b];
+    if (k < 0) return;                                                     // the streaming merge: this image keeps what it has
+    const float4* src = reinterpret_cast<const float4*>(cand) + ((int64_t)b * N + k) * chw4;
     float4* dst = reinterpret_cast<float4*>(out) + (int64_t)b * chw4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < chw4; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 __global__ void gather_best_scalar_kernel(const float* __restrict__ cand, const int* __restrict__ best, float* __restrict__ out, int N, int64_t chw) {
-    const int b = blockIdx.y;
-    const float* src = cand + ((int64_t)b * N + best[b]) * chw;
+    const int b = blockIdx.y, k = best[b];
+    if (k < 0) return;
+    const float* src = cand + ((int64_t)b * N + k) * chw;
     float* dst = out + (int64_t)b * chw;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < chw; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
@@ -231,6 +233,8 @@ __global__ void select_scores_kernel(const float* __restrict__ s1, const float* 
 
 // Monte-Carlo mean of eval.py:224-225,308-314: mc = clamp(mean_n clamp(pred_n[:h,:w], 0, 1), 0, 1); with GT-mean the whole image is
 // scaled by mean(gray(target)) / mean(gray(mc)), gray = cv2.COLOR_BGR2GRAY of the array as stored (0.114 c0 + 0.587 c1 + 0.299 c2).
+// SUMMED: pred is the (B,3,h,w) plane of sums that mc_accum_kernel left (the same additions in the same order), not the N raw outputs.
+template <bool SUMMED>
 __global__ __launch_bounds__(256) void mc_mean_kernel(const float* __restrict__ pred, float* __restrict__ out, double* __restrict__ gsum,
                                                      const float* __restrict__ target, int N, int Hp, int Wp, int h, int w) {
     __shared__ double sh[2][4];
@@ -241,7 +245,8 @@ __global__ __launch_bounds__(256) void mc_mean_kernel(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
         const int y = (int)(i / w), x = (int)(i % w);
         float a = 0.f;
-        for (int n = 0; n < N; ++n) a += fminf(fmaxf(pred[(((int64_t)b * N + n) * 3 + ch) * Hp * Wp + (int64_t)y * Wp + x], 0.f), 1.f);
+        if (SUMMED) a = pred[((int64_t)b * 3 + ch) * hw + i];
+        else for (int n = 0; n < N; ++n) a += fminf(fmaxf(pred[(((int64_t)b * N + n) * 3 + ch) * Hp * Wp + (int64_t)y * Wp + x], 0.f), 1.f);
         a = fminf(fmaxf(a / (float)N, 0.f), 1.f);
         out[((int64_t)b * 3 + ch) * hw + i] = a;
         sm += (double)(gw * a);
@@ -261,6 +266,122 @@ __global__ void mc_rescale_kernel(float* __restrict__ out, const double* __restr
     const int64_t b = i / chw;
     const float ratio = (float)(gsum[2 * b + 1] / gsum[2 * b]);
     out[i] = fminf(fmaxf(out[i] * ratio, 0.f), 1.f);
+}
+
+template <bool SUMMED>
+void launch_mc_mean(const float* pred, const float* target, float* out, double* ws, int B, int N, int Hp, int Wp, int h, int w, int gt_mean,
+                    hipStream_t s) {
+    const unsigned gx = (unsigned)std::min<int64_t>(cdiv64((int64_t)h * w, 256), 256);
+    mc_mean_kernel<SUMMED><<<dim3(gx, 3, B), 256, 0, s>>>(pred, out, gt_mean ? ws : nullptr, gt_mean ? target : nullptr, N, Hp, Wp, h, w);
+    if (gt_mean) {
+        const int64_t total = (int64_t)B * 3 * h * w;
+        mc_rescale_kernel<<<GRID1D(total), 256, 0, s>>>(out, ws, (int64_t)3 * h * w, total);
+    }
+}
+
+// ---------------------------------------------------------------- streamed Monte-Carlo statistics ----------
+// V consecutive floats of a row as one access: V = 4 where the row lengths, pitches and pointers are multiples of 16 bytes.
+template <int V> struct fvec { float v[V]; };
+template <int V> __device__ __forceinline__ fvec<V> ld_vec(const float* p) {
+    fvec<V> r;
+    if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w; }
+    else r.v[0] = *p;
+    return r;
+}
+template <int V> __device__ __forceinline__ void st_vec(float* p, const fvec<V>& r) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else *p = r.v[0];
+}
+
+// Welford's update with x as sample number k.  Every operation is rounded to f32 on its own: a contracted d * (x - mean) + m2 would
+// make the bits depend on what the compiler fuses, and the state must be a function of the sample sequence alone.
+__device__ __forceinline__ void welford_step(float x, float k, float& mean, float& m2) {
+#pragma clang fp contract(off)
+    const float d = x - mean;
+    mean = mean + d / k;
+    const float t = d * (x - mean);
+    m2 = m2 + t;
+}
+
+// One chunk of Nc samples per image into the state planes: thread = V elements of one (image, channel) plane, samples in order.
+template <int V>
+__global__ __launch_bounds__(256) void mc_accum_kernel(const float* __restrict__ raw, const float* __restrict__ fin, float* __restrict__ sum,
+                                                      float* __restrict__ mean, float* __restrict__ m2, int Nc, int n_done, int Hp, int Wp,
+                                                      int h, int w) {
+    const int ch = blockIdx.y, b = blockIdx.z;
+    const int64_t hw = (int64_t)h * w, pitch = (int64_t)Hp * Wp, plane = ((int64_t)b * 3 + ch) * hw;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw / V; i += (int64_t)gridDim.x * 256) {
+        const int64_t e = i * V;
+        if (raw) {
+            const int64_t at = (e / w) * Wp + (e % w);                    // w % V == 0: the V elements share a row
+            fvec<V> a = ld_vec<V>(sum + plane + e);
+            for (int n = 0; n < Nc; ++n) {
+                const fvec<V> x = ld_vec<V>(raw + (((int64_t)b * Nc + n) * 3 + ch) * pitch + at);
+#pragma unroll
+                for (int j = 0; j < V; ++j) a.v[j] += fminf(fmaxf(x.v[j], 0.f), 1.f);
+            }
+            st_vec<V>(sum + plane + e, a);
+        }
+        if (fin) {
+            fvec<V> m = ld_vec<V>(mean + plane + e), q = ld_vec<V>(m2 + plane + e);
+            for (int n = 0; n < Nc; ++n) {
+                const fvec<V> x = ld_vec<V>(fin + (((int64_t)b * Nc + n) * 3 + ch) * hw + e);
+#pragma unroll
+                for (int j = 0; j < V; ++j) welford_step(x.v[j], (float)(n_done + n + 1), m.v[j], q.v[j]);
+            }
+            st_vec<V>(mean + plane + e, m);
+            st_vec<V>(m2 + plane + e, q);
+        }
+    }
+}
+
+// std = sqrt(m2 / (N - 1)) (zeros for N = 1) and, per workgroup, the f64 sum of what it wrote: part[b * MC_STD_BLOCKS + block].
+// Workgroup k of an image takes elements [k * per, (k + 1) * per): which workgroup sums what depends on the shape alone.
+constexpr int MC_STD_BLOCKS = 256;
+template <int V>
+__global__ __launch_bounds__(256) void mc_std_kernel(const float* __restrict__ m2, float* __restrict__ out, double* __restrict__ part, int N,
+                                                    int64_t chw, int64_t per) {
+    __shared__ double sh[4];
+    const int b = blockIdx.y;
+    const float div = (float)(N - 1);
+    const int64_t i0 = (int64_t)blockIdx.x * per, i1 = std::min<int64_t>(i0 + per, chw / V);
+    double s = 0.0;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+        fvec<V> q = ld_vec<V>(m2 + (int64_t)b * chw + i * V);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            q.v[j] = N > 1 ? sqrtf(q.v[j] / div) : 0.f;
+            s += (double)q.v[j];
+        }
+        st_vec<V>(out + (int64_t)b * chw + i * V, q);
+    }
+    s = block_sum<4>(s, sh);
+    if (threadIdx.x == 0) part[(int64_t)b * MC_STD_BLOCKS + blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void mc_std_mean_kernel(const double* __restrict__ part, double* __restrict__ std_mean, int nblk, int64_t chw) {
+    __shared__ double sh[4];
+    const int b = blockIdx.x;
+    double s = (int)threadIdx.x < nblk ? part[(int64_t)b * MC_STD_BLOCKS + threadIdx.x] : 0.0;      // nblk <= MC_STD_BLOCKS = 256 threads
+    s = block_sum<4>(s, sh);
+    if (threadIdx.x == 0) std_mean[b] = s / (double)chw;
+}
+
+// The loop of select_scores_kernel's rules 1 / 2, continued over a chunk: pick[b] = the chunk's row to copy, -1 to keep the running image.
+__global__ void select_merge_kernel(const float* __restrict__ scores, int rule, int* __restrict__ best, float* __restrict__ best_score,
+                                    int* __restrict__ pick, int B, int Nc, int n_done) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* p = scores + (int64_t)b * Nc;
+    int bi = -1, i = 0;
+    double bs;
+    if (n_done == 0) { bs = (double)p[0]; bi = 0; i = 1; }
+    else bs = (double)best_score[b];
+    for (; i < Nc; ++i) {
+        const double sc = (double)p[i];
+        if (rule == 1 ? sc > bs : sc < bs) { bs = sc; bi = i; }
+    }
+    pick[b] = bi;
+    if (bi >= 0) { best[b] = n_done + bi; best_score[b] = p[bi]; }
 }
 
 // best_img[b] = cand[b][best[b]]: 16-byte copies when the planes allow it
@@ -351,11 +472,64 @@ extern "C" int bem_mc_mean_f32(const float* pred, const float* target, float* ou
     if (B == 0) return BEM_OK;
     hipStream_t s = (hipStream_t)stream;
     if (gt_mean) BEM_ZERO(ws, sizeof(double) * 2 * B, s, "mc_mean");
-    const unsigned gx = (unsigned)std::min<int64_t>(cdiv64((int64_t)h * w, 256), 256);
-    mc_mean_kernel<<<dim3(gx, 3, B), 256, 0, s>>>(pred, out, gt_mean ? ws : nullptr, gt_mean ? target : nullptr, N, Hp, Wp, h, w);
-    if (gt_mean) {
-        const int64_t total = (int64_t)B * 3 * h * w;
-        mc_rescale_kernel<<<GRID1D(total), 256, 0, s>>>(out, ws, (int64_t)3 * h * w, total);
-    }
+    launch_mc_mean<false>(pred, target, out, ws, B, N, Hp, Wp, h, w, gt_mean, s);
     return bem_check_launch("mc_mean");
+}
+
+extern "C" int bem_mc_accum_f32(const float* raw, const float* fin, float* sum, float* mean, float* m2, int B, int Nc, int n_done, int Hp, int Wp,
+                                int h, int w, void* stream) {
+    BEM_REQUIRE(raw || fin, "mc_accum: null tensor (neither raw outputs nor candidates)");
+    BEM_REQUIRE(!raw || sum, "mc_accum: null sum plane for the raw outputs");
+    BEM_REQUIRE(!fin || (mean && m2), "mc_accum: null mean / m2 plane for the candidates");
+    BEM_REQUIRE(B >= 0 && B <= 65535, "mc_accum: at most 65535 images per call, got B=%d", B);
+    BEM_REQUIRE(Nc >= 1 && n_done >= 0 && (int64_t)n_done + Nc < (1 << 24), "mc_accum: bad sample counts Nc=%d n_done=%d", Nc, n_done);
+    BEM_REQUIRE(h > 0 && w > 0 && h <= Hp && w <= Wp, "mc_accum: bad shape h=%d w=%d of Hp=%d Wp=%d", h, w, Hp, Wp);
+    if (B == 0) return BEM_OK;
+    const uintptr_t ptrs = (uintptr_t)raw | (uintptr_t)fin | (uintptr_t)sum | (uintptr_t)mean | (uintptr_t)m2;
+    const bool v4 = w % 4 == 0 && (!raw || Wp % 4 == 0) && (ptrs & 15) == 0;
+    const int64_t n = (int64_t)h * w / (v4 ? 4 : 1);
+    dim3 grid((unsigned)std::min<int64_t>(cdiv64(n, 256), 1024), 3, B);
+    if (v4) mc_accum_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(raw, fin, sum, mean, m2, Nc, n_done, Hp, Wp, h, w);
+    else mc_accum_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(raw, fin, sum, mean, m2, Nc, n_done, Hp, Wp, h, w);
+    return bem_check_launch("mc_accum");
+}
+
+extern "C" int bem_mc_finish_f32(const float* sum, const float* m2, const float* target, float* mc, float* std, double* std_mean, double* ws,
+                                 int B, int N, int h, int w, int gt_mean, void* stream) {
+    BEM_REQUIRE(mc || std, "mc_finish: null outputs (neither mc nor std asked for)");
+    BEM_REQUIRE(!mc || sum, "mc_finish: mc needs the sum plane");
+    BEM_REQUIRE(!std || (m2 && std_mean), "mc_finish: std needs the m2 plane and std_mean");
+    BEM_REQUIRE(ws, "mc_finish: null workspace");
+    BEM_REQUIRE(B >= 0 && B <= 65535 && N >= 1 && h > 0 && w > 0, "mc_finish: bad arguments B=%d N=%d h=%d w=%d", B, N, h, w);
+    BEM_REQUIRE(!(mc && gt_mean) || target, "mc_finish: GT-mean needs the target");
+    if (B == 0) return BEM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (mc) {
+        if (gt_mean) BEM_ZERO(ws, sizeof(double) * 2 * B, s, "mc_finish");
+        launch_mc_mean<true>(sum, target, mc, ws, B, N, h, w, h, w, gt_mean, s);
+    }
+    if (std) {
+        const int64_t chw = (int64_t)3 * h * w;
+        const bool v4 = chw % 4 == 0 && (((uintptr_t)m2 | (uintptr_t)std) & 15) == 0;
+        const int64_t n = chw / (v4 ? 4 : 1);
+        const int nblk = (int)std::min<int64_t>(cdiv64(n, 256), MC_STD_BLOCKS);
+        double* part = ws + 2 * (int64_t)B;
+        if (v4) mc_std_kernel<4><<<dim3(nblk, B), 256, 0, s>>>(m2, std, part, N, chw, cdiv64(n, nblk));
+        else mc_std_kernel<1><<<dim3(nblk, B), 256, 0, s>>>(m2, std, part, N, chw, cdiv64(n, nblk));
+        mc_std_mean_kernel<<<B, 256, 0, s>>>(part, std_mean, nblk, chw);
+    }
+    return bem_check_launch("mc_finish");
+}
+
+extern "C" int bem_select_merge_f32(const float* cand, const float* scores, int rule, int* best, float* best_score, float* best_img, int* pick,
+                                    int B, int Nc, int n_done, int64_t chw, void* stream) {
+    BEM_REQUIRE(scores && best && best_score && pick, "select_merge: null tensor");
+    BEM_REQUIRE(B >= 0 && B <= 65535 && Nc >= 1 && n_done >= 0 && chw >= 0, "select_merge: bad arguments B=%d Nc=%d n_done=%d", B, Nc, n_done);
+    BEM_REQUIRE(rule == 1 || rule == 2, "select_merge: rule %d cannot be decided chunk by chunk (1 = max, 2 = min)", rule);
+    BEM_REQUIRE((cand == nullptr) == (best_img == nullptr), "select_merge: cand and best_img go together");
+    if (B == 0) return BEM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    select_merge_kernel<<<cdiv(B, 64), 64, 0, s>>>(scores, rule, best, best_score, pick, B, Nc, n_done);
+    if (cand && chw > 0) launch_gather_best(cand, pick, best_img, B, Nc, chw, s);
+    return bem_check_launch("select_merge");
 }

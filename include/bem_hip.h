@@ -400,6 +400,30 @@ int64_t bem_uiqm_ws_bytes(int Bn, int h, int w, int Hr);   /* 0 for Hr < 10 */
 int bem_mc_mean_f32(const float* pred, const float* target, float* out, double* ws, int B, int N, int Hp, int Wp, int h, int w,
                     int gt_mean, void* stream);
 
+/* The same mean, and the per-pixel spread of the N predictions, streamed over chunks of the N samples (a chunk = Nc samples of every
+ * image; the chunks of a run are handed over in sample order).  State planes (B,3,h,w) f32, zero before the first chunk:
+ *   sum       += clamp(raw[b*Nc+n][:, :h, :w], 0, 1), n = 0 .. Nc-1 one at a time: the additions bem_mc_mean_f32 performs, in its order
+ *   mean, m2  Welford's update with fin[b*Nc+n] as sample number n_done + n + 1 (d = x - mean; mean += d / k; m2 += d * (x - mean)),
+ *             every operation rounded to f32 on its own (no contraction)
+ * raw (B*Nc,3,Hp,Wp) with sum, and / or fin (B*Nc,3,h,w) with mean and m2; either pair may be NULL.  An element's state depends on the
+ * sequence of its samples alone, so any split of N into chunks leaves the same bits. */
+int bem_mc_accum_f32(const float* raw, const float* fin, float* sum, float* mean, float* m2, int B, int Nc, int n_done, int Hp, int Wp,
+                     int h, int w, void* stream);
+
+/* What the state planes hold after N samples.  sum with mc: mc (B,3,h,w) = clamp(sum / N, 0, 1) and the GT-mean rescale, bit for bit
+ * bem_mc_mean_f32 of the same N raw outputs (target when gt_mean).  m2 with std: std (B,3,h,w) = sqrt(m2 / (N - 1)), zeros for N = 1, and
+ * std_mean (B) f64 = its mean over the 3 h w elements of an image (per-workgroup f64 partials summed in a fixed order by a second launch:
+ * the same bits on every run).  Either pair may be NULL.  ws: 258 B doubles. */
+int bem_mc_finish_f32(const float* sum, const float* m2, const float* target, float* mc, float* std, double* std_mean, double* ws, int B,
+                      int N, int h, int w, int gt_mean, void* stream);
+
+/* bem_select_scores_f32's rules 1 (max) and 2 (min) over chunks of an image's samples handed over in sample order: best (B) int32,
+ * best_score (B) and best_img (B, chw) are the running choice over the n_done samples seen so far (not read when n_done = 0).  They
+ * change only where the chunk (scores (B*Nc), cand (B*Nc, chw)) holds a strictly better score, compared in f64 -- the first index wins
+ * ties, as in one bem_select_scores_f32 call over all the samples.  cand / best_img may both be NULL; pick: B int32 of scratch. */
+int bem_select_merge_f32(const float* cand, const float* scores, int rule, int* best, float* best_score, float* best_img, int* pick, int B,
+                         int Nc, int n_done, int64_t chw, void* stream);
+
 /* The whole gdMlp branch of a VSSBlock in one kernel (vmamba.py:116-133 gdMlp.forward + the block's norm2 / residual :1330-1333):
  *   out (B,C,H,W) = x + W_o (GELU(h[0:Hd]) * h[Hd:2Hd]) + b_o,   h = dw3x3(W_i LayerNorm2d(x) + b_i) + b_dw.
  * Neither the 2Hd-channel project_in output nor the Hd-channel gate tensor reaches HBM (4 x 32 pixel tiles, both live as 16-gate-channel
