@@ -107,9 +107,11 @@ def auto_sample_chunk(pipe, img, tgt, num_samples, **kw):
     """--sample_chunk auto: one extra forward of ONE sample of this image (its draws are not used), the peak of allocated memory around it
     and the memory that is free now.  That forward's whole peak is counted once per sample of a chunk -- the per-image part with it, so
     the estimate K x peak is on the high side -- and K is the largest chunk whose estimate stays under HALF the free memory (a safety cap, not
-    a tuned number).  A second cap keeps K x peak under 2^33 bytes: no tensor of the one-sample forward is larger than its peak, so no
-    tensor of a chunk then holds 2^31 elements or more -- sizes no test covers; an explicit ``--sample_chunk K`` is the way past it.
-    Returns (K, bytes per sample)."""
+    a tuned number).  A second cap keeps K x peak under 2^34 bytes: no tensor of the one-sample forward is larger than its peak, so no
+    tensor of a chunk then holds 2^32 elements or more -- the range tests/test_large_tensors_gpu.py covers: it runs the kernels of the eval
+    forward, the selection tail and the no-reference scorers on tensors that cross 2^29, 2^30, 2^31 and 2^32 elements (DESIGN.md section
+    4.9).  Units of float4 can still wrap at 2^33 and 2^34 elements, which nothing tests; an explicit ``--sample_chunk K`` is the way past
+    the cap.  Returns (K, bytes per sample)."""
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     before = torch.cuda.memory_allocated()
@@ -117,7 +119,7 @@ def auto_sample_chunk(pipe, img, tgt, num_samples, **kw):
     torch.cuda.synchronize()
     per = max(torch.cuda.max_memory_allocated() - before, 1)
     free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()     # the allocator's cache is free too
-    return max(1, min(num_samples, int(free // 2 // per), (2**33 - 1) // per)), per
+    return max(1, min(num_samples, int(free // 2 // per), (2**34 - 1) // per)), per
 
 
 def main(argv=None):

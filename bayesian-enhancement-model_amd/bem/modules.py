@@ -381,7 +381,7 @@ class VSSBlock(nn.Module):
         C = x.shape[1]
         # the SS2D tail inside the gdMlp kernel: x1 = x + out_proj(out_norm(y0 + y1)) is never written
         if ops.USE_VSS_BACK and self.op.tail_deferrable(C) and self.mlp.fused_supported(C) \
-                and ops.vss_back_supported(C, self.mlp.project_in.out_channels // 2):
+                and ops.vss_back_supported(C, self.mlp.project_in.out_channels // 2, x.shape[2] * x.shape[3]):
             return self.mlp.forward_fused(x, self.norm2, pre=self.op.forward_fused(x, self.norm, defer_tail=True))
         x = self.op.forward_fused(x, self.norm)
         return self.mlp.forward_fused(x, self.norm2)

@@ -155,6 +155,15 @@ def _tables(key, device, build):
 
 
 _GRID_MAX = 65535        # the y and z extent of a launch grid: planes, candidates (x 3 channels) or images go there
+# The tile kernels (gdmlp_x6, ss2d_front) address one image's planes with 32-bit byte offsets below _TILE_NARROW elements and with 64-bit
+# ones up to _TILE_MAX, where the int pixel indices end; the library states the same two bounds (gdmlp_x6.hip, ss2d_front_x6.hip).
+_TILE_NARROW, _TILE_MAX = 1 << 30, 1 << 31
+
+
+def _tile_plane_set(op, elems):
+    """Refuses a plane set the tile kernels cannot index, with the library's message, before anything is allocated for it."""
+    if elems >= _TILE_MAX:
+        raise native.BemNativeError(f"{op}: plane set too large for 32-bit offsets ({elems} elements per image, at most {_TILE_MAX - 1})")
 
 
 def _pslice(t, c0):
@@ -311,22 +320,25 @@ def ss2d_scan_rm(x, xd0, xd1, dtw, dtb, A, Ds):
 
 
 def _transpose(src, src_c0, C, dst=None, dst_c0=0):
-    """dst[:, dst_c0:dst_c0+C] (B,*,W,H) = the planes of src[:, src_c0:src_c0+C] (B,*,H,W) transposed, in one launch (its B C planes
-    go into gridDim.z).  C None: every channel from src_c0 on; dst None: a new (B,C,W,H) tensor.  Returns dst."""
+    """dst[:, dst_c0:dst_c0+C] (B,*,W,H) = the planes of src[:, src_c0:src_c0+C] (B,*,H,W) transposed.  The planes of a launch go into
+    gridDim.z: one launch per _GRID_MAX // C batch rows.  C None: every channel from src_c0 on; dst None: a new (B,C,W,H) tensor.  Returns dst."""
     _chk(src, "src")
     B, Cs, H, W = src.shape
     C = Cs - src_c0 if C is None else C
     if C < 0 or src_c0 < 0 or src_c0 + C > Cs:
         raise ValueError(f"transpose_planes: channels [{src_c0}, {src_c0 + C}) of a source with {Cs}")
-    if B * C > _GRID_MAX:
-        raise ValueError(f"transpose_planes: at most {_GRID_MAX} planes per launch, got {B * C}")
+    if C > _GRID_MAX:
+        raise ValueError(f"transpose_planes: at most {_GRID_MAX} planes per batch row, got {C}")
     if dst is None:
         dst = torch.empty(B, C, W, H, device=src.device, dtype=src.dtype)
     _chk(dst, "dst")
     if dst.dim() != 4 or dst.shape[0] != B or tuple(dst.shape[2:]) != (W, H) or dst_c0 < 0 or dst_c0 + C > dst.shape[1]:
         raise ValueError(f"transpose_planes: {C} transposed planes of src {tuple(src.shape)} do not fit dst {tuple(dst.shape)} at channel {dst_c0}")
     (sp, sbs), (dp, dbs) = _pslice(src, src_c0), _pslice(dst, dst_c0)
-    check(lib().bem_transpose_planes_f32(sp, sbs, dp, dbs, B, C, H, W, _stream()), "transpose_planes")
+    step = _GRID_MAX // max(C, 1)
+    for b0 in range(0, max(B, 1), step):
+        check(lib().bem_transpose_planes_f32(ctypes.c_void_p((sp.value or 0) + 4 * b0 * sbs), sbs, ctypes.c_void_p((dp.value or 0) + 4 * b0 * dbs), dbs,
+                                             min(step, B - b0), C, H, W, _stream()), "transpose_planes")
     return dst
 
 
@@ -563,6 +575,7 @@ def ss2d_front(x, ln_w, ln_b, ln_eps, Wp_in, bias_in, dww, dwb, Wp_x, Mx):
     if ln_w.numel() != C or ln_b.numel() != C or dww.numel() != 9 * C or (dwb is not None and dwb.numel() != C) or (bias_in is not None and bias_in.numel() != C):
         raise ValueError("ss2d_front: parameter shapes")
     _chk_packed1("ss2d_front", (("Wp_in", Wp_in, C, C), ("Wp_x", Wp_x, Mx, C)))
+    _tile_plane_set("ss2d_front", max(C, Mx) * H * W)
     xc = torch.empty_like(x)
     xd = torch.empty(B, Mx, H, W, device=x.device, dtype=x.dtype)
     check(lib().bem_ss2d_front_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_in), _p(bias_in), _p(dww), _p(dwb), _p(Wp_x), _p(xc), _p(xd),
@@ -597,8 +610,10 @@ def dw_gate_params10(dww, dwb, Hd):
 USE_VSS_BACK = True
 
 
-def vss_back_supported(C, Hd):
-    return C <= 48 and C % 8 == 0 and Hd % 16 == 0
+def vss_back_supported(C, Hd, L):
+    """L = H W of the image: the kernel addresses with 32-bit byte offsets and has no wide form, so a plane set of 2^30 elements or more
+    belongs to the two-kernel chain (bem_gdmlp_x6_f32 has 64-bit forms up to 2^31)."""
+    return C <= 48 and C % 8 == 0 and Hd % 16 == 0 and C * L < _TILE_NARROW
 
 
 def vss_back_rows(C):
@@ -653,17 +668,19 @@ def gdmlp_x6(x, ln_w, ln_b, ln_eps, Wp_gate, bias_gate, dw10, Wp_out, bias_out, 
     if ln_w.numel() != C or ln_b.numel() != C or bias_gate.numel() != 2 * Hd or (bias_out is not None and bias_out.numel() != C):
         raise ValueError("gdmlp_x6: parameter shapes")
     _chk_packed1("gdmlp_x6", (("Wp_gate", Wp_gate, 2 * Hd, C), ("Wp_out", Wp_out, C, Hd)))
-    out = torch.empty_like(x)
+    _tile_plane_set("gdmlp_x6", C * H * W)
     if pre is not None:
         y0, y1, on_w, on_b, on_eps, Wp_op, b_op = pre
         for n_, t in (("y0", y0), ("y1", y1), ("on_w", on_w), ("on_b", on_b), ("Wp_outproj", Wp_op)):
             _chk(t, n_)
         _chk(b_op, "bias_outproj", optional=True)
-        if not vss_back_supported(C, Hd):
-            raise ValueError(f"gdmlp_x6 with pre: C = {C} (<= 48, % 8) not supported")
+        if not vss_back_supported(C, Hd, H * W):
+            raise ValueError(f"gdmlp_x6 with pre: C = {C} (<= 48, % 8) with {C * H * W} elements per image (< {_TILE_NARROW}) not supported")
         if y0.shape != x.shape or y1.shape != x.shape or on_w.numel() != C or on_b.numel() != C or (b_op is not None and b_op.numel() != C):
             raise ValueError("gdmlp_x6 with pre: y0 / y1 must have the shape of x, out_norm and the out_proj bias C entries")
         _chk_packed1("gdmlp_x6", (("Wp_outproj", Wp_op, 32 * ((8 * ((C + 15) // 16) + 15) // 16), C),))      # len(vss_back_rows(C)) rows
+    out = torch.empty_like(x)
+    if pre is not None:
         check(lib().bem_vss_back_x6_f32(_p(x), _p(ln_w), _p(ln_b), float(ln_eps), _p(Wp_gate), _p(bias_gate), _p(dw10), _p(Wp_out),
                                         _p(bias_out), _p(out), B, C, Hd, H, W, _p(y0), _p(y1), _p(on_w), _p(on_b), float(on_eps),
                                         _p(Wp_op), _p(b_op), _stream()), "gdmlp_x6")

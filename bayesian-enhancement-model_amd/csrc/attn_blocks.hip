@@ -14,7 +14,7 @@
 namespace {
 
 __global__ void row_scale_kernel(const float* __restrict__ w, const float* __restrict__ s, float* __restrict__ out, int64_t total, int K) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i < total) out[i] = w[i] * s[i / K];
 }
 
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
 
 // a thread per pixel: mean and max over the channels of x * y  ->  map (B, 2, HW)
 __global__ void sa_stats_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ map, int C, int64_t HW, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t b = i / HW, p = i - b * HW;
     const float* xp = x + b * C * HW + p;
@@ -81,7 +81,7 @@ __device__ __forceinline__ float sa_gate(const float* __restrict__ map, const fl
 // a thread per pixel: a = sigmoid(conv_kxk(map), zero padding k / 2); out[c] = x[c] * y[c] * a
 __global__ void sa_apply_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ map, const float* __restrict__ w,
                                 float* __restrict__ out, int C, int H, int W, int k, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
     const float a = sa_gate(map, w, b, (int)(p / W), (int)(p % W), H, W, k);
@@ -98,7 +98,7 @@ __global__ void sa_apply_kernel(const float* __restrict__ x, const float* __rest
 // ------------------------------------------------------------------------------------------------------------------------
 __global__ void chan_scale_kernel(const float* __restrict__ x, const float* __restrict__ scale, int64_t scale_bs, const float* __restrict__ add,
                                   const float* __restrict__ add_bc, float add_bc_scale, float* __restrict__ out, int C, int64_t HW, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t bc = i / HW, b = bc / C;
     const int c = (int)(bc - b * C);
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
 // dpre[b][p] = (sum_c dout x) a (1 - a),  a = sigmoid(conv(map))
 __global__ void sa_bwd_pre_kernel(const float* __restrict__ x, const float* __restrict__ dout, const float* __restrict__ map, const float* __restrict__ w,
                                   float* __restrict__ dpre, int C, int H, int W, int k, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
     const float a = sa_gate(map, w, b, (int)(p / W), (int)(p % W), H, W, k);
@@ -189,7 +189,7 @@ __global__ void sa_bwd_pre_kernel(const float* __restrict__ x, const float* __re
 // dx[c] = dout[c] a + dmap_mean / C + [c == argmax_c x] dmap_max,  dmap[ch][p] = sum_taps w[ch][tap] dpre[p - tap offset]   (transposed conv)
 __global__ void sa_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ dout, const float* __restrict__ map, const float* __restrict__ w,
                                  const float* __restrict__ dpre, float* __restrict__ dx, int C, int H, int W, int k, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t HW = (int64_t)H * W, b = i / HW, p = i - b * HW;
     const int py = (int)(p / W), px = (int)(p % W), r = k / 2;
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void sa_bwd_dw_kernel(const float* __restrict_
 extern "C" int bem_row_scale_f32(const float* w, const float* scale, float* out, int M, int K, void* stream) {
     BEM_REQUIRE(w && scale && out && M > 0 && K > 0, "row_scale: bad arguments");
     const int64_t total = (int64_t)M * K;
-    row_scale_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(w, scale, out, total, K);
+    row_scale_kernel<<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(w, scale, out, total, K);
     return bem_check_launch("row_scale");
 }
 
@@ -262,8 +262,8 @@ extern "C" int bem_spatial_attention_f32(const float* x, const float* chan_scale
     if (B == 0) return BEM_OK;
     const int64_t total = (int64_t)B * H * W;
     hipStream_t s = (hipStream_t)stream;
-    sa_stats_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, s>>>(x, chan_scale, map_ws, C, (int64_t)H * W, total);
-    sa_apply_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, s>>>(x, chan_scale, map_ws, w, out, C, H, W, k, total);
+    sa_stats_kernel<<<GRID1D(total), 256, 0, s>>>(x, chan_scale, map_ws, C, (int64_t)H * W, total);
+    sa_apply_kernel<<<GRID1D(total), 256, 0, s>>>(x, chan_scale, map_ws, w, out, C, H, W, k, total);
     return bem_check_launch("spatial_attention");
 }
 
@@ -274,7 +274,7 @@ extern "C" int bem_chan_scale_f32(const float* x, const float* scale, int64_t sc
     BEM_REQUIRE(x && scale && out && B >= 0 && C > 0 && HW > 0 && (scale_bstride == 0 || scale_bstride == C), "chan_scale: bad arguments");
     const int64_t total = (int64_t)B * C * HW;
     if (total == 0) return BEM_OK;
-    chan_scale_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(x, scale, scale_bstride, add, add_bc, add_bc_scale, out, C, HW, total);
+    chan_scale_kernel<<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(x, scale, scale_bstride, add, add_bc, add_bc_scale, out, C, HW, total);
     return bem_check_launch("chan_scale");
 }
 
@@ -301,8 +301,8 @@ extern "C" int bem_spatial_attention_bwd_f32(const float* x, const float* dout, 
     BEM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (k == 3 || k == 7), "spatial_attention_bwd: bad shape");
     const int64_t total = (int64_t)B * H * W;
     hipStream_t s = (hipStream_t)stream;
-    sa_bwd_pre_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, s>>>(x, dout, map, w, dpre_ws, C, H, W, k, total);
-    sa_bwd_dx_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, s>>>(x, dout, map, w, dpre_ws, dx, C, H, W, k, total);
+    sa_bwd_pre_kernel<<<GRID1D(total), 256, 0, s>>>(x, dout, map, w, dpre_ws, C, H, W, k, total);
+    sa_bwd_dx_kernel<<<GRID1D(total), 256, 0, s>>>(x, dout, map, w, dpre_ws, dx, C, H, W, k, total);
     sa_bwd_dw_kernel<<<2 * k * k, 256, 0, s>>>(map, dpre_ws, dw, B, H, W, k);
     return bem_check_launch("spatial_attention_bwd");
 }

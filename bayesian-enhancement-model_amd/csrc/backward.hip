@@ -35,7 +35,7 @@ __global__ void l1_final_kernel(const double* __restrict__ acc, float* __restric
 // ---------------------------------------------------------------- IWT + Hamilton backward ---------------------------
 __global__ void iwt_hamilton_bwd_kernel(const float* __restrict__ q1w, const float* __restrict__ q2w, const float* __restrict__ dout,
                                         float* __restrict__ d1, float* __restrict__ d2, int h, int w, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int x = (int)(i % w), y = (int)((i / w) % h), b = (int)(i / ((int64_t)w * h));
     const int64_t hw = (int64_t)h * w;
@@ -96,7 +96,7 @@ __global__ void iwt_hamilton_bwd_kernel(const float* __restrict__ q1w, const flo
 // ---------------------------------------------------------------- layout / reductions -------------------------------
 // nn.PixelUnshuffle(2): (B,C,2H,2W) -> (B,4C,H,W), out[c*4 + i*2 + j][y][x] = in[c][2y+i][2x+j]  (inverse of bem_pixel_shuffle2_f32)
 __global__ void pixel_unshuffle2_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int xx = (int)(i % W), y = (int)((i / W) % H);
     const int c = (int)((i / ((int64_t)W * H)) % C), b = (int)(i / ((int64_t)W * H * C));
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
 }
 
 __global__ void add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int64_t n, float alpha) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i < n) out[i] = fmaf(alpha, b[i], a[i]);
 }
 
@@ -541,7 +541,7 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
         coef = fminf(max_norm / (tn + 1e-6f), 1.f);
         if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = tn;
     }
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= n) return;
     const float gi = g[i] * coef;
     g[i] = gi;
@@ -570,7 +570,7 @@ extern "C" int bem_l1_loss_f32(const float* pred, const float* gt, float* dpred,
 namespace {
 // backward of bem_hamilton_f32: q (B,8,HW) = [p | q], dout (B,3,HW) = d(i, j, k parts of p x q)  ->  dq8 (B,8,HW) = [dp | dq]
 __global__ void hamilton_bwd_kernel(const float* __restrict__ q8, const float* __restrict__ dout, float* __restrict__ dq8, int64_t HW, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t pix = i % HW, b = i / HW;
     const float* s = q8 + b * 8 * HW + pix;

@@ -82,7 +82,7 @@ __global__ void batch_assemble_kernel(const uint8_t* __restrict__ lq_arena, cons
                                       const float* __restrict__ noise, int steps, int Sh, int Sw, int s,
                                       float* __restrict__ lq, float* __restrict__ gt, float* __restrict__ lq_down,
                                       float* __restrict__ gt_down, int64_t nfull, int64_t total) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t i = bem_gid1d();
     if (i >= total) return;
     if (i < nfull) {
         const int x = (int)(i % Sw), y = (int)((i / Sw) % Sh), j = (int)(i / ((int64_t)Sw * Sh));

@@ -36,7 +36,16 @@ static inline int bem_check_launch(const char* what) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-#define GRID1D(n) dim3((unsigned)cdiv64((n), 256))      // one thread per element, 256 per workgroup
+// One thread per element, 256 per workgroup.  A grid dimension holds fewer than 2^32 threads (the dispatch packet's grid size is 32 bits):
+// 2^24 workgroups of 256 in x wrap, and the launch covers n mod 2^32 elements without an error.  From BEM_GRID1D_X workgroups on, GRID1D
+// puts the rest into grid.y; a kernel launched with it takes its element index from bem_gid1d() and leaves where that is past n.
+constexpr int64_t BEM_GRID1D_X = 1 << 23;
+static inline dim3 bem_grid1d(int64_t n) {
+    const int64_t nb = cdiv64(n, 256);
+    return nb <= BEM_GRID1D_X ? dim3((unsigned)nb) : dim3((unsigned)BEM_GRID1D_X, (unsigned)cdiv64(nb, BEM_GRID1D_X));
+}
+#define GRID1D(n) bem_grid1d(n)
+__device__ __forceinline__ int64_t bem_gid1d() { return ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; }
 
 // Workgroup ids are dealt round-robin to the 8 XCDs (each with its own L2).  Give every XCD a contiguous run of work items (the pixel
 // tiles of a plane in the x6 kernels, the channel rows of one (orientation, image) in the scans), so that what one L2 collects

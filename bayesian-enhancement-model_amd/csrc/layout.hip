@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void transpose_planes_kernel(const float* __re
 
 __global__ void copy_channels_kernel(const float* __restrict__ src, int64_t src_bs, float* __restrict__ dst,
                                      int64_t dst_bs, int64_t CL, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t b = i / CL, r = i - b * CL;
     dst[b * dst_bs + r] = src[b * src_bs + r];
@@ -44,7 +44,7 @@ __global__ void copy_channels_kernel(const float* __restrict__ src, int64_t src_
 // dst row b takes the channels of src row b / rep: an image's planes handed to its `rep` Monte-Carlo samples in one launch
 __global__ void copy_channels_rep_kernel(const float* __restrict__ src, int64_t src_bs, float* __restrict__ dst,
                                          int64_t dst_bs, int64_t CL, int64_t total, int rep) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t b = i / CL, r = i - b * CL;
     dst[b * dst_bs + r] = src[(b / rep) * src_bs + r];
@@ -52,7 +52,7 @@ __global__ void copy_channels_rep_kernel(const float* __restrict__ src, int64_t 
 
 __global__ void add_channels_kernel(const float* __restrict__ src, int64_t src_bs, float* __restrict__ dst,
                                     int64_t dst_bs, int64_t CL, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t b = i / CL, r = i - b * CL;
     dst[b * dst_bs + r] += src[b * src_bs + r];
@@ -60,7 +60,7 @@ __global__ void add_channels_kernel(const float* __restrict__ src, int64_t src_b
 
 __global__ void bilinear_up_kernel(const float* __restrict__ src, int64_t src_bs, float* __restrict__ dst,
                                    int64_t dst_bs, int C, int H, int W, int s, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int Wo = W * s, Ho = H * s;
     const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho);
@@ -73,7 +73,7 @@ __global__ void bilinear_up_kernel(const float* __restrict__ src, int64_t src_bs
 __global__ void space_to_depth_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W,
                                       int64_t total) {
     // out (B,4C,H/2,W/2): block q = dy + 2*dx  ->  [ee, oe, eo, oo]  (UNet_arch.py:74-78)
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int h2 = H >> 1, w2 = W >> 1;
     const int xx = (int)(i % w2), y = (int)((i / w2) % h2);
@@ -86,7 +86,7 @@ __global__ void space_to_depth_kernel(const float* __restrict__ x, float* __rest
 __global__ void pixel_shuffle2_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W,
                                       int64_t total) {
     // out (B,C,2H,2W)[c][2y+i][2x+j] = x[c*4 + i*2 + j][y][x]
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int Wo = 2 * W, Ho = 2 * H;
     const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho);
@@ -103,7 +103,7 @@ __device__ __forceinline__ int reflect_idx(int i, int n) { return i < n ? i : 2 
 
 __global__ void pad_reflect_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W, int Hp, int Wp,
                                    int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int xo = (int)(i % Wp), yo = (int)((i / Wp) % Hp);
     const int64_t plane = i / ((int64_t)Wp * Hp);
@@ -112,7 +112,7 @@ __global__ void pad_reflect_kernel(const float* __restrict__ x, float* __restric
 
 __global__ void resize_down_kernel(const float* __restrict__ x, float* __restrict__ out, int Hp, int Wp, int s,
                                    int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int wd = Wp / s, hd = Hp / s;
     const int xo = (int)(i % wd), yo = (int)((i / wd) % hd);
@@ -218,13 +218,13 @@ extern "C" int bem_resize_down_f32(const float* x, float* out, int P, int Hp, in
 // ------------------------------------------------------------------------------------------------
 namespace {
 __global__ void cast16_to_f32_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, int64_t n, int dtype) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= n) return;
     const uint16_t b = src[i];
     dst[i] = dtype == 1 ? (float)__builtin_bit_cast(_Float16, b) : __builtin_bit_cast(float, (uint32_t)b << 16);
 }
 __global__ void cast_f32_to16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n, int dtype) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= n) return;
     const float v = src[i];
     if (dtype == 1) {
@@ -239,12 +239,12 @@ __global__ void cast_f32_to16_kernel(const float* __restrict__ src, uint16_t* __
 extern "C" int bem_cast16_to_f32(const void* src, float* dst, int64_t n, int dtype, void* stream) {
     BEM_REQUIRE(src && dst && n >= 0 && (dtype == 1 || dtype == 2), "cast16_to_f32: bad arguments");
     if (n == 0) return BEM_OK;
-    cast16_to_f32_kernel<<<(unsigned)cdiv64(n, 256), 256, 0, (hipStream_t)stream>>>((const uint16_t*)src, dst, n, dtype);
+    cast16_to_f32_kernel<<<GRID1D(n), 256, 0, (hipStream_t)stream>>>((const uint16_t*)src, dst, n, dtype);
     return bem_check_launch("cast16_to_f32");
 }
 extern "C" int bem_cast_f32_to16(const float* src, void* dst, int64_t n, int dtype, void* stream) {
     BEM_REQUIRE(src && dst && n >= 0 && (dtype == 1 || dtype == 2), "cast_f32_to16: bad arguments");
     if (n == 0) return BEM_OK;
-    cast_f32_to16_kernel<<<(unsigned)cdiv64(n, 256), 256, 0, (hipStream_t)stream>>>(src, (uint16_t*)dst, n, dtype);
+    cast_f32_to16_kernel<<<GRID1D(n), 256, 0, (hipStream_t)stream>>>(src, (uint16_t*)dst, n, dtype);
     return bem_check_launch("cast_f32_to16");
 }

@@ -17,7 +17,7 @@ const LpipsScale kLpipsScale = {{-0.030f, -0.088f, -0.188f}, {0.458f, 0.448f, 0.
 // padding of conv1 (zero after the scaling layer, as nn.Conv2d pads its own input).
 __global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict__ ref, const float* __restrict__ pred, float* __restrict__ xs,
                                                          int B, int H, int W, int Hb, int Wb, LpipsScale sc, int mode, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int bx = (int)(i % Wb), by = (int)((i / Wb) % Hb);
     const int64_t pc = i / ((int64_t)Wb * Hb);
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict
 // walk (row-major from -inf, `val > max || isnan(val)`): a NaN in the window is the result.
 __global__ __launch_bounds__(256) void maxpool3s2_kernel(const float* __restrict__ x, int64_t x_ps, int64_t x_rs, float* __restrict__ out,
                                                          int Ho, int Wo, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int ox = (int)(i % Wo), oy = (int)((i / Wo) % Ho);
     const int64_t p = i / ((int64_t)Wo * Ho);

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void niqe_mscn_kernel(const float* __restrict_
 // padding is folded into the host-built index table), f32 result.
 __global__ __launch_bounds__(256) void niqe_resize_h_kernel(const float* __restrict__ y, float* __restrict__ out, const float* __restrict__ wt,
                                                             const int* __restrict__ ix, int K, int H, int W, int Ho, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int x = (int)(i % W), o = (int)((i / W) % Ho);
     const int64_t b = i / ((int64_t)W * Ho);
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void niqe_resize_h_kernel(const float* __restr
 // W pass, then * 255 (niqe.py's img * 255.) in f32.
 __global__ __launch_bounds__(256) void niqe_resize_w_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ wt,
                                                             const int* __restrict__ ix, int K, int W, int Wo, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int o = (int)(i % Wo);
     const float* p = in + (i / Wo) * W;
@@ -309,8 +309,8 @@ extern "C" int bem_niqe_f32(const float* final, const double* mu_pris, const dou
     const int H2 = L.Hc / 2, W2 = L.Wc / 2;
     niqe_mscn_kernel<true><<<dim3(cdiv(L.Wc, NQ_TW), cdiv(L.Hc, NQ_TH), Bn), 256, 0, s>>>(final, y1, n1, window, h, w, L.Hc, L.Wc);
     const int64_t nh = (int64_t)Bn * H2 * L.Wc, nw = (int64_t)Bn * H2 * W2;
-    niqe_resize_h_kernel<<<(unsigned)cdiv64(nh, 256), 256, 0, s>>>(y1, t1, rs_wh, rs_ih, kh, L.Hc, L.Wc, H2, nh);
-    niqe_resize_w_kernel<<<(unsigned)cdiv64(nw, 256), 256, 0, s>>>(t1, y2, rs_ww, rs_iw, kw, L.Wc, W2, nw);
+    niqe_resize_h_kernel<<<GRID1D(nh), 256, 0, s>>>(y1, t1, rs_wh, rs_ih, kh, L.Hc, L.Wc, H2, nh);
+    niqe_resize_w_kernel<<<GRID1D(nw), 256, 0, s>>>(t1, y2, rs_ww, rs_iw, kw, L.Wc, W2, nw);
     niqe_mscn_kernel<false><<<dim3(cdiv(W2, NQ_TW), cdiv(H2, NQ_TH), Bn), 256, 0, s>>>(y2, nullptr, n2, window, 0, 0, H2, W2);
     niqe_feature_kernel<<<dim3(L.nb, 2, Bn), 256, 0, s>>>(n1, n2, gam_tab, ntab, feat, L.Hc, L.Wc, L.nbh, L.nb);
     niqe_mvg_kernel<<<Bn, 64, 0, s>>>(feat, mu_pris, cov_pris, scores, L.nb);

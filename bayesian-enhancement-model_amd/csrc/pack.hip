@@ -42,7 +42,7 @@ __device__ __forceinline__ void pack_x6_item(int64_t i, const float* __restrict_
 
 __global__ void pack_x6_kernel(const float* __restrict__ W, u32x4* __restrict__ Wp, int M, int K, int MT, int KB, int64_t total,
                                int64_t ss, int64_t rs, int64_t cs) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     pack_x6_item(i, W, Wp, M, K, MT, KB, ss, rs, cs);
 }
@@ -103,7 +103,7 @@ __device__ __forceinline__ void sample_pack_x6_item(int64_t i, const float* __re
 __global__ void sample_pack_x6_kernel(const float* __restrict__ mu, const float* __restrict__ rho, const float* __restrict__ eps_in,
                                       u32x4* __restrict__ Wp, int M, int K, int MT, int KB, int64_t total, uint64_t seed, uint64_t stream_id,
                                       const uint64_t* __restrict__ stream_add, int sigma_given) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     if (stream_add) stream_id += stream_add[0];                          // device-resident part of the id (see randn_kernel)
     sample_pack_x6_item(i, mu, rho, eps_in, Wp, M, K, MT, KB, seed, stream_id, sigma_given);
@@ -114,7 +114,7 @@ __global__ void sample_pack_x6_kernel(const float* __restrict__ mu, const float*
 // ([forward epoch] << 20, see SampleCtx.next_stream) kept in HBM so that a captured HIP graph of the step draws fresh numbers on
 // every replay; NULL = the id is complete as passed.
 __global__ void randn_kernel(float* __restrict__ out, int64_t total, uint64_t seed, uint64_t stream_id, const uint64_t* __restrict__ stream_add) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (stream_add) stream_id += stream_add[0];
     if (i < total) out[i] = philox_normal(i, seed, stream_id);
 }
@@ -123,7 +123,7 @@ __global__ void randn_kernel(float* __restrict__ out, int64_t total, uint64_t se
 __global__ void bnn_sample_kernel(const float* __restrict__ mu, const float* __restrict__ rho,
                                   const float* __restrict__ eps_in, float* __restrict__ out, int64_t n, int64_t total,
                                   uint64_t seed, uint64_t stream_id, const uint64_t* __restrict__ stream_add) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = bem_gid1d();
     const int64_t i0 = 4 * j;
     if (i0 >= total) return;
     if (stream_add) stream_id += stream_add[0];
@@ -226,7 +226,7 @@ extern "C" int bem_bnn_sample_pack_x6(const float* mu, const float* rho, const f
     if (nsets == 0) return BEM_OK;
     const int MT = cdiv(M, 32), KB = cdiv(K, 16);
     const int64_t total = (int64_t)nsets * MT * KB * 64;
-    sample_pack_x6_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(mu, rho, eps_in, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB,
+    sample_pack_x6_kernel<<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(mu, rho, eps_in, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB,
                                                                                        total, seed, stream_id, stream_add, sigma_given);
     return bem_check_launch("bnn_sample_pack_x6");
 }
@@ -243,7 +243,7 @@ extern "C" int bem_pack_pw_weight_x6_strided(const float* W, float* Wp, int nset
     if (nsets == 0) return BEM_OK;
     const int MT = cdiv(M, 32), KB = cdiv(K, 16);
     const int64_t total = (int64_t)nsets * MT * KB * 64;
-    pack_x6_kernel<<<(unsigned)cdiv64(total, 256), 256, 0, (hipStream_t)stream>>>(W, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB, total, set_stride,
+    pack_x6_kernel<<<GRID1D(total), 256, 0, (hipStream_t)stream>>>(W, reinterpret_cast<u32x4*>(Wp), M, K, MT, KB, total, set_stride,
                                                                                  row_stride, col_stride);
     return bem_check_launch("pack_pw_weight_x6");
 }

@@ -21,7 +21,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void vgg_prep_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                        float* __restrict__ xn, int B, int64_t HW, VggNorm nm, int range_norm,
                                                        int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     constexpr int E = VEC ? 4 : 1;
     const int64_t U = HW / E;
@@ -53,7 +53,7 @@ __device__ __forceinline__ float vgg_norm_bwd1(float g, float std, int range_nor
 template <bool VEC>
 __global__ __launch_bounds__(256) void vgg_prep_bwd_kernel(const float* __restrict__ dxn, int64_t dxn_bs, float* __restrict__ dpred,
                                                            int64_t HW, VggNorm nm, int range_norm, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     constexpr int E = VEC ? 4 : 1;
     const int64_t U = HW / E;
@@ -85,7 +85,7 @@ __device__ __forceinline__ float window_max(float a, float b, float c, float d, 
 // MaxPool2d(2, 2), floor: x (P, H, W) -> out (P, H/2, W/2).  VEC (W % 8 == 0, aligned): four outputs per thread from four float4 loads.
 template <bool VEC>
 __global__ __launch_bounds__(256) void maxpool2_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int Ho = H >> 1, Wo = W >> 1;
     constexpr int E = VEC ? 4 : 1;
@@ -120,7 +120,7 @@ __device__ __forceinline__ void window_bwd(float a, float b, float c, float d, f
 template <bool VEC>
 __global__ __launch_bounds__(256) void relu_pool_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dpool,
                                                             float* __restrict__ dy, int H, int W, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int Ho = H >> 1, Wo = W >> 1;
     constexpr int E = VEC ? 2 : 1;                  // windows per thread
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void relu_pool_bwd_kernel(const float* __restr
 // writes the same elements.  Threads [0, nv) move float4s, threads [nv, nv + tail) the single floats behind them.
 template <bool BWD>
 __global__ __launch_bounds__(256) void relu_kernel(const float* y, const float* dy, float* out, int64_t nv, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i < nv) {
         const float4 a = reinterpret_cast<const float4*>(y)[i];
         float4 r;

@@ -768,7 +768,9 @@ extern "C" int bem_pw_gemm_x6_f32(const bem_pw_args* a, void* stream) {
     BEM_REQUIRE(a->out_mode == 0 || (a->out_mode == 1 && a->M % 4 == 0 && a->Win > 0 && a->L % a->Win == 0 && !a->res),
                 "pw_gemm_x6: out_mode %d constraints", a->out_mode);
     BEM_REQUIRE(((uintptr_t)a->Wp & 15) == 0 && a->w_bstride % 4 == 0, "pw_gemm_x6: packed weights must be 16-byte aligned");
-    BEM_REQUIRE((int64_t)a->M * a->L < (1ll << 30), "pw_gemm_x6: M * L = %lld exceeds the 32-bit lane offsets of the epilogue", (long long)a->M * a->L);
+    // Plane bases (batch row, channel, output row) are 64-bit and wave-uniform; a lane adds its pixel and, in the row epilogue, its 4-row
+    // half: (4 kh L + p) elements as a uint32, 20 L bytes at most.  That offset, not M L, is what has to fit into 32 bits.
+    BEM_REQUIRE((int64_t)20 * a->L < (1ll << 32), "pw_gemm_x6: a plane of L = %d pixels exceeds the 32-bit lane offsets of the epilogue (20 L bytes)", a->L);
     const bool ln = a->ln_w != nullptr;
     BEM_REQUIRE(!ln || a->K <= BEM_X6_MAXK_LN, "pw_gemm_x6: LayerNorm prologue supports K <= %d (got %d)", BEM_X6_MAXK_LN, a->K);
     if (a->B == 0 || a->L == 0) return BEM_OK;

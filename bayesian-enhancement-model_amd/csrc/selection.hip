@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void mc_mean_kernel(const float* __restrict__ 
     }
 }
 __global__ void mc_rescale_kernel(float* __restrict__ out, const double* __restrict__ gsum, int64_t chw, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t b = i / chw;
     const float ratio = (float)(gsum[2 * b + 1] / gsum[2 * b]);

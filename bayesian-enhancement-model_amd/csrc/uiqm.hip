@@ -85,7 +85,7 @@ __device__ __forceinline__ uint8_t pil_tap_sum(const uint8_t* __restrict__ src, 
 
 __global__ __launch_bounds__(256) void uiqm_resize_h_kernel(const uint8_t* __restrict__ q, uint8_t* __restrict__ out, const int* __restrict__ bounds,
                                                             const int* __restrict__ k, int K, int h, int w, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int x = (int)(i % UQ_W);
     const int64_t row = i / UQ_W;                   // (b * 3 + c) * h + y
@@ -407,7 +407,7 @@ extern "C" int bem_uiqm_uciqe_f32(const float* final, const int* lab_tab, const 
     const int64_t hw = (int64_t)h * w, nrs = (int64_t)Hr * UQ_W, ntmp = (int64_t)Bn * 3 * h * UQ_W;
     if (hipMemsetAsync(cnt, 0, (size_t)Bn * UQ_NCNT * 4, s) != hipSuccess) return bem_check_launch("uiqm_uciqe: memset");
     uiqm_quant_lab_kernel<<<dim3(L.ntiles, Bn), 256, 0, s>>>(final, lab_tab, q, lab, cnt, part, hw, L.ntiles);
-    uiqm_resize_h_kernel<<<(unsigned)cdiv64(ntmp, 256), 256, 0, s>>>(q, tmp, rs_bh, rs_kh, kh, h, w, ntmp);
+    uiqm_resize_h_kernel<<<GRID1D(ntmp), 256, 0, s>>>(q, tmp, rs_bh, rs_kh, kh, h, w, ntmp);
     uiqm_resize_v_kernel<<<dim3((unsigned)cdiv64(nrs, 256), Bn), 256, 0, s>>>(tmp, rs, rs_bv, rs_kv, kv, h, Hr, cnt);
     uiqm_sobel_max_kernel<<<dim3((unsigned)cdiv64(nrs, 256), Bn), 256, 0, s>>>(rs, Hr, cnt);
     uiqm_blocks_kernel<<<dim3(cdiv(L.nb, 4), Bn), 256, 0, s>>>(rs, cnt, eme, ucm, Hr, L.nx, L.ny);

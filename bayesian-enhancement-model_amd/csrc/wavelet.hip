@@ -28,7 +28,7 @@ __device__ __forceinline__ void haar_bands(const float (&q)[4], float (&o)[4]) {
 // stack and writes the 4 Haar bands (QD/model4.py:7-18,216-236).
 __global__ void quat_dwt_kernel(const float* __restrict__ rgb, int64_t x_bs, float* __restrict__ out, int H, int W,
                                 int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int h2 = H >> 1, w2 = W >> 1;
     const int x = (int)(i % w2), y = (int)((i / w2) % h2), b = (int)(i / ((int64_t)w2 * h2));
@@ -52,7 +52,7 @@ __global__ void quat_dwt_kernel(const float* __restrict__ rgb, int64_t x_bs, flo
 }
 
 __global__ void dwt_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int h2 = H >> 1, w2 = W >> 1;
     const int xx = (int)(i % w2), y = (int)((i / w2) % h2);
@@ -70,7 +70,7 @@ __global__ void dwt_kernel(const float* __restrict__ x, float* __restrict__ out,
 
 __global__ void iwt_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W, int64_t total) {
     // x (B,4C,H,W) -> out (B,C,2H,2W); one thread per input pixel and channel
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int xx = (int)(i % W), y = (int)((i / W) % H);
     const int c = (int)((i / ((int64_t)W * H)) % C), b = (int)(i / ((int64_t)W * H * C));
@@ -92,7 +92,7 @@ __device__ __forceinline__ void hamilton_ijk(const float (&p)[4], const float (&
 __global__ void iwt_hamilton_kernel(const float* __restrict__ q1w, const float* __restrict__ q2w,
                                     float* __restrict__ out, int h, int w, int64_t total) {
     // q*w (B,16,h,w): channel = band*4 + component.  out (B,3,2h,2w).
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int x = (int)(i % w), y = (int)((i / w) % h), b = (int)(i / ((int64_t)w * h));
     const int64_t hw = (int64_t)h * w;
@@ -124,7 +124,7 @@ __global__ void iwt_hamilton_kernel(const float* __restrict__ q1w, const float* 
 }
 
 __global__ void hamilton_kernel(const float* __restrict__ q, float* __restrict__ out, int64_t HW, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t pix = i % HW, b = i / HW;
     const float* p = q + b * 8 * HW + pix;
@@ -138,7 +138,7 @@ __global__ void hamilton_kernel(const float* __restrict__ q, float* __restrict__
 
 // all four components (real part first), the reference's hamilton_product (QD/quaternion.py:3-17)
 __global__ void hamilton_full_kernel(const float* __restrict__ q1, const float* __restrict__ q2, float* __restrict__ out, int64_t HW, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int64_t pix = i % HW, b = i / HW;
     const float* p = q1 + b * 4 * HW + pix;
@@ -157,7 +157,7 @@ __global__ void hamilton_full_kernel(const float* __restrict__ q1, const float* 
 // conditions per 8 MiB of output: every read after the first is an L1 hit), and writes each of the 32 planes with one 4 NPX-byte store.
 template <int NPX>
 __global__ __launch_bounds__(256) void cond_dwt_kernel(const float* __restrict__ cond, float* __restrict__ out, int H, int W, int s, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = bem_gid1d();
     if (i >= total) return;
     const int h2 = (H * s) >> 1, w2 = (W * s) >> 1, wq = w2 / NPX;
     const int x = (int)(i % wq) * NPX, y = (int)((i / wq) % h2), b = (int)(i / ((int64_t)wq * h2));

@@ -3,18 +3,17 @@ that reach every address and mask path of their loads and stores: ragged last ti
 borders, one exact tile, two tiles across, a second k-block that is not full (C = 24), the C = 80 form, C % 8 != 0, with and without biases.
 Each output is compared with torch in float64 (the reference and the bounds of tests/test_ops_gpu.py and tests/test_vss_back_gpu.py for the
 same op) and is allocated inside a larger buffer of canary values, so that a store through a wrong or clamped address shows."""
-import contextlib
-
 import pytest
 import torch
 import torch.nn.functional as F
+
+from large_rows import canaries
 
 pytestmark = pytest.mark.gpu
 
 # (B, C, H, W)
 TILE_CASES = [(2, 40, 6, 34), (1, 48, 4, 32), (2, 24, 5, 33), (1, 40, 9, 64)]
 GDMLP_ONLY = [(1, 80, 8, 36), (1, 36, 5, 33)]
-CANARY, PAD = 12345.0, 1 << 15
 
 
 @pytest.fixture(scope="module")
@@ -36,31 +35,6 @@ def close(a, b, rtol, atol, what=""):
     err = (a - b).abs().max().item()
     print(f"{what}: max abs err {err:.3e} (ref max {b.abs().max():.3e})")
     assert torch.allclose(a, b, rtol=rtol, atol=atol), f"{what}: max abs err {err:.3e} (ref max {b.abs().max():.3e})"
-
-
-@contextlib.contextmanager
-def canaries(monkeypatch):
-    """Every tensor the op allocates for its results (torch.empty / torch.empty_like) becomes a view into the middle of a larger buffer
-    filled with CANARY; on exit the margins on both sides must still hold it."""
-    bufs = []
-
-    def inside(shape, device, dtype):
-        n = 1
-        for s in shape:
-            n *= int(s)
-        buf = torch.full((n + 2 * PAD,), CANARY, device=device, dtype=dtype)
-        bufs.append((buf, n))
-        return buf[PAD:PAD + n].view(*shape)
-
-    with monkeypatch.context() as m:
-        m.setattr(torch, "empty_like", lambda t: inside(t.shape, t.device, t.dtype))
-        m.setattr(torch, "empty", lambda *shape, device=None, dtype=None: inside(shape, device, dtype))
-        yield
-    torch.cuda.synchronize()
-    assert bufs, "the op allocated no output"
-    for buf, n in bufs:
-        assert bool((buf[:PAD] == CANARY).all()) and bool((buf[PAD + n:] == CANARY).all()), "a store landed outside the output tensor"
-        assert not bool((buf[PAD:PAD + n] == CANARY).any()), "an output element was never written"
 
 
 def ln64(v, w, b, eps):

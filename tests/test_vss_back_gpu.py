@@ -58,8 +58,10 @@ def test_row_permutation_against_the_accumulator_layout():
 
 
 def test_supported_widths_and_cost():
-    assert ops.vss_back_supported(40, 160) and ops.vss_back_supported(24, 32) and ops.vss_back_supported(48, 16)
-    assert not ops.vss_back_supported(80, 320) and not ops.vss_back_supported(44, 32) and not ops.vss_back_supported(40, 24)
+    L = 256 * 256
+    assert ops.vss_back_supported(40, 160, L) and ops.vss_back_supported(24, 32, L) and ops.vss_back_supported(48, 16, L)
+    assert not ops.vss_back_supported(80, 320, L) and not ops.vss_back_supported(44, 32, L) and not ops.vss_back_supported(40, 24, L)
+    assert ops.vss_back_supported(40, 160, (1 << 30) // 40 - 1) and not ops.vss_back_supported(40, 160, -(-(1 << 30) // 40))     # C L < 2^30
     x = torch.zeros(2, 40, 8, 32)
     nb, nf = ops._gdmlp_x6_cost(x=x, Hd=160, pre=None)
     assert (nb, nf) == (8.0 * x.numel(), 12.0 * 2 * 8 * 32 * (320 * 40 + 160 * 40))         # without pre: as it was
