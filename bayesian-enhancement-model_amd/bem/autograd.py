@@ -377,7 +377,7 @@ class VSSBlockFn(Function):
         del dysn
         ops.pw_wgrad_(dx2, nys, grad_of(oww), dbias=None if owb is None else grad_of(owb))
         del nys
-        wall, dtw, dtb, A, Ds = op._scan_params()
+        wall, dtw, dtb, A, Ds, _ = op._scan_params()
         M = R + 2 * op.d_state                           # x_dbl rows per direction
         dysT = ops.transpose_planes(dys)
         xcT = ops.transpose_planes(xc)

@@ -291,11 +291,12 @@ class SS2D(nn.Module):
         def prep():
             xw = self.x_proj_weight.detach()                                # (4, R+2N, C)
             # one x_proj GEMM over the row-major planes for all four directions: rows [dir 0 | dir 2 | dir 1 | dir 3]
-            wall = ops.pack_pw_weight(torch.cat([xw[0], xw[2], xw[1], xw[3]], 0).contiguous())
+            rows = torch.cat([xw[0], xw[2], xw[1], xw[3]], 0).float().contiguous()     # raw f32: what bem_ss2d_core_small_f32 reads
+            wall = ops.pack_pw_weight(rows)
             A = -torch.exp(self.A_logs.detach().float())                    # (4C, N): flat (4C) for the d_state = 1 kernels
             A = (A.reshape(-1) if self.d_state == 1 else A).contiguous()
             return (wall, self.dt_projs_weight.detach().contiguous(), self.dt_projs_bias.detach().contiguous(), A,
-                    self.Ds.detach().float().contiguous())
+                    self.Ds.detach().float().contiguous(), rows)
         return ops.derived(self).get("scan", [self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds], prep)
 
     def tail_deferrable(self, C):
@@ -307,12 +308,24 @@ class SS2D(nn.Module):
         """x + out_proj(out_norm(y0 + y1)), (y0, y1) = scan(SiLU(dw(in_proj(LN(x)))))  (vmamba.py:700-716 + 547-698), for every d_state.
         keep=True (the training forward, VSSBlockFn) returns (out, (t, xc, xd, xd1, y0, y1)): the intermediates the backward
         reads, y0 / y1 row-major (B, Ci, H, W).  defer_tail=True returns no output but the ``pre`` operands of ops.gdmlp_x6:
-        (y0, y1, out_norm weight, bias, eps, packed row-permuted out_proj weight, out_proj bias)."""
+        (y0, y1, out_norm weight, bias, eps, packed row-permuted out_proj weight, out_proj bias).  With neither, d_state 1 and a plane of
+        at most 256 pixels (ops.ss2d_core_small_supported) everything between in_proj and out_proj is one kernel."""
         B, C, H, W = x.shape
         Ci, R, N, L = self.d_inner, self.dt_rank, self.d_state, H * W
         M = R + 2 * N                                    # x_dbl rows per direction: [dt_0..dt_{R-1} | B_0..B_{N-1} | C_0..C_{N-1}]
-        wall, dtw, dtb, A, Ds = self._scan_params()
+        wall, dtw, dtb, A, Ds, xrows = self._scan_params()
         lnw, lnb = norm.weight.detach(), norm.bias.detach()
+        on = self.out_norm
+        # small planes (Stage I's 16x16 .. 4x4 maps): depthwise conv + SiLU, x_proj and the four scans in one kernel with a sample's planes
+        # in LDS (bem_ss2d_core_small_f32) -- no xc, x_dbl or transposed plane in memory, one y instead of y0 / y1.  The fused tail
+        # (defer_tail) and the training forward (keep) need y0 / y1 and keep the chain.
+        if ops.USE_SS2D_CORE and not keep and not defer_tail and ops.ss2d_core_small_supported(Ci, H, W, R, N):
+            Wp, b = self.in_proj.gemm_weights(B)
+            w, bw = self.conv2d.dw_weights(B)
+            t = ops.pw_gemm(x, Wp, Ci, ln=(lnw, lnb), ln_eps=norm.eps, bias=b)
+            y = ops.ss2d_core_small(t, w, bw, xrows, dtw, dtb, A, Ds)
+            Wp, b = self.out_proj.gemm_weights(B)
+            return ops.pw_gemm(y, Wp, _out_features(self.out_proj), ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
         # row-major scan (d_state = 1): no transposed copy of xc, y1 comes back row-major (the column orientation goes through LDS)
         rm = N == 1 and ops.ss2d_scan_rm_supported(H, W, R)
         # LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel (bem_ss2d_front_x6_f32).  The in_proj output t stays in
@@ -342,7 +355,6 @@ class SS2D(nn.Module):
             else:
                 y0, y1 = ops.ss2d_scan(x0, x1, xd0v, xd1v, dtw, dtb, A, Ds)
             y0, y1 = y0.view(B, Ci, H, W), ops.transpose_planes(y1.view(B, Ci, W, H))
-        on = self.out_norm
         if defer_tail:
             op = self.out_proj
             Wpp = ops.derived(self).get("vss_back", [op.weight], lambda: ops.pack_vss_back_outproj(op.weight.detach()))

@@ -319,6 +319,44 @@ def ss2d_scan_rm(x, xd0, xd1, dtw, dtb, A, Ds):
     return y0, y1
 
 
+# SS2D's conv + x_proj + scans as one kernel on small planes (bem_ss2d_core_small_f32): a test reaches the six-launch chain by switching it off.
+USE_SS2D_CORE = True
+
+
+def ss2d_core_small_supported(C, H, W, R, N=1):
+    """d_state N = 1, H W <= 256 and a sample's planes within one CU's LDS (the library states the exact bound)."""
+    return N == 1 and bool(lib().bem_ss2d_core_small_supported(int(C), int(H), int(W), int(R)))
+
+
+def ss2d_core_small(t, dww, dwb, xw, dtw, dtb, A, Ds):
+    """t (B,C,H,W) -> y (B,C,H,W) = (y_dir0 + y_dir2) + (y_dir1 + y_dir3) of the four-direction scan over xc = SiLU(dw3x3(t) + dwb) with
+    x_dbl = xw xc, in one launch.  dww (C,1,3,3) or (B,C,1,3,3), dwb (C) | (B,C) | None as for dwconv3x3; xw (4(R+2),C) the raw x_proj rows
+    in the order [dir 0 | dir 2 | dir 1 | dir 3]; dtw (4,C,R), dtb (4,C), A (4C), Ds (4C)."""
+    for n, v in (("t", t), ("dww", dww), ("xw", xw), ("dtw", dtw), ("dtb", dtb), ("A", A), ("Ds", Ds)):
+        _chk(v, n)
+    _chk(dwb, "dwb", optional=True)
+    B, C, H, W = t.shape
+    if dtw.dim() != 3 or dtw.shape[:2] != (4, C):
+        raise ValueError(f"ss2d_core_small: dtw {tuple(dtw.shape)} is not (4, {C}, R)")
+    R = dtw.shape[2]
+    if not ss2d_core_small_supported(C, H, W, R, 1 if A.dim() == 1 else A.shape[1]):
+        raise ValueError(f"ss2d_core_small: C = {C}, plane {H}x{W}, dt_rank {R} not supported")
+    per_b = dww.dim() == 5
+    if tuple(dww.shape[-4:]) != (C, 1, 3, 3) or (per_b and dww.shape[0] != B) or dww.dim() not in (4, 5):
+        raise ValueError(f"ss2d_core_small: depthwise weight {tuple(dww.shape)} vs {C} channels, batch {B}")
+    bb = 0
+    if dwb is not None:
+        if dwb.shape[-1] != C or dwb.dim() > 2 or (dwb.dim() == 2 and dwb.shape[0] not in (1, B)):
+            raise ValueError("ss2d_core_small: bias shape")
+        bb = C if (dwb.dim() == 2 and dwb.shape[0] == B and B > 1) else 0
+    if xw.shape != (4 * (R + 2), C) or dtb.shape != (4, C) or A.numel() != 4 * C or Ds.numel() != 4 * C:
+        raise ValueError("ss2d_core_small: parameter shapes")
+    y = torch.empty_like(t)
+    check(lib().bem_ss2d_core_small_f32(_p(t), _p(dww), (C * 9 if per_b else 0), _p(dwb), bb, _p(xw), _p(dtw), _p(dtb), _p(A), _p(Ds), _p(y),
+                                        B, C, H, W, R, _stream()), "ss2d_core_small")
+    return y
+
+
 def _transpose(src, src_c0, C, dst=None, dst_c0=0):
     """dst[:, dst_c0:dst_c0+C] (B,*,W,H) = the planes of src[:, src_c0:src_c0+C] (B,*,H,W) transposed.  The planes of a launch go into
     gridDim.z: one launch per _GRID_MAX // C batch rows.  C None: every channel from src_c0 on; dst None: a new (B,C,W,H) tensor.  Returns dst."""

@@ -113,6 +113,22 @@ int bem_ss2d_scan_n_f32(const float* x0, const float* x1, const float* xd0, cons
                         const float* A, const float* Ds, float* y0, float* y1, int B, int C, int L, int R, int N,
                         int64_t xd0_bstride, int64_t xd1_bstride, void* stream);
 
+/* The deterministic middle of SS2D (d_state = 1) on small planes as one kernel, one workgroup per sample with the sample's planes in LDS:
+ *   y = (y_dir0 + y_dir2) + (y_dir1 + y_dir3), row-major, of xc = SiLU(dw3x3(t) + bias), x_dbl = x_proj(xc) and the four-direction scan.
+ *   t   (B,C,H,W)          the in_proj output
+ *   dww (C,9) | (B,C,9)    depthwise weights, dww_bstride = 0 (shared) or the elements between samples
+ *   dwb (C) | (B,C) | NULL depthwise bias, dwb_bstride likewise
+ *   xw  (4(R+2),C)         raw f32 x_proj rows, directions in the order [0 | 2 | 1 | 3], per direction [dt_0..dt_{R-1}, B, C]
+ *   dtw (4,C,R), dtb (4,C), A (4C) = -exp(A_logs), Ds (4C)
+ *   y   (B,C,H,W)          out
+ * Neither xc nor x_dbl nor a transposed plane reaches memory; no atomics (the same bits from launch to launch).
+ * bem_ss2d_core_small_supported: C % 4 == 0, W % 4 == 0, R >= 1, H W = 64, 128 or 256 or below 64, and
+ * 4 ((H W < 64 ? 5 C H W + 64 : C H W) + 4 (R + 2) (H W + C) + 4 C (R + 3)) bytes within 160 KiB of LDS.  t, y and xw on 16 bytes. */
+int bem_ss2d_core_small_supported(int C, int H, int W, int R);
+int bem_ss2d_core_small_f32(const float* t, const float* dww, int64_t dww_bstride, const float* dwb, int64_t dwb_bstride,
+                            const float* xw, const float* dtw, const float* dtb, const float* A, const float* Ds, float* y,
+                            int B, int C, int H, int W, int R, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pointwise (1x1) channel-mix GEMM with fused prologue / epilogue (argument block of bem_pw_gemm_x6_f32).  Replaces
  * Linear2d / nn.Conv2d(k=1) / LayerNorm2d+Linear2d chains (vmamba.py:42-63,123-133,702,715,1326-1334).

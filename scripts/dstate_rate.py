@@ -54,7 +54,7 @@ for N in [int(v) for v in a.n.split(",")]:
     # the scan pair alone, on the operands forward_fused hands it
     from bem import ops
     op = blk.op
-    wall, dtw, dtb, A, Ds = op._scan_params()
+    wall, dtw, dtb, A, Ds, _ = op._scan_params()
     M = R + 2 * N
     xc = torch.randn(B, C, H, H, device="cuda")
     xd = ops.pw_gemm(xc, wall, 4 * M)
