@@ -19,6 +19,8 @@ scores every candidate with UIQM and UCIQE on the device (bem.ops.uiqm_uciqe) an
 ``alexnet-owt-7be5be79.pth`` of torchvision and ``alex.pth`` of the lpips package, are data and not shipped here: ``--lpips_weights DIR``, the
 environment variable BEM_LPIPS_WEIGHTS or experiments/pretrained_models/ names the directory holding them.  Scoring happens after the
 candidates are gathered, so every mode works on the sample-sharded ``torchrun`` path.
+``--weights_key`` / ``--cond_weights_key`` (default ``params``) name the state dict of each checkpoint to load: ``params_ema`` evaluates the
+averaged weights of a run trained with ``train.ema_decay``; a key the file lacks stops the driver with the keys it has.
 ``--sample_chunk K`` runs the samples of an image K at a time (BEMPipeline.enhance(sample_chunk=K): the memory knob for many samples of
 large images; every chunk draws under a fresh Philox epoch, so the N samples differ from the single batch's with the same seed);
 ``--sample_chunk auto`` measures one one-sample forward per image size and picks the largest K whose estimate stays under half the free
@@ -52,6 +54,8 @@ def get_parser():
     p.add_argument("--cond_opt", type=str, default="your condition_yaml.yaml", help="Path to option YAML file.")
     p.add_argument("--weights", default="yourweight.pth", type=str, help="Path to weights")
     p.add_argument("--cond_weights", default="yourweight.pth", type=str, help="Path to weights")
+    p.add_argument("--weights_key", default="params", type=str, help="state dict of --weights to load: params, or params_ema (averaged weights)")
+    p.add_argument("--cond_weights_key", default="params", type=str, help="state dict of --cond_weights to load: params, or params_ema")
     p.add_argument("--dataset", default="yourdataset", type=str, help="Name of dataset")
     p.add_argument("--GT_mean", action="store_true", help="Use the mean of GT to rectify the output of the model")
     p.add_argument("--num_samples", default=200, type=int, help="Number of random samples")
@@ -90,9 +94,17 @@ def save_rgb(path, img01_hw3):
     Image.fromarray(np.rint(np.clip(img01_hw3, 0, 1) * 255.0).astype(np.uint8)).save(path)   # img_as_ubyte
 
 
-def load_params(net, path):
+def load_params(net, path, key="params"):
+    """``key``: which state dict of the checkpoint to load -- ``params``, or ``params_ema`` for the averaged weights of a run trained with
+    ``train.ema_decay``.  A file that is a bare state dict serves as ``params``; any other missing key is an error."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
-    sd = ck["params"] if "params" in ck else ck
+    if key in ck:
+        sd = ck[key]
+    elif key == "params" and not any(isinstance(v, dict) for v in ck.values()):
+        sd = ck
+    else:
+        keys = sorted(map(str, ck))
+        raise KeyError(f"{path}: no '{key}' in the checkpoint; keys present: {keys[:8] + (['...'] if len(keys) > 8 else [])}")
     net.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()})      # eval.py:98-100 (strict)
 
 
@@ -179,8 +191,11 @@ def main(argv=None):
     net = build_model(opt).net_g
     set_prediction_type(net, deterministic=args.deterministic)
     cond_net = build_model(cond_opt).net_g
-    load_params(net, args.weights)
-    load_params(cond_net, args.cond_weights)
+    try:
+        load_params(net, args.weights, args.weights_key)
+        load_params(cond_net, args.cond_weights, args.cond_weights_key)
+    except KeyError as e:
+        raise SystemExit(f"--weights_key / --cond_weights_key: {e.args[0]}")
     net, cond_net = net.cuda().eval(), cond_net.cuda().eval()
     # scale from the Stage-I option file, noise level from the Stage-II one, default 0 (eval.py:174-176,207)
     pipe = BEMPipeline(net, cond_net, opt.get("condition", {}).get("scale_down", 16), cond_opt.get("condition", {}).get("noise_level", 0))

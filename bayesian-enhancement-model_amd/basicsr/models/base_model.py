@@ -54,9 +54,29 @@ class BaseModel:
 
     def load_network(self, net, load_path, strict=True, param_key="params"):
         ck = torch.load(load_path, map_location="cpu", weights_only=True)
+        if param_key is not None and param_key not in ck and "params" in ck:
+            print(f"Loading: {param_key} does not exist, use params.", flush=True)       # base_model.py:331-335
+            param_key = "params"
         sd = ck[param_key] if param_key is not None and param_key in ck else ck
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
         net.load_state_dict(sd, strict=strict)
+
+    def init_ema_weights(self, net_ema, weight_ema):
+        """The averaged net's start (image_enhancer_model.py:77-83): ``params_ema`` of ``path.pretrain_network_g`` where that is set (a
+        resumed run restores both copies; a file without the key gives ``params``), else a copy of net_g.  It stays in eval()."""
+        path = self.opt["path"].get("pretrain_network_g")
+        if path is not None:
+            self.load_network(net_ema, path, self.opt["path"].get("strict_load_g", True), "params_ema")     # copies into the flat buffer's views
+        else:
+            weight_ema.copy_from_net()
+        net_ema.eval()
+
+    def with_ema_state(self, save_dict):
+        """``save_dict`` plus ``params_ema`` when the model keeps an averaged net: save_best's file then also holds the weights that
+        earned the metric."""
+        if hasattr(self, "net_g_ema"):
+            save_dict["params_ema"] = OrderedDict((k, v.detach().cpu()) for k, v in self.net_g_ema.state_dict().items())
+        return save_dict
 
     def save(self, epoch, current_iter):
         """Save networks and training state (overridden by the model classes)."""

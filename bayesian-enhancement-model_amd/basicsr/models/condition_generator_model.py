@@ -1,5 +1,6 @@
 """ConditionGenerator (basicsr/models/condition_generator_model.py): Stage-I net + BNN conversion (:28-75), training settings and
-optimizer (:77-144), data feed (:146-174), the training step with the KL term (:176-218), checkpoints (:346-370)."""
+optimizer (:77-144), data feed (:146-174), the training step with the KL term (:176-218), checkpoints (:346-370); with
+``train.ema_decay > 0`` the averaged copy ``net_g_ema`` (bem.train.WeightEma), which validation runs and ``save`` writes as ``params_ema``."""
 import os
 from collections import OrderedDict
 
@@ -12,17 +13,14 @@ from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
 from bem import bayes, ops
-from bem.train import BemAdamW, StepState
+from bem.train import BemAdamW, StepState, WeightEma
 
 
 @MODEL_REGISTRY.register()
 class ConditionGenerator(BaseModel):
     def __init__(self, opt):
         super().__init__(opt)
-        self.net_g = build_network(opt["network_g"])
-        cfg = {"sigma_init": opt.get("sigma_init", 0.05), "decay": 0.998, "pretrain": False}
-        (convert2bnn_selective if opt.get("selective", True) else convert2bnn)(self.net_g, cfg)
-        self.net_g = self.model_to_device(self.net_g)
+        self.net_g = self.model_to_device(self._build_bnn())
         path = opt["path"].get("pretrain_network_g")
         if path is not None:
             self.load_network(self.net_g, path, opt["path"].get("strict_load_g", True), opt["path"].get("param_key", "params"))
@@ -34,12 +32,16 @@ class ConditionGenerator(BaseModel):
                 raise NotImplementedError("ConditionGenerator: mixup augmentation is host-side data preparation outside the hot path")
             self.init_training_settings()
 
+    def _build_bnn(self):
+        net = build_network(self.opt["network_g"])
+        cfg = {"sigma_init": self.opt.get("sigma_init", 0.05), "decay": 0.998, "pretrain": False}
+        (convert2bnn_selective if self.opt.get("selective", True) else convert2bnn)(net, cfg)
+        return net
+
     def init_training_settings(self):
         self.net_g.train()
         train_opt = self.opt["train"]
         self.ema_decay = train_opt.get("ema_decay", 0)
-        if self.ema_decay > 0:
-            raise NotImplementedError("ConditionGenerator: ema_decay > 0 (a second, averaged copy of the net) is not used by the shipped option files")
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
         if train_opt.get("perceptual_opt"):
             raise NotImplementedError("ConditionGenerator: perceptual_opt is not available for Stage I: its predictions are 8x8 planes, below what "
@@ -51,6 +53,13 @@ class ConditionGenerator(BaseModel):
         self.optimizers, self.schedulers = [], []
         self.setup_optimizers()
         self.setup_schedulers()
+        self.weight_ema = None
+        if self.ema_decay > 0:
+            # :69-83: net_g_ema (converted like net_g) is only validated and saved, on every rank the same average (never wrapped)
+            print(f"Use Exponential Moving Average with decay: {self.ema_decay}", flush=True)
+            self.net_g_ema = self._build_bnn().to(self.device)
+            self.weight_ema = WeightEma(self.optimizer_g, self.get_bare_model(self.net_g), self.net_g_ema)
+            self.init_ema_weights(self.net_g_ema, self.weight_ema)
 
     def setup_optimizers(self):
         normal, custom = [], []
@@ -124,10 +133,16 @@ class ConditionGenerator(BaseModel):
         mgn = self.opt["train"].get("max_grad_norm")
         total_norm = self.optimizer_g.clip_grad_norm_(mgn if mgn else float("inf"))
         # a parameter outside this iteration's graph has .grad None in the reference and is skipped by AdamW: the mask token without a mask
+        # model_ema(decay) (:213-214) after the step has put skipped slices back: the mask token is averaged in every iteration.  decay is
+        # constant, so a captured step records the launch with it by value, as one more node on the same stream
         if state is not None:
             self.optimizer_g.step_captured(state, skip=skip)
+            if self.weight_ema is not None:
+                self.weight_ema.update(self.ema_decay)
             return loss_dict, total_norm
         self.optimizer_g.step(skip=skip)
+        if self.weight_ema is not None:
+            self.weight_ema.update(self.ema_decay)
         self.log_dict = self.reduce_loss_dict(loss_dict)
         return total_norm
 
@@ -171,20 +186,21 @@ class ConditionGenerator(BaseModel):
     def validation(self, dataloader, current_iter, tb_logger=None, save_img=False, rgb2bgr=True, use_image=True):
         """Mean PSNR of the predicted condition planes against the down-sampled ground truth, deterministic weights (mu), float form on
         the device."""
-        was_training = self.net_g.training
-        self.net_g.eval()
-        set_prediction_type(self.net_g, True)
+        net = self.net_g_ema if hasattr(self, "net_g_ema") else self.net_g       # :239-247: the averaged net where there is one
+        was_training = net.training
+        net.eval()
+        set_prediction_type(net, True)
         tot, cnt = 0.0, 0
         for data in dataloader:
             self.feed_data(data)
-            pred = self.net_g(self.lq.contiguous())[-1]
+            pred = net(self.lq.contiguous())[-1]
             h, w = pred.shape[-2:]
             _, ps = ops.candidate_finalize(pred.contiguous(), self.gt.contiguous(), 1, h, w, False)
             tot += float(ps.sum())
             cnt += pred.shape[0]
-        set_prediction_type(self.net_g, False)
+        set_prediction_type(net, False)
         if was_training:
-            self.net_g.train()
+            net.train()
         self.metric_results = {"psnr": tot / max(cnt, 1)}
         if self.opt.get("rank", 0) == 0:
             print(f"Validation,\t\t # psnr: {self.metric_results['psnr']:.4f}", flush=True)
@@ -202,10 +218,13 @@ class ConditionGenerator(BaseModel):
                 os.remove(f)
             sd = {(k[7:] if k.startswith("module.") else k): v.detach().cpu() for k, v in self.get_bare_model(self.net_g).state_dict().items()}
             os.makedirs(root, exist_ok=True)
-            torch.save({param_key: sd}, path)
+            torch.save(self.with_ema_state({param_key: sd}), path)
         return path
 
     # -- checkpoints (:346-370) ---------------------------------------------------------------------------------------------
     def save(self, epoch, current_iter, **kwargs):
-        self.save_network(self.net_g, "net_g", current_iter)
+        if hasattr(self, "net_g_ema"):
+            self.save_network([self.net_g, self.net_g_ema], "net_g", current_iter, param_key=["params", "params_ema"])
+        else:
+            self.save_network(self.net_g, "net_g", current_iter)
         self.save_training_state(epoch, current_iter, **kwargs)

@@ -4,7 +4,9 @@
 The step runs entirely on the HIP path: condition upsample + concat (bem.ops), forward / backward (bem.autograd), global-norm clip +
 AdamW on one flat buffer (bem.train.BemAdamW), the pixel loss and -- with ``train.perceptual_opt`` -- the VGG19 perceptual loss
 (bem.percep), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
-gradient norm come back as device scalars (read them when logging).  AMP (`use_amp`) is not offered: the path is f32."""
+gradient norm come back as device scalars (read them when logging).  AMP (`use_amp`) is not offered: the path is f32.
+``train.ema_decay > 0`` keeps ``net_g_ema`` (:69-83), averaged by one more launch after the optimizer step (bem.train.WeightEma), validated
+instead of net_g (:239-247) and saved as ``params_ema`` (:341-347)."""
 from collections import OrderedDict
 
 import torch
@@ -15,7 +17,7 @@ from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
 from bem import ops
-from bem.train import BemAdamW
+from bem.train import BemAdamW, WeightEma
 
 
 @MODEL_REGISTRY.register()
@@ -41,8 +43,6 @@ class ImageEnhancer(BaseModel):
         self.net_g.train()
         train_opt = self.opt["train"]
         self.ema_decay = train_opt.get("ema_decay", 0)
-        if self.ema_decay > 0:
-            raise NotImplementedError("ImageEnhancer: ema_decay > 0 (a second, averaged copy of the net) is not used by the shipped option files")
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
         self.cri_perceptual = build_loss(train_opt["perceptual_opt"]).to(self.device) if train_opt.get("perceptual_opt") else None
         if self.cri_pix is None and self.cri_perceptual is None:
@@ -50,6 +50,13 @@ class ImageEnhancer(BaseModel):
         self.optimizers, self.schedulers = [], []
         self.setup_optimizers()
         self.setup_schedulers()
+        self.weight_ema = None
+        if self.ema_decay > 0:
+            # :69-83: net_g_ema is only validated and saved, on every rank the same average of the same parameters (never wrapped)
+            print(f"Use Exponential Moving Average with decay: {self.ema_decay}", flush=True)
+            self.net_g_ema = build_network(self.opt["network_g"]).to(self.device)
+            self.weight_ema = WeightEma(self.optimizer_g, self.get_bare_model(self.net_g), self.net_g_ema)
+            self.init_ema_weights(self.net_g_ema, self.weight_ema)
 
     def setup_optimizers(self):
         train_opt = self.opt["train"]
@@ -118,6 +125,8 @@ class ImageEnhancer(BaseModel):
         mgn = self.opt["train"].get("max_grad_norm")
         total_norm = self.optimizer_g.clip_grad_norm_(mgn if mgn else float("inf"))
         self.optimizer_g.step()
+        if self.weight_ema is not None:
+            self.weight_ema.update(self.ema_decay)                     # model_ema(decay), :213-214
         self.log_dict = self.reduce_loss_dict(loss_dict)
         return total_norm
 
@@ -128,8 +137,9 @@ class ImageEnhancer(BaseModel):
         noise).  The inference kernels run the forward; PSNR is the float form ``10 log10(1 / mse)`` on [0,1] tensors computed on the
         device (the reference's ``use_image: false`` branch; its uint8 / cv2 image branch and image dumps are host-side reporting)."""
         from bem import ops
-        was_training = self.net_g.training
-        self.net_g.eval()
+        net = self.net_g_ema if hasattr(self, "net_g_ema") else self.net_g       # :239-247: the averaged net where there is one
+        was_training = net.training
+        net.eval()
         s = self.opt["condition"].get("scale_down", 0) + self.opt["condition"].get("hist_patch_size", 0)
         tot, cnt = 0.0, 0
         for data in dataloader:
@@ -138,14 +148,14 @@ class ImageEnhancer(BaseModel):
             x = torch.empty(B, 6, H, W, device=self.lq.device, dtype=torch.float32)
             ops.copy_channels(self.lq.contiguous(), x, 0)
             ops.bilinear_up(self.conds, s, dst=x, dst_c0=3)
-            pred = self.net_g(x)[-1]
+            pred = net(x)[-1]
             h, w = data.get("crop_hw", (H, W))
             gt = self.gt[..., :h, :w].contiguous()
             _, ps = ops.candidate_finalize(pred.contiguous(), gt, 1, h, w, False)
             tot += float(ps.sum())
             cnt += B
         if was_training:
-            self.net_g.train()
+            net.train()
         self.metric_results = {"psnr": tot / max(cnt, 1)}
         if self.opt.get("rank", 0) == 0:
             print(f"Validation {getattr(dataloader.dataset, 'opt', {}).get('name', 'val')},\t\t # psnr: {self.metric_results['psnr']:.4f}", flush=True)
@@ -153,7 +163,10 @@ class ImageEnhancer(BaseModel):
 
     # -- checkpoints (image_enhancer_model.py:340-370) --------------------------------------------------------------------
     def save(self, epoch, current_iter, **kwargs):
-        self.save_network(self.net_g, "net_g", current_iter)
+        if hasattr(self, "net_g_ema"):
+            self.save_network([self.net_g, self.net_g_ema], "net_g", current_iter, param_key=["params", "params_ema"])
+        else:
+            self.save_network(self.net_g, "net_g", current_iter)
         self.save_training_state(epoch, current_iter, **kwargs)
 
     def save_best(self, best_metric, param_key="params"):
@@ -169,5 +182,5 @@ class ImageEnhancer(BaseModel):
                 os.remove(f)
             sd = {(k[7:] if k.startswith("module.") else k): v.detach().cpu() for k, v in self.get_bare_model(self.net_g).state_dict().items()}
             os.makedirs(root, exist_ok=True)
-            torch.save({param_key: sd}, path)
+            torch.save(self.with_ema_state({param_key: sd}), path)
         return path

@@ -2127,3 +2127,21 @@ def adamw_step_(p, g, m, v, lr, betas, eps, weight_decay, step, max_norm=0.0, su
         raise ValueError("adamw_step: buffer sizes differ")
     check(lib().bem_adamw_step_f32(_p(p), _p(g), _p(m), _p(v), n, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                    int(step), float(max_norm), _p(sumsq), _p(norm_out), _p(hyper), _stream()), "adamw_step")
+
+
+@_bracket(lambda ema, **_: (12.0 * ema.numel(), 3.0 * ema.numel()))
+def ema_update_(ema, p, decay):
+    """ema = decay * ema + (1 - decay) * p in place over two flat f32 buffers of equal length (base_model.py:77-84).  The kernel gets
+    torch's two constants, (float)decay and (float)(1 - decay) with the difference taken in double; decay = 0 copies p bit for bit."""
+    _chk(ema, "ema"); _chk(p, "p")
+    if ema.device != p.device:
+        raise ValueError(f"ema_update: ema on {ema.device}, p on {p.device}")
+    if ema.numel() != p.numel():
+        raise ValueError(f"ema_update: ema holds {ema.numel()} elements, p {p.numel()}")
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"ema_update: decay {decay} outside [0, 1]")
+    if ema.numel() == 0:                   # nothing to launch, and torch's empty tensors carry the null pointer the library refuses
+        return ema
+    check(lib().bem_ema_update_f32(_p(ema), _p(p), ema.numel(), decay, 1.0 - decay, _stream()), "ema_update")
+    return ema

@@ -64,6 +64,54 @@ class StepState:
             fn()
 
 
+class WeightEma:
+    """The exponentially averaged copy of a net's weights (``train.ema_decay``; basicsr/models/base_model.py:77-84, model_ema).
+
+    For every non-empty parameter group of ``optimizer`` (a BemAdamW over ``net``'s trainable parameters) one flat f32 buffer with the
+    layout of the group's ``p`` buffer -- same order, same ``_align4`` offsets, padding words 0 -- holds the average; the parameters of
+    ``net_ema`` with the same names are views of it, so one launch per group updates the whole copy.  Parameters of ``net`` outside the
+    optimizer (frozen ones) are copied into ``net_ema`` once, here; buffers are not averaged (``net_ema`` keeps its own), as in the reference.
+    The flat buffers start from ``net_ema``'s values: load a checkpoint into it before or after, or call ``copy_from_net()``."""
+
+    def __init__(self, optimizer: "BemAdamW", net: torch.nn.Module, net_ema: torch.nn.Module):
+        src, dst = dict(net.named_parameters()), dict(net_ema.named_parameters())
+        if src.keys() != dst.keys():
+            raise ValueError("WeightEma: the two nets' parameter names differ")
+        names = {id(p): k for k, p in src.items()}
+        self._pairs = []         # per non-empty group: (flat average, the optimizer's flat parameters)
+        with torch.no_grad():
+            for f in optimizer._flat:
+                if f is None:
+                    continue
+                buf = torch.zeros_like(f["p"])
+                off = 0
+                for p in f["params"]:
+                    q, n = dst[names.pop(id(p))], p.numel()
+                    if q.shape != p.shape or q.dtype != torch.float32 or q.device != buf.device:
+                        raise ValueError("WeightEma: the averaged net's parameters must match the trained net's (shape, float32, device)")
+                    buf[off:off + n].copy_(q.detach().reshape(-1))
+                    q.data = buf[off:off + n].view(q.shape)
+                    off += _align4(n)
+                self._pairs.append((buf, f["p"]))
+            for k in names.values():                                # not in the optimizer: copied once, never touched again
+                dst[k].copy_(src[k])
+        ops.bump_weight_epoch()
+
+    @property
+    def buffers(self):
+        """The flat averages, one per non-empty parameter group, in group order."""
+        return [e for e, _ in self._pairs]
+
+    def update(self, decay: float):
+        """ema = decay * ema + (1 - decay) * p: one launch per group on the current stream (a captured step records it as one more node)."""
+        for e, p in self._pairs:
+            ops.ema_update_(e, p, decay)
+        ops.bump_weight_epoch()        # written behind torch's version counters: the averaged net's derived-weight caches are stale
+
+    def copy_from_net(self):
+        self.update(0)
+
+
 class BemAdamW(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **ignored):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)

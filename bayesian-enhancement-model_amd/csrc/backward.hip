@@ -554,6 +554,35 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
     p[i] = pi;
 }
 
+// Averaged weights (basicsr/models/base_model.py:77-84, model_ema): ema = decay * ema + (1 - decay) * p with the two f32 constants torch's
+// mul_(decay).add_(p, alpha=1 - decay) uses, evaluated as fmaf(one_minus_decay, p, decay * ema).  decay == 0 copies p bit for bit
+// (model_ema(0)), whatever ema held.
+__device__ __forceinline__ float ema_one(float e, float p, float decay, float omd) {
+    return decay == 0.f ? p : fmaf(omd, p, decay * e);
+}
+
+// Grid-stride over 64-bit indices.  VEC (both pointers 16-byte aligned): float4 for the first n / 4 * 4 elements; the scalar loop takes the
+// last n % 4 of them, or everything without VEC.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, float decay, float omd) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        float4* e4 = reinterpret_cast<float4*>(ema);
+        const float4* p4 = reinterpret_cast<const float4*>(p);
+        for (int64_t i = t; i < n4; i += stride) {
+            float4 e = e4[i];
+            const float4 v = p4[i];
+            e.x = ema_one(e.x, v.x, decay, omd); e.y = ema_one(e.y, v.y, decay, omd);
+            e.z = ema_one(e.z, v.z, decay, omd); e.w = ema_one(e.w, v.w, decay, omd);
+            e4[i] = e;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + t; i < n; i += stride) ema[i] = ema_one(ema[i], p[i], decay, omd);
+}
+
 }  // namespace
 
 extern "C" int bem_l1_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
@@ -716,4 +745,14 @@ extern "C" int bem_adamw_step_f32(float* p, float* g, float* m, float* v, int64_
     adamw_kernel<<<GRID1D(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
                                                           max_norm, sumsq, norm_out, hyper);
     return bem_check_launch("adamw_step");
+}
+
+extern "C" int bem_ema_update_f32(float* ema, const float* p, int64_t n, float decay, float one_minus_decay, void* stream) {
+    BEM_REQUIRE(ema && p && n >= 0, "ema_update: null pointer / negative length");
+    if (n == 0) return BEM_OK;
+    const bool vec = (((uintptr_t)ema | (uintptr_t)p) & 15) == 0;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(vec ? cdiv64(n, 4) : n, 256), 2048);
+    if (vec) ema_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(ema, p, n, decay, one_minus_decay);
+    else ema_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(ema, p, n, decay, one_minus_decay);
+    return bem_check_launch("ema_update");
 }

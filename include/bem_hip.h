@@ -590,6 +590,15 @@ int bem_adamw_step_f32(float* p, float* g, float* m, float* v, int64_t n, float 
                        float weight_decay, int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper,
                        void* stream);
 
+/* base_model.py:77-84: ema = decay * ema + (1 - decay) * p over n floats.
+ * The averaged copy of the weights (train.ema_decay), one launch per flat parameter buffer, after the optimizer step.  The host passes
+ * decay = (float)decay and one_minus_decay = (float)(1.0 - (double)decay), the two constants of torch's mul_(decay).add_(p, alpha=1 - decay);
+ * per element the kernel computes fmaf(one_minus_decay, p, decay * ema): the product decay * ema rounded once, then one fused
+ * multiply-add.  decay == 0 gives ema = p bit for bit (model_ema(0), the initial copy).  ema and p must not overlap.  16-byte vector
+ * accesses when both pointers are 16-byte aligned, scalar ones otherwise and for the last n % 4 elements.  n == 0 returns 0 without a
+ * launch; n < 0 or a null pointer is BEM_ERR_INVALID. */
+int bem_ema_update_f32(float* ema, const float* p, int64_t n, float decay, float one_minus_decay, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Stage-I training: ConditionGenerator.optimize_parameters,
  * basicsr/models/condition_generator_model.py:176-218.  Everything else of that step runs on the Stage-II training entry points.
