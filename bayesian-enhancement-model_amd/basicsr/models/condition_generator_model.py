@@ -47,6 +47,10 @@ class ConditionGenerator(BaseModel):
             raise NotImplementedError("ConditionGenerator: perceptual_opt is not available for Stage I: its predictions are 8x8 planes, below what "
                                       "VGG19's deeper layers (conv5_4 needs 16x16) can take, and its training step is a captured graph; "
                                       "remove `perceptual_opt` (the Stage-I option files of the reference train on the pixel loss)")
+        if train_opt.get("ssim_opt"):
+            raise NotImplementedError("ConditionGenerator: ssim_opt is not available for Stage I: its predictions are 8x8 planes, smaller than "
+                                      "the 11x11 window of SSIMLoss; remove `ssim_opt` (the Stage-I option files of the reference train on the "
+                                      "pixel loss)")
         self.cri_perceptual = None
         if self.cri_pix is None:
             raise ValueError("Both pixel and perceptual losses are None.")

@@ -3,7 +3,7 @@
 
 The step runs entirely on the HIP path: condition upsample + concat (bem.ops), forward / backward (bem.autograd), global-norm clip +
 AdamW on one flat buffer (bem.train.BemAdamW), the pixel loss and -- with ``train.perceptual_opt`` -- the VGG19 perceptual loss
-(bem.percep), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
+(bem.percep) and -- with ``train.ssim_opt`` -- the SSIM term of basicsr/losses/my_loss.py:37-38 (csrc/ssim_loss.hip), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
 gradient norm come back as device scalars (read them when logging).  AMP (`use_amp`) is not offered: the path is f32.
 ``train.ema_decay > 0`` keeps ``net_g_ema`` (:69-83), averaged by one more launch after the optimizer step (bem.train.WeightEma), validated
 instead of net_g (:239-247) and saved as ``params_ema`` (:341-347)."""
@@ -45,8 +45,10 @@ class ImageEnhancer(BaseModel):
         self.ema_decay = train_opt.get("ema_decay", 0)
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
         self.cri_perceptual = build_loss(train_opt["perceptual_opt"]).to(self.device) if train_opt.get("perceptual_opt") else None
-        if self.cri_pix is None and self.cri_perceptual is None:
-            raise ValueError("Both pixel and perceptual losses are None.")
+        self.cri_ssim = build_loss(train_opt["ssim_opt"]).to(self.device) if train_opt.get("ssim_opt") else None
+        if self.cri_pix is None and self.cri_perceptual is None and self.cri_ssim is None:
+            raise ValueError("Pixel, perceptual and SSIM losses are all None.")
+        self._ssim_metrics()                                           # a val.metrics entry validation would refuse is refused now
         self.optimizers, self.schedulers = [], []
         self.setup_optimizers()
         self.setup_schedulers()
@@ -102,24 +104,27 @@ class ImageEnhancer(BaseModel):
         ops.bilinear_up(self.conds, s, dst=x, dst_c0=3)                # F.interpolate(conds, scale_factor=s, 'bilinear') into channels 3..5
         _, preds = self.net_g(x, mask=None)                           # the Decomp* archs ignore the MIM mask (DDWavelet_arch.py:301)
         loss_dict = OrderedDict()
-        if self.cri_perceptual is None:
-            l_total = l_pix = self.cri_pix(preds, self.gt)
-        else:
-            # :183-191: l_total = l_pix + l_percep; preds feeds both losses, its two gradients are summed by bem_add_f32 (ag.fork)
-            p_pix, p_per = ag.fork(preds) if self.cri_pix is not None else (None, preds)
-            l_percep, _ = self.cri_perceptual(p_per, self.gt)
-            l_pix = None if self.cri_pix is None else self.cri_pix(p_pix, self.gt)
-            if l_percep is None:                                         # perceptual_weight <= 0 (:186): the term is off
-                if l_pix is None:
-                    raise ValueError("Both pixel and perceptual losses are None.")
-                l_total = l_pix
-            else:
-                l_total = l_percep if l_pix is None else ag.AddFn.apply(l_pix, l_percep)
+        # :183-191: l_total = l_pix + l_percep (+ l_ssim, my_loss.py:37-38) over the configured terms; preds feeds each of them, its
+        # gradients are summed by bem_add_f32 (ag.fork_n; one term alone takes preds itself)
+        crits = (self.cri_pix, self.cri_perceptual, self.cri_ssim)
+        heads = iter(ag.fork_n(preds, sum(c is not None for c in crits)))
+        l_pix, l_percep, l_ssim = ((None if c is None else c(next(heads), self.gt)) for c in crits)
+        if l_percep is not None:
+            l_percep, _ = l_percep                                       # None with perceptual_weight <= 0 (:186): the term is off
+        l_total = None
+        for l in (l_pix, l_percep, l_ssim):
+            if l is not None:
+                l_total = l if l_total is None else ag.AddFn.apply(l_total, l)
+        if l_total is None:
+            raise ValueError("Pixel, perceptual and SSIM losses are all None.")
         if l_pix is not None:
             w = self.opt["train"]["pixel_opt"].get("loss_weight", 1)
             loss_dict["l_pix"] = l_pix.detach() if w == 1 else l_pix.detach() / w
-        if self.cri_perceptual is not None and l_percep is not None:
+        if l_percep is not None:
             loss_dict["l_percep"] = l_percep.detach() / self.cri_perceptual.perceptual_weight          # :188
+        if l_ssim is not None:
+            w = self.cri_ssim.loss_weight
+            loss_dict["l_ssim"] = l_ssim.detach() if w == 1 else l_ssim.detach() / w                  # the unweighted 1 - SSIM
         l_total.backward()
         self.sync_gradients(self.optimizer_g)
         mgn = self.opt["train"].get("max_grad_norm")
@@ -141,7 +146,8 @@ class ImageEnhancer(BaseModel):
         was_training = net.training
         net.eval()
         s = self.opt["condition"].get("scale_down", 0) + self.opt["condition"].get("hist_patch_size", 0)
-        tot, cnt = 0.0, 0
+        ssim_names = self._ssim_metrics()
+        tot, cnt, ssim_tot = 0.0, 0, 0.0
         for data in dataloader:
             self.feed_train_data(data)
             B, _, H, W = self.lq.shape
@@ -154,12 +160,40 @@ class ImageEnhancer(BaseModel):
             _, ps = ops.candidate_finalize(pred.contiguous(), gt, 1, h, w, False)
             tot += float(ps.sum())
             cnt += B
+            if ssim_names and ssim_tot == ssim_tot:
+                if h <= 10 or w <= 10:
+                    if self.opt.get("rank", 0) == 0:
+                        print(f"Warning: validation SSIM needs images larger than its 11x11 window, got {h} x {w}: reported as nan", flush=True)
+                    ssim_tot = float("nan")
+                else:
+                    # calculate_ssim (basicsr/metrics/psnr_ssim.py:88-132) on tensor2img values of the cropped output and target
+                    ssim_tot += float(ops.ssim(pred[..., :h, :w].contiguous(), gt, 1).sum())
         if was_training:
             net.train()
         self.metric_results = {"psnr": tot / max(cnt, 1)}
+        line = f"Validation {getattr(dataloader.dataset, 'opt', {}).get('name', 'val')},\t\t # psnr: {self.metric_results['psnr']:.4f}"
+        for name in ssim_names:
+            self.metric_results[name] = ssim_tot / max(cnt, 1)
+            line += f"\t # {name}: {self.metric_results[name]:.4f}"
         if self.opt.get("rank", 0) == 0:
-            print(f"Validation {getattr(dataloader.dataset, 'opt', {}).get('name', 'val')},\t\t # psnr: {self.metric_results['psnr']:.4f}", flush=True)
+            print(line, flush=True)
         return self.metric_results["psnr"]
+
+    def _ssim_metrics(self):
+        """Names of the ``val.metrics`` entries of type calculate_ssim.  crop_border / test_y_channel on one of them are refused: the device
+        metric (bem_ssim_f32) is the whole-image RGB form, which is what every option file of the reference asks for (0 / false)."""
+        names = []
+        for name, m in ((self.opt.get("val") or {}).get("metrics") or {}).items():
+            if not isinstance(m, dict) or m.get("type") != "calculate_ssim":
+                continue
+            if m.get("crop_border", 0) != 0 or m.get("test_y_channel", False):
+                raise NotImplementedError(f"ImageEnhancer: val.metrics.{name}: crop_border={m.get('crop_border', 0)}, test_y_channel="
+                                          f"{m.get('test_y_channel', False)}: validation SSIM is computed on the whole RGB image (crop_border 0, "
+                                          "test_y_channel false)")
+            if name == "psnr":
+                raise ValueError("ImageEnhancer: val.metrics.psnr is the PSNR entry's result; give the calculate_ssim entry another name")
+            names.append(name)
+        return names
 
     # -- checkpoints (image_enhancer_model.py:340-370) --------------------------------------------------------------------
     def save(self, epoch, current_iter, **kwargs):

@@ -75,6 +75,16 @@ def fork(x):
     return ForkFn.apply(x) if x.requires_grad else (x, x)
 
 
+def fork_n(x, n):
+    """x for n >= 1 consumers, as a list: a chain of n - 1 two-way forks, so every sum of incoming gradients is a bem_add_f32
+    (g1 + (g2 + (g3 + ...))); one consumer gets x itself."""
+    heads = []
+    for _ in range(n - 1):
+        h, x = fork(x)
+        heads.append(h)
+    return heads + [x]
+
+
 class L1LossFn(Function):
     """basicsr/losses/losses.py L1Loss(loss_weight, reduction='mean')."""
 
@@ -94,6 +104,30 @@ class L1LossFn(Function):
 
 def l1_loss(pred, gt, weight=1.0):
     return L1LossFn.apply(pred, gt, float(weight))
+
+
+class SSIMLossFn(Function):
+    """basicsr/losses/my_loss.py:37-38: weight * (1 - ssim(pred, gt)), 11x11 Gaussian window, data range 1.  The forward launch writes the
+    three coefficient maps of the backward when pred wants a gradient; gt takes none."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, weight):
+        pred, gt = pred.contiguous(), gt.contiguous()
+        ctx.weight = weight
+        if not ctx.needs_input_grad[0]:
+            return ops.ssim_loss(pred, gt, weight).reshape(())
+        loss, coef = ops.ssim_loss(pred, gt, weight, want_grad=True)
+        ctx.save_for_backward(pred, gt, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, gt, coef = ctx.saved_tensors
+        return ops.ssim_loss_bwd(pred, gt, coef, ctx.weight, g.reshape(1).contiguous().float()), None, None
+
+
+def ssim_loss(pred, gt, weight=1.0):
+    return SSIMLossFn.apply(pred, gt, float(weight))
 
 
 # ------------------------------------------------------------------------------------------------------------------

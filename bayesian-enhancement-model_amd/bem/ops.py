@@ -1713,6 +1713,69 @@ def l1_loss_bwd(pred, gt, weight=1.0, gmul=None):
     return dp
 
 
+SSIM_WINDOW = 11          # the Gaussian window of the SSIM loss (sigma 1.5): the valid region of an H x W plane is (H - 10) x (W - 10)
+
+
+def ssim_loss_tile():
+    """Edge of the square tile one workgroup of the SSIM-loss kernels takes (csrc/ssim_loss.hip)."""
+    return int(lib().bem_ssim_loss_tile())
+
+
+def _ssim_loss_planes(op, pred, gt):
+    """Operand check shared by the SSIM loss and its backward -> (planes, H, W)."""
+    _chk(pred, "pred"); _chk(gt, "gt")
+    if pred.dim() != 4 or pred.shape != gt.shape:
+        raise ValueError(f"{op}: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be one (B,C,H,W) shape")
+    B, C, H, W = pred.shape
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f"{op}: {H} x {W} planes are smaller than the {SSIM_WINDOW}x{SSIM_WINDOW} window")
+    if B * C == 0:
+        raise ValueError(f"{op}: empty tensor")
+    return B * C, H, W
+
+
+def _ssim_valid(pred):
+    return _prod(pred.shape[:2]) * (pred.shape[2] - SSIM_WINDOW + 1) * (pred.shape[3] - SSIM_WINDOW + 1)
+
+
+def ssim_loss_cost(pred, want_grad=False, **_):
+    """Algorithmic (bytes, flops) of the forward: pred and gt read once, the three coefficient maps written when a gradient is wanted;
+    5 separable 11-tap filters (2 x 11 multiply-adds per position and map, at the valid region's size) and ~40 flops of map arithmetic."""
+    nv = _ssim_valid(pred)
+    return 8.0 * pred.numel() + (12.0 * nv if want_grad else 0.0), nv * (5 * 2 * 2 * SSIM_WINDOW + 40.0)
+
+
+def ssim_loss_bwd_cost(pred, **_):
+    """Algorithmic (bytes, flops) of the backward: the three maps, pred and gt read once, dpred written; 3 separable filters + 5 flops."""
+    return 12.0 * _ssim_valid(pred) + 12.0 * pred.numel(), pred.numel() * (3 * 2 * 2 * SSIM_WINDOW + 5.0)
+
+
+@_bracket(ssim_loss_cost)
+def ssim_loss(pred, gt, weight=1.0, want_grad=False):
+    """loss (1,) = weight * (1 - mean SSIM(pred, gt)) on (B,C,H,W) tensors in [0,1]: 11x11 Gaussian window (sigma 1.5), valid region,
+    every (b,c) plane on its own (my_loss.py:37-38).  ``want_grad``: also the backward's coefficient maps (3,B,C,H-10,W-10), written by
+    the same launch -> (loss, coef)."""
+    P, H, W = _ssim_loss_planes("ssim_loss", pred, gt)
+    dev = pred.device
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    coef = torch.empty((3,) + tuple(pred.shape[:2]) + (H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1), device=dev, dtype=torch.float32) if want_grad else None
+    ws = _scratch("ssim_loss", dev, int(lib().bem_ssim_loss_ws_elems(P, H, W)), torch.float64)
+    check(lib().bem_ssim_loss_f32(_p(pred), _p(gt), _p(loss), _p(coef), _p(ws), P, H, W, float(weight), _stream()), "ssim_loss")
+    return (loss, coef) if want_grad else loss
+
+
+@_bracket(ssim_loss_bwd_cost)
+def ssim_loss_bwd(pred, gt, coef, weight=1.0, gmul=None):
+    """dpred of ssim_loss from the coefficient maps its forward wrote (gmul: device scalar dL/dloss, None = 1)."""
+    P, H, W = _ssim_loss_planes("ssim_loss_bwd", pred, gt)
+    _chk(coef, "coef"); _chk(gmul, "gmul", optional=True)
+    if tuple(coef.shape) != (3,) + tuple(pred.shape[:2]) + (H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1):
+        raise ValueError(f"ssim_loss_bwd: coef {tuple(coef.shape)} is not the three valid-region maps of pred {tuple(pred.shape)}")
+    dp = torch.empty_like(pred)
+    check(lib().bem_ssim_loss_bwd_f32(_p(pred), _p(gt), _p(coef), _p(dp), P, H, W, float(weight), _p(gmul), _stream()), "ssim_loss_bwd")
+    return dp
+
+
 def iwt_hamilton_bwd(q1w, q2w, dout):
     _chk(q1w, "q1w"); _chk(q2w, "q2w"); _chk(dout, "dout")
     B, C, h, w = q1w.shape

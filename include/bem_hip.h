@@ -489,6 +489,23 @@ int bem_ss2d_front_x6_f32(const float* x, const float* ln_w, const float* ln_b, 
 int bem_l1_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
                     const float* gmul, void* stream);
 
+/* SSIM loss (basicsr/losses/my_loss.py:37-38: 1 - pytorch_msssim.ssim(y_true, y_pred, data_range=1.0, size_average=True)) on f32
+ * tensors in [0,1], no quantisation (csrc/ssim_loss.hip states the formulas).  pred, gt (planes,H,W), planes = B*C handled independently,
+ * H, W >= 11, H*W < 2^31, planes <= 32768 * 65535: loss[0] = weight * (1 - mean of the SSIM map over all planes * (H-10) * (W-10) valid
+ * positions), bit-reproducible from call to call (per-workgroup f64 partials in ws, added in a fixed order by a second launch; no atomics).
+ * coef (or NULL): the three coefficient maps a | b | c of the backward, 3 x (planes,H-10,W-10), written by the same launch.
+ * ws: bem_ssim_loss_ws_elems(planes, H, W) doubles of scratch (every one written by the call).  bem_ssim_loss_tile: the edge of the
+ * square tile of valid positions (forward) / pixels (backward) one workgroup takes. */
+int bem_ssim_loss_tile(void);
+int64_t bem_ssim_loss_ws_elems(int64_t planes, int H, int W);
+int bem_ssim_loss_f32(const float* pred, const float* gt, float* loss, float* coef, double* ws, int64_t planes, int H, int W,
+                      float weight, void* stream);
+/* Backward of bem_ssim_loss_f32 (basicsr/losses/my_loss.py:37-38 under autograd; pred alone takes a gradient):
+ * dpred (planes,H,W) = gmul[0] * -(weight / Npos) * (G^T a + 2 pred G^T b + gt G^T c), G^T the full 11x11 correlation of a valid-region
+ * map back to H x W, coef = a | b | c as the forward wrote them, gmul = device scalar dL/dloss (NULL = 1). */
+int bem_ssim_loss_bwd_f32(const float* pred, const float* gt, const float* coef, float* dpred, int64_t planes, int H, int W,
+                          float weight, const float* gmul, void* stream);
+
 /* Backward of bem_iwt_hamilton_f32: dout (B,3,2h,2w) -> dq1w, dq2w (B,16,h,w) (written). */
 int bem_iwt_hamilton_bwd_f32(const float* q1w, const float* q2w, const float* dout, float* dq1w, float* dq2w, int B, int h, int w,
                              void* stream);
