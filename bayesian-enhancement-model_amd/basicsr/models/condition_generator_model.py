@@ -1,6 +1,6 @@
-"""ConditionGenerator (basicsr/models/condition_generator_model.py): Stage-I net + BNN conversion (:28-75), training settings and
-optimizer (:77-144), data feed (:146-174), the training step with the KL term (:176-218), checkpoints (:346-370); with
-``train.ema_decay > 0`` the averaged copy ``net_g_ema`` (bem.train.WeightEma), which validation runs and ``save`` writes as ``params_ema``."""
+"""ConditionGenerator (basicsr/models/condition_generator_model.py): Stage-I net + BNN conversion (:32-75), the losses of the training
+settings (:77-113), data feed (:148-174), the training step with the KL term (:176-218), validation (:272-334).  What it shares with
+ImageEnhancer -- loading, optimizer, the averaged net ``net_g_ema`` (converted like net_g), the step's tail, checkpoints -- is BaseModel's."""
 import os
 from collections import OrderedDict
 
@@ -13,26 +13,16 @@ from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
 from bem import bayes, ops
-from bem.train import BemAdamW, StepState, WeightEma
+from bem.train import StepState
 
 
 @MODEL_REGISTRY.register()
 class ConditionGenerator(BaseModel):
     def __init__(self, opt):
         super().__init__(opt)
-        self.net_g = self.model_to_device(self._build_bnn())
-        path = opt["path"].get("pretrain_network_g")
-        if path is not None:
-            self.load_network(self.net_g, path, opt["path"].get("strict_load_g", True), opt["path"].get("param_key", "params"))
-        self.mask = None
-        if self.is_train:
-            if opt.get("use_amp"):
-                raise NotImplementedError("ConditionGenerator: use_amp is not available on the f32 HIP path")
-            if opt["train"].get("mixing_augs", {}).get("mixup", False):
-                raise NotImplementedError("ConditionGenerator: mixup augmentation is host-side data preparation outside the hot path")
-            self.init_training_settings()
+        self._init_net_g()
 
-    def _build_bnn(self):
+    def _build_net(self):
         net = build_network(self.opt["network_g"])
         cfg = {"sigma_init": self.opt.get("sigma_init", 0.05), "decay": 0.998, "pretrain": False}
         (convert2bnn_selective if self.opt.get("selective", True) else convert2bnn)(net, cfg)
@@ -41,7 +31,6 @@ class ConditionGenerator(BaseModel):
     def init_training_settings(self):
         self.net_g.train()
         train_opt = self.opt["train"]
-        self.ema_decay = train_opt.get("ema_decay", 0)
         self.cri_pix = build_loss(train_opt["pixel_opt"]).to(self.device) if train_opt.get("pixel_opt") else None
         if train_opt.get("perceptual_opt"):
             raise NotImplementedError("ConditionGenerator: perceptual_opt is not available for Stage I: its predictions are 8x8 planes, below what "
@@ -54,30 +43,7 @@ class ConditionGenerator(BaseModel):
         self.cri_perceptual = None
         if self.cri_pix is None:
             raise ValueError("Both pixel and perceptual losses are None.")
-        self.optimizers, self.schedulers = [], []
-        self.setup_optimizers()
-        self.setup_schedulers()
-        self.weight_ema = None
-        if self.ema_decay > 0:
-            # :69-83: net_g_ema (converted like net_g) is only validated and saved, on every rank the same average (never wrapped)
-            print(f"Use Exponential Moving Average with decay: {self.ema_decay}", flush=True)
-            self.net_g_ema = self._build_bnn().to(self.device)
-            self.weight_ema = WeightEma(self.optimizer_g, self.get_bare_model(self.net_g), self.net_g_ema)
-            self.init_ema_weights(self.net_g_ema, self.weight_ema)
-
-    def setup_optimizers(self):
-        normal, custom = [], []
-        for k, v in self.net_g.named_parameters():
-            if v.requires_grad:
-                (custom if "impfusion" in k else normal).append(v)
-        groups = [{"params": normal, "lr_mult": 1, "name": "normal_params"},
-                  {"params": custom, "lr_mult": 1, "decay_mult": 0, "name": "custom_params"}]
-        cfg = dict(self.opt["train"]["optim_g"])
-        kind = cfg.pop("type")
-        if kind != "AdamW":
-            raise NotImplementedError(f"optimizer {kind} is not supperted yet.")
-        self.optimizer_g = BemAdamW(groups, **cfg)
-        self.optimizers.append(self.optimizer_g)
+        self.init_optimizer_and_ema()
 
     def feed_train_data(self, data):
         kind = self.opt["condition"]["type"]
@@ -126,27 +92,16 @@ class ConditionGenerator(BaseModel):
         loss_dict = OrderedDict()
         l_kl = get_kl_loss(self.net_g)
         loss_dict["l_kl"] = l_kl.detach()
-        if self.cri_pix is None:
-            raise NotImplementedError("ConditionGenerator: the pixel loss is the only image loss on the HIP path")
         l_pix = self.cri_pix(preds, self.gt)
-        w = self.opt["train"]["pixel_opt"].get("loss_weight", 1)
-        loss_dict["l_pix"] = l_pix.detach() if w == 1 else l_pix.detach() / w
+        loss_dict["l_pix"] = self.unweighted(l_pix, self.opt["train"]["pixel_opt"].get("loss_weight", 1))
         l_total = ag.ScaledSumFn.apply(l_pix, l_kl, 0.01 / self.opt["datasets"]["train"]["mini_batch_sizes"][0])
         l_total.backward()
-        self.sync_gradients(self.optimizer_g)
-        mgn = self.opt["train"].get("max_grad_norm")
-        total_norm = self.optimizer_g.clip_grad_norm_(mgn if mgn else float("inf"))
         # a parameter outside this iteration's graph has .grad None in the reference and is skipped by AdamW: the mask token without a mask
         # model_ema(decay) (:213-214) after the step has put skipped slices back: the mask token is averaged in every iteration.  decay is
         # constant, so a captured step records the launch with it by value, as one more node on the same stream
+        total_norm = self.finish_step(skip, state)
         if state is not None:
-            self.optimizer_g.step_captured(state, skip=skip)
-            if self.weight_ema is not None:
-                self.weight_ema.update(self.ema_decay)
-            return loss_dict, total_norm
-        self.optimizer_g.step(skip=skip)
-        if self.weight_ema is not None:
-            self.weight_ema.update(self.ema_decay)
+            return loss_dict, total_norm              # reduced once per replay, outside the captured body
         self.log_dict = self.reduce_loss_dict(loss_dict)
         return total_norm
 
@@ -190,45 +145,15 @@ class ConditionGenerator(BaseModel):
     def validation(self, dataloader, current_iter, tb_logger=None, save_img=False, rgb2bgr=True, use_image=True):
         """Mean PSNR of the predicted condition planes against the down-sampled ground truth, deterministic weights (mu), float form on
         the device."""
-        net = self.net_g_ema if hasattr(self, "net_g_ema") else self.net_g       # :239-247: the averaged net where there is one
-        was_training = net.training
-        net.eval()
-        set_prediction_type(net, True)
         tot, cnt = 0.0, 0
-        for data in dataloader:
-            self.feed_data(data)
-            pred = net(self.lq.contiguous())[-1]
-            h, w = pred.shape[-2:]
-            _, ps = ops.candidate_finalize(pred.contiguous(), self.gt.contiguous(), 1, h, w, False)
-            tot += float(ps.sum())
-            cnt += pred.shape[0]
-        set_prediction_type(net, False)
-        if was_training:
-            net.train()
-        self.metric_results = {"psnr": tot / max(cnt, 1)}
-        if self.opt.get("rank", 0) == 0:
-            print(f"Validation,\t\t # psnr: {self.metric_results['psnr']:.4f}", flush=True)
-        return self.metric_results["psnr"]
-
-    def save_best(self, best_metric, param_key="params"):
-        import glob
-        import os
-        if self.opt.get("rank", 0) != 0:
-            return None
-        root = self.opt["path"]["experiments_root"]
-        path = os.path.join(root, f"best_psnr_{best_metric['psnr']:.2f}_{best_metric['iter']}.pth")
-        if not os.path.exists(path):
-            for f in glob.glob(f"{root}/best_*"):
-                os.remove(f)
-            sd = {(k[7:] if k.startswith("module.") else k): v.detach().cpu() for k, v in self.get_bare_model(self.net_g).state_dict().items()}
-            os.makedirs(root, exist_ok=True)
-            torch.save(self.with_ema_state({param_key: sd}), path)
-        return path
-
-    # -- checkpoints (:346-370) ---------------------------------------------------------------------------------------------
-    def save(self, epoch, current_iter, **kwargs):
-        if hasattr(self, "net_g_ema"):
-            self.save_network([self.net_g, self.net_g_ema], "net_g", current_iter, param_key=["params", "params_ema"])
-        else:
-            self.save_network(self.net_g, "net_g", current_iter)
-        self.save_training_state(epoch, current_iter, **kwargs)
+        with self.validated_net() as net:                             # :239-247: the averaged net where there is one
+            set_prediction_type(net, True)
+            for data in dataloader:
+                self.feed_data(data)
+                pred = net(self.lq.contiguous())[-1]
+                h, w = pred.shape[-2:]
+                _, ps = ops.candidate_finalize(pred.contiguous(), self.gt.contiguous(), 1, h, w, False)
+                tot += float(ps.sum())
+                cnt += pred.shape[0]
+            set_prediction_type(net, False)
+        return self.report_validation("Validation", {"psnr": tot}, cnt)

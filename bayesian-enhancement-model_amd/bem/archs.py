@@ -726,9 +726,7 @@ class PatchMerging(nn.Module):
         if grad_mode(self):
             ps = [p for p in (self.norm.weight, self.norm.bias, self.reduction.weight) if p.requires_grad]
             return ag.LnPwFn.apply(ag.SpaceToDepthFn.apply(x), self.norm, self.reduction, *ps)
-        s = ops.space_to_depth(x)
-        Wp, _ = self.reduction.gemm_weights(x.shape[0])
-        return ops.pw_gemm(s, Wp, 2 * self.dim, ln=(self.norm.weight.detach(), self.norm.bias.detach()), ln_eps=self.norm.eps)
+        return ag.ln_pw(ops.space_to_depth(x), self.norm, self.reduction)
 
 
 class _Shuffle(nn.Module):

@@ -21,8 +21,10 @@ from . import ops
 from .native import BemNativeError
 
 
-def grad_of(p: torch.Tensor) -> torch.Tensor:
-    """The buffer the kernels accumulate this parameter's gradient into."""
+def grad_of(p):
+    """The buffer the kernels accumulate this parameter's gradient into; None for an absent parameter (a layer without a bias)."""
+    if p is None:
+        return None
     if p.grad is None:
         p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
     elif not p.grad.is_contiguous():
@@ -39,6 +41,15 @@ def _w2d(w):
     return w.detach().reshape(w.shape[0], -1)
 
 
+def _packT(layer, w):
+    """The transposed weight of a 1x1 layer as GEMM operand (its input-gradient GEMM), cached on the layer under "T"."""
+    return _pack(layer, "T", [w], lambda: _w2d(w).t())
+
+
+def _det(t):
+    return None if t is None else t.detach()
+
+
 def wb(m):
     """(weight, bias | None) tensors of a leaf: nn.Conv2d / nn.Linear parameters, or -- for a Bayesian leaf in a training forward -- the
     weights it sampled for this forward (``m.sample``, a bayes.Sample); their .grad is the buffer the reparameterisation kernel
@@ -50,6 +61,37 @@ def wb(m):
             raise RuntimeError("Bayesian leaf: no weight sample is active (training forwards run under Network.forward)")
         return m.sample.w, m.sample.b
     return m.weight, m.bias
+
+
+def out_width(m):
+    return m.out_features if hasattr(m, "out_features") else m.out_channels
+
+
+def ln_pw(x, norm, layer, asked=None, **kw):
+    """layer(LayerNorm2d(x)) for a 1x1 layer, the normalisation in the GEMM's prologue; ``kw`` goes to ops.pw_gemm (res, x2 / in_mode).
+    ``asked``: the layer's ``gemm_weights`` where the caller has asked for them already.  A Bayesian leaf draws when it is asked, and
+    its Philox streams follow the asking order in_proj, conv2d, out_proj, project_in, dwconv, project_out: a
+    caller that needs another leaf's weights before this GEMM is launched asks both itself, in that order, and no leaf twice."""
+    Wp, b = asked if asked is not None else layer.gemm_weights(x.shape[0])
+    return ops.pw_gemm(x, Wp, out_width(layer), ln=(norm.weight.detach(), norm.bias.detach()), ln_eps=norm.eps, bias=b, **kw)
+
+
+def _ln_pw_bwd(x, d, norm, layer, x2=None, dres=None):
+    """Backward of ln_pw(x [+ x2], norm, layer) for the output gradient d: the layer's weight / bias and the norm's gradients are
+    accumulated, the gradient of x (+ dres, a residual branch's) is returned."""
+    w, b = wb(layer)
+    dn = ops.pw_gemm(d, _packT(layer, w), x.shape[1])
+    dx, nrm = ops.ln_bwd(x, dn, norm.weight.detach(), norm.bias.detach(), norm.eps, grad_of(norm.weight), grad_of(norm.bias), x2=x2, dres=dres)
+    del dn
+    ops.pw_wgrad_(d, nrm, grad_of(w), dbias=grad_of(b))
+    return dx
+
+
+def _dw_bwd(layer, t, d, mode):
+    """Backward of the depthwise 3x3 + activation (mode 1: SiLU, 2: GELU gate) over t: the gradient of t; weight / bias gradients accumulated."""
+    w, b = wb(layer)
+    dpre = ops.dwact_bwd(t, w.detach(), _det(b), d, grad_of(w), grad_of(b), mode)
+    return ops.dwconv3x3(dpre, ops.derived(layer).get("flip", [w], lambda: w.detach().flip(2, 3).contiguous()), None, mode=0)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -263,9 +305,9 @@ class PwFn(Function):
         Wp, _ = holder.gemm_weights(x1.shape[0])
         if x2 is not None:
             x2 = x2.contiguous()
-            out = ops.pw_gemm(x1, Wp, M, x2=x2, in_mode=2, bias=None if bias is None else bias.detach())
+            out = ops.pw_gemm(x1, Wp, M, x2=x2, in_mode=2, bias=_det(bias))
         else:
-            out = ops.pw_gemm(x1, Wp, M, bias=None if bias is None else bias.detach())
+            out = ops.pw_gemm(x1, Wp, M, bias=_det(bias))
         ctx.save_for_backward(x1, x2)
         ctx.holder, ctx.weight, ctx.bias = holder, weight, bias
         return out
@@ -276,7 +318,7 @@ class PwFn(Function):
         dout = dout.contiguous()
         w, b, h = ctx.weight, ctx.bias, ctx.holder
         C1 = x1.shape[1]
-        ops.pw_wgrad_(dout, x1, grad_of(w), x2=x2, dbias=None if b is None else grad_of(b))
+        ops.pw_wgrad_(dout, x1, grad_of(w), x2=x2, dbias=grad_of(b))
         w2 = _w2d(w)
         dx1 = dx2 = None
         if ctx.needs_input_grad[0]:
@@ -341,7 +383,7 @@ class Conv2dFn(Function):
         x = x.contiguous()
         ctx.save_for_backward(x)
         ctx.holder, ctx.weight, ctx.bias, ctx.cin_slice = holder, weight, bias, cin_slice
-        return ops.conv2d(x, holder.conv_weight(), None if bias is None else bias.detach(), stride=holder.stride[0], pad=holder.padding[0],
+        return ops.conv2d(x, holder.conv_weight(), _det(bias), stride=holder.stride[0], pad=holder.padding[0],
                           cin_slice=cin_slice)
 
     @staticmethod
@@ -350,7 +392,7 @@ class Conv2dFn(Function):
         w, b, h = ctx.weight, ctx.bias, ctx.holder
         dout = dout.contiguous()
         s, p = h.stride[0], h.padding[0]
-        ops.conv_wgrad_(dout, x, grad_of(w), None if b is None else grad_of(b), stride=s, pad=p, cin_slice=ctx.cin_slice)
+        ops.conv_wgrad_(dout, x, grad_of(w), grad_of(b), stride=s, pad=p, cin_slice=ctx.cin_slice)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.cin_slice is not None:
@@ -387,30 +429,14 @@ class VSSBlockFn(Function):
         op, mlp = blk.op, blk.mlp
         B, C, H, W = x.shape
         Ci, R, L = op.d_inner, op.dt_rank, H * W
-        n1, n2, on = blk.norm, blk.norm2, op.out_norm
-        pi, dwc, po = mlp.project_in, mlp.dwconv, mlp.project_out
-        (piw, pib), (dww, dwb), (pow_, pob) = wb(pi), wb(dwc), wb(po)
-        Hd = pow_.shape[1]
         # ---- gdMlp: out = x2 + W_o g + b_o, g = GELU(h1) h2, h = dw(t2) + b, t2 = W_i LN2(x2) + b_i
-        ops.pw_wgrad_(dout, g, grad_of(pow_), dbias=None if pob is None else grad_of(pob))
-        dg = ops.pw_gemm(dout, _pack(po, "T", [pow_], lambda: _w2d(pow_).t()), Hd)
-        dh = ops.dwact_bwd(t2, dww.detach(), None if dwb is None else dwb.detach(), dg, grad_of(dww), None if dwb is None else grad_of(dwb), 2)
-        del dg
-        dt2 = ops.dwconv3x3(dh, ops.derived(dwc).get("flip", [dww], lambda: dww.detach().flip(2, 3).contiguous()), None, mode=0)
-        del dh
-        dn2 = ops.pw_gemm(dt2, _pack(pi, "T", [piw], lambda: _w2d(piw).t()), C)
-        dx2, nrm = ops.ln_bwd(x2, dn2, n2.weight.detach(), n2.bias.detach(), n2.eps, grad_of(n2.weight), grad_of(n2.bias), dres=dout)
-        del dn2
-        ops.pw_wgrad_(dt2, nrm, grad_of(piw), dbias=None if pib is None else grad_of(pib))
-        del dt2, nrm
-        # ---- SS2D: x2 = x + W_out LN_on(y0 + y1)
-        opw = op.out_proj
-        oww, owb = wb(opw)
-        dysn = ops.pw_gemm(dx2, _pack(opw, "T", [oww], lambda: _w2d(oww).t()), Ci)
-        dys, nys = ops.ln_bwd(y0, dysn, on.weight.detach(), on.bias.detach(), on.eps, grad_of(on.weight), grad_of(on.bias), x2=y1)
-        del dysn
-        ops.pw_wgrad_(dx2, nys, grad_of(oww), dbias=None if owb is None else grad_of(owb))
-        del nys
+        pow_, pob = wb(mlp.project_out)
+        ops.pw_wgrad_(dout, g, grad_of(pow_), dbias=grad_of(pob))
+        dt2 = _dw_bwd(mlp.dwconv, t2, ops.pw_gemm(dout, _packT(mlp.project_out, pow_), pow_.shape[1]), 2)
+        dx2 = _ln_pw_bwd(x2, dt2, blk.norm2, mlp.project_in, dres=dout)
+        del dt2
+        # ---- SS2D: x2 = x + W_out LN_on(y0 + y1), (y0, y1) = scan(xc, x_proj xc), xc = SiLU(dw(t)), t = W_in LN(x)
+        dys = _ln_pw_bwd(y0, dx2, op.out_norm, op.out_proj, x2=y1)
         wall, dtw, dtb, A, Ds, _ = op._scan_params()
         M = R + 2 * op.d_state                           # x_dbl rows per direction
         dysT = ops.transpose_planes(dys)
@@ -430,18 +456,10 @@ class VSSBlockFn(Function):
         dxc = ops.pw_gemm(dxd, wallT, Ci, res=dx0.view(B, Ci, H, W))
         dxc = ops.add(dxc, ops.transpose_planes(dx1T.view(B, Ci, W, H)))
         del dx0, dx1T, dxd, dxd0, dxd1
-        cv = op.conv2d
-        cvw, cvb = wb(cv)
-        dpre = ops.dwact_bwd(t, cvw.detach(), None if cvb is None else cvb.detach(), dxc, grad_of(cvw), None if cvb is None else grad_of(cvb), 1)
-        dt = ops.dwconv3x3(dpre, ops.derived(cv).get("flip", [cvw], lambda: cvw.detach().flip(2, 3).contiguous()), None, mode=0)
-        del dpre, dxc
-        ipw = op.in_proj
-        iww, iwb = wb(ipw)
-        dn = ops.pw_gemm(dt, _pack(ipw, "T", [iww], lambda: _w2d(iww).t()), C)
-        need_dx = ctx.needs_input_grad[0]
-        dx, nrm = ops.ln_bwd(x, dn, n1.weight.detach(), n1.bias.detach(), n1.eps, grad_of(n1.weight), grad_of(n1.bias), dres=dx2)
-        ops.pw_wgrad_(dt, nrm, grad_of(iww), dbias=None if iwb is None else grad_of(iwb))
-        return (dx if need_dx else None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
+        dt = _dw_bwd(op.conv2d, t, dxc, 1)
+        del dxc
+        dx = _ln_pw_bwd(x, dt, blk.norm, op.in_proj, dres=dx2)
+        return (dx if ctx.needs_input_grad[0] else None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
 def vssblock_params(blk):
@@ -471,20 +489,14 @@ class LnPwFn(Function):
     @staticmethod
     def forward(ctx, x, norm, layer, *params):
         x = x.contiguous()
-        Wp, b = layer.gemm_weights(x.shape[0])
         ctx.save_for_backward(x)
         ctx.norm, ctx.layer = norm, layer
-        return ops.pw_gemm(x, Wp, layer.weight.shape[0], ln=(norm.weight.detach(), norm.bias.detach()), ln_eps=norm.eps, bias=b)
+        return ln_pw(x, norm, layer)
 
     @staticmethod
     def backward(ctx, dout):
         (x,) = ctx.saved_tensors
-        n, m = ctx.norm, ctx.layer
-        dout = dout.contiguous()
-        w, b = wb(m)
-        dn = ops.pw_gemm(dout, _pack(m, "T", [w], lambda: _w2d(w).t()), x.shape[1])
-        dx, nrm = ops.ln_bwd(x, dn, n.weight.detach(), n.bias.detach(), n.eps, grad_of(n.weight), grad_of(n.bias))
-        ops.pw_wgrad_(dout, nrm, grad_of(w), dbias=None if b is None else grad_of(b))
+        dx = _ln_pw_bwd(x, dout.contiguous(), ctx.norm, ctx.layer)
         return (dx if ctx.needs_input_grad[0] else None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 

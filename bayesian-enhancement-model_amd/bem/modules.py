@@ -194,10 +194,6 @@ def fold_up_fuse(up: "ConvT2x2", fuse: PwConv2d, pre: Optional[PwConv2d] = None,
 # ------------------------------------------------------------------------------------------------
 # SS2D / gdMlp / VSSBlock  (basicsr/vmamba/models/vmamba.py:116-133, 438-716, 1241-1334)
 # ------------------------------------------------------------------------------------------------
-def _out_features(m):
-    return m.out_features if hasattr(m, "out_features") else m.out_channels
-
-
 class gdMlp(nn.Module):
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0, channels_first=False):
         super().__init__()
@@ -238,13 +234,11 @@ class gdMlp(nn.Module):
         """The branch as three kernels; returns (out, t2, g): the output and the two intermediates VSSBlockFn.backward needs,
         t2 = project_in(LN(x)) and g = GELU(h1) * h2."""
         B = x.shape[0]
-        Wp, b = self.project_in.gemm_weights(B)
-        t2 = ops.pw_gemm(x, Wp, _out_features(self.project_in), ln=(norm.weight.detach(), norm.bias.detach()),
-                         ln_eps=norm.eps, bias=b)
+        t2 = ag.ln_pw(x, norm, self.project_in)
         w, b = self.dwconv.dw_weights(B)
         g = ops.dwconv3x3(t2, w, b, mode=2)
         Wp, b = self.project_out.gemm_weights(B)
-        return ops.pw_gemm(g, Wp, _out_features(self.project_out), bias=b, res=x), t2, g
+        return ops.pw_gemm(g, Wp, ag.out_width(self.project_out), bias=b, res=x), t2, g
 
 
 SS2D_MAX_D_STATE = 16       # bem_ss2d_scan_n_f32 / bem_ss2d_scan_n_bwd_f32
@@ -314,18 +308,17 @@ class SS2D(nn.Module):
         Ci, R, N, L = self.d_inner, self.dt_rank, self.d_state, H * W
         M = R + 2 * N                                    # x_dbl rows per direction: [dt_0..dt_{R-1} | B_0..B_{N-1} | C_0..C_{N-1}]
         wall, dtw, dtb, A, Ds, xrows = self._scan_params()
-        lnw, lnb = norm.weight.detach(), norm.bias.detach()
         on = self.out_norm
+        # Bayesian leaves draw when they are asked, and their Philox streams follow the asking order in_proj, conv2d, out_proj (DESIGN.md
+        # section 4.2): both are asked here, ahead of every launch of this forward, and in_proj's answer is handed on to ag.ln_pw
+        ip = self.in_proj.gemm_weights(B)
+        w, bw = self.conv2d.dw_weights(B)
         # small planes (Stage I's 16x16 .. 4x4 maps): depthwise conv + SiLU, x_proj and the four scans in one kernel with a sample's planes
         # in LDS (bem_ss2d_core_small_f32) -- no xc, x_dbl or transposed plane in memory, one y instead of y0 / y1.  The fused tail
         # (defer_tail) and the training forward (keep) need y0 / y1 and keep the chain.
         if ops.USE_SS2D_CORE and not keep and not defer_tail and ops.ss2d_core_small_supported(Ci, H, W, R, N):
-            Wp, b = self.in_proj.gemm_weights(B)
-            w, bw = self.conv2d.dw_weights(B)
-            t = ops.pw_gemm(x, Wp, Ci, ln=(lnw, lnb), ln_eps=norm.eps, bias=b)
-            y = ops.ss2d_core_small(t, w, bw, xrows, dtw, dtb, A, Ds)
-            Wp, b = self.out_proj.gemm_weights(B)
-            return ops.pw_gemm(y, Wp, _out_features(self.out_proj), ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
+            y = ops.ss2d_core_small(ag.ln_pw(x, norm, self.in_proj, asked=ip), w, bw, xrows, dtw, dtb, A, Ds)
+            return ag.ln_pw(y, on, self.out_proj, res=x)
         # row-major scan (d_state = 1): no transposed copy of xc, y1 comes back row-major (the column orientation goes through LDS)
         rm = N == 1 and ops.ss2d_scan_rm_supported(H, W, R)
         # LayerNorm + in_proj + depthwise 3x3 + SiLU + x_proj in one kernel (bem_ss2d_front_x6_f32).  The in_proj output t stays in
@@ -333,13 +326,11 @@ class SS2D(nn.Module):
         # alone when it was added, no reason for leaving the transposed-plane scan out is recorded; d_state > 1 has no such condition.
         front = not keep and (rm or N > 1) and ops.ss2d_front_supported(C, 4 * M) and Ci == C \
             and type(self.in_proj) is Linear2d and type(self.conv2d) is DwConv2d
-        Wp, b = self.in_proj.gemm_weights(B)
-        w, bw = self.conv2d.dw_weights(B)
         t = None
         if front:
-            xc, xd = ops.ss2d_front(x, lnw, lnb, norm.eps, Wp, b, w, bw, wall, 4 * M)
+            xc, xd = ops.ss2d_front(x, norm.weight.detach(), norm.bias.detach(), norm.eps, *ip, w, bw, wall, 4 * M)
         else:
-            t = ops.pw_gemm(x, Wp, Ci, ln=(lnw, lnb), ln_eps=norm.eps, bias=b)
+            t = ag.ln_pw(x, norm, self.in_proj, asked=ip)
             xc = ops.dwconv3x3(t, w, bw, mode=1)
             xd = ops.pw_gemm(xc, wall, 4 * M)            # (B, 4M, H, W), rows [dir 0 | dir 2 | dir 1 | dir 3]
         # x_dbl of the column-major directions = the row-major GEMM's rows in transposed pixel order: 2M planes to transpose
@@ -359,9 +350,7 @@ class SS2D(nn.Module):
             op = self.out_proj
             Wpp = ops.derived(self).get("vss_back", [op.weight], lambda: ops.pack_vss_back_outproj(op.weight.detach()))
             return y0, y1, on.weight.detach(), on.bias.detach(), on.eps, Wpp, (op.bias.detach() if op.bias is not None else None)
-        Wp, b = self.out_proj.gemm_weights(B)
-        out = ops.pw_gemm(y0, Wp, _out_features(self.out_proj), x2=y1, in_mode=1,
-                          ln=(on.weight.detach(), on.bias.detach()), ln_eps=on.eps, bias=b, res=x)
+        out = ag.ln_pw(y0, on, self.out_proj, x2=y1, in_mode=1, res=x)
         return (out, (t, xc, xd, xd1, y0, y1)) if keep else out
 
     def forward(self, x):
