@@ -22,6 +22,8 @@ from typing import Callable, List, Optional
 import torch
 import torch.distributed as dist
 
+from .scorers import first_index
+
 
 def shard_images(n_images: int, rank: int, world: int):
     """Image-major block partition: keeps all N candidates of an image on one rank (selection is local,
@@ -65,36 +67,23 @@ def gather_ragged(final: torch.Tensor, score: torch.Tensor, counts, world: int):
 
 def first_best(score_rows: List[List[float]], rule: str = "max") -> List[int]:
     """Python ``list.index(max(...))`` / ``index(min(...))`` per image (eval.py:268-285): FIRST occurrence on ties."""
-    pick = max if rule == "max" else min
-    return [row.index(pick(row)) for row in score_rows]
+    return [first_index(row, rule=rule) for row in score_rows]
 
 
 def select_best(score: torch.Tensor, samples_per_image: int):
     """eval.py:284-285 with psnr_weight = 1: index of the first maximum of psnr / max(psnr) per image."""
-    best = []
-    for row in score.view(-1, samples_per_image).cpu().tolist():
-        m = max(row)
-        if m == 0:               # no usable score (e.g. all-zero PSNR without targets): the reference's first candidate
-            best.append(0)
-            continue
-        rel = [v / m for v in row]
-        best.append(rel.index(max(rel)))
-    return best
+    return [first_index(row) for row in score.view(-1, samples_per_image).cpu().tolist()]
 
 
 def _select_device(final, score, N):
-    """Selection without leaving the device: the HIP kernel on GPU tensors, a torch restatement of the same first-maximum rule on
-    CPU tensors (gloo tests).  Returns (best (B) int64, best images (B,3,h,w))."""
+    """Selection without leaving the device: the HIP kernel on GPU tensors; on CPU tensors (gloo tests, a handful of images) the host's
+    statement of the same rule, row by row.  Returns (best (B) int64, best images (B,3,h,w))."""
     B = final.shape[0] // N
     if final.is_cuda:
         from . import ops
         best, _, img = ops.select_best(final.contiguous(), score.contiguous(), N)
         return best.long(), img
-    s = score.view(B, N)
-    m = s.max(dim=1, keepdim=True).values
-    rel = torch.where(m != 0, s / torch.where(m != 0, m, torch.ones_like(m)), torch.zeros_like(s))
-    top = rel.max(dim=1, keepdim=True).values
-    best = (rel == top).float().argmax(dim=1)                      # first index of the maximum
+    best = torch.tensor(select_best(score, N), dtype=torch.int64)
     img = final.view(B, N, *final.shape[1:])[torch.arange(B), best]
     return best, img
 

@@ -1390,11 +1390,20 @@ def se_gate_bwd(mean, w1, w2, y, dy, dw1, dw2):
     return dmean
 
 
-def _spi(op, Bn, samples_per_image):
-    """Bn candidates in groups of samples_per_image -> the number of images."""
+def _images(op, Bn, samples_per_image, what="images", limit=_GRID_MAX):
+    """Bn candidates in groups of samples_per_image -> the number of images.  A call takes at most ``limit`` of ``what``: 'images' or
+    'candidates', whichever the op's launch grids spread over y or z."""
     if samples_per_image < 1 or Bn % samples_per_image:
         raise ValueError(f"{op}: {Bn} candidates are not a multiple of samples_per_image = {samples_per_image}")
-    return Bn // samples_per_image
+    B = Bn // samples_per_image
+    n = B if what == "images" else Bn
+    if n > limit:
+        raise ValueError(f"{op}: at most {limit} {what} per call, got {n}")
+    return B
+
+
+# bem_select_scores_f32's rule numbers (csrc/selection.hip states the rules)
+SELECT_RULES = {"weighted": 0, "max": 1, "min": 2, "relative": 3}
 
 
 def cond_postproc(pred, target_mean, noise, samples_per_image, noise_level):
@@ -1416,11 +1425,9 @@ def candidate_finalize(pred, target, samples_per_image, h, w, gt_mean):
     """pred (Bn,3,Hp,Wp), target (n_img,3,h,w)|None -> (final (Bn,3,h,w), psnr (Bn)).  3 Bn <= 65535 (one grid row per candidate channel)."""
     _chk(pred, "pred"); _chk(target, "target", optional=True)
     Bn, C, Hp, Wp = pred.shape
-    _spi("candidate_finalize", Bn, samples_per_image)
+    _images("candidate_finalize", Bn, samples_per_image, "candidates", _GRID_MAX // 3)
     if C != 3 or not (0 < h <= Hp and 0 < w <= Wp):
         raise ValueError("candidate_finalize: shapes")
-    if 3 * Bn > _GRID_MAX:
-        raise ValueError(f"candidate_finalize: at most {_GRID_MAX // 3} candidates per call, got {Bn}")
     if gt_mean and target is None:
         raise ValueError("candidate_finalize: gt_mean needs a target")
     if target is not None and tuple(target.shape) != (Bn // samples_per_image, 3, h, w):
@@ -1434,19 +1441,8 @@ def candidate_finalize(pred, target, samples_per_image, h, w, gt_mean):
 
 
 def select_best(final, psnr, samples_per_image):
-    """eval.py:284-285 on the device: (best (B) int32, best_psnr (B), best_images (B,3,h,w)); row = image*N + sample.  B <= 65535."""
-    _chk(final, "final"); _chk(psnr, "psnr")
-    Bn = final.shape[0]
-    N = samples_per_image
-    B = _spi("select_best", Bn, N)
-    if psnr.numel() != Bn:
-        raise ValueError("select_best: shapes")
-    if B > _GRID_MAX:
-        raise ValueError(f"select_best: at most {_GRID_MAX} images per call, got {B}")
-    best = torch.empty(B, device=final.device, dtype=torch.int32)
-    bp = torch.empty(B, device=final.device, dtype=torch.float32)
-    img = torch.empty((B,) + tuple(final.shape[1:]), device=final.device, dtype=final.dtype)
-    check(lib().bem_select_best_f32(_p(final), _p(psnr), _p(best), _p(bp), _p(img), B, N, final[0].numel(), _stream()), "select_best")
+    """eval.py:284-285 on the device, select_scores' rule 'relative': (best (B) int32, best_psnr (B), best_images (B,3,h,w))."""
+    best, bp, _, img = select_scores(final, psnr, samples_per_image, rule="relative")
     return best, bp, img
 
 
@@ -1454,9 +1450,7 @@ def ssim(final, target, samples_per_image):
     """Enhancement/utils.py calculate_ssim per candidate: final (Bn,3,h,w) in [0,1], target (Bn/N,3,h,w) -> (Bn) f32.  Bn <= 65535."""
     _chk(final, "final"); _chk(target, "target")
     Bn, C, h, w = final.shape
-    _spi("ssim", Bn, samples_per_image)
-    if Bn > _GRID_MAX:
-        raise ValueError(f"ssim: at most {_GRID_MAX} candidates per call, got {Bn}")
+    _images("ssim", Bn, samples_per_image, "candidates")
     if C != 3 or tuple(target.shape) != (Bn // samples_per_image, 3, h, w) or h <= 10 or w <= 10:
         raise ValueError("ssim: shapes (3-channel images larger than the 11x11 window)")
     out = torch.empty(Bn, device=final.device, dtype=torch.float32)
@@ -1466,24 +1460,24 @@ def ssim(final, target, samples_per_image):
 
 
 def select_scores(final, s1, samples_per_image, s2=None, weight=1.0, rule="weighted"):
-    """Per-image selection on the device (eval.py:268-297): rule 'weighted' (weight s1/max + (1-weight) s2/max), 'max', 'min';
-    first index on ties.  Returns (best (B) int32, best s1 (B), best s2 (B)|None, best images (B,3,h,w)|None).  B <= 65535."""
+    """Per-image selection on the device (eval.py:268-297): rule 'weighted' (weight s1/max + (1-weight) s2/max), 'max', 'min', or
+    'relative' (s1/max of one score, started like Python's max(): the default PSNR rule); first index on ties; row = image*N + sample.
+    Returns (best (B) int32, best s1 (B), best s2 (B)|None, best images (B,3,h,w)|None).  B <= 65535."""
     _chk(s1, "s1"); _chk(s2, "s2", optional=True); _chk(final, "final", optional=True)
     N = samples_per_image
     Bn = s1.numel()
-    if rule not in ("weighted", "max", "min"):
+    if rule not in SELECT_RULES:
         raise ValueError(f"select_scores: unknown rule {rule!r}")
-    if _spi("select_scores", Bn, N) > _GRID_MAX:
-        raise ValueError(f"select_scores: at most {_GRID_MAX} images per call, got {Bn // N}")
+    B = _images("select_scores", Bn, N)
     if (s2 is not None and s2.numel() != Bn) or (final is not None and final.shape[0] != Bn):
         raise ValueError("select_scores: shapes")
-    r = {"weighted": 0, "max": 1, "min": 2}[rule]
-    B = Bn // N
+    if s2 is not None and rule == "relative":
+        raise ValueError("select_scores: the 'relative' rule takes one score")
     best = torch.empty(B, device=s1.device, dtype=torch.int32)
     b1 = torch.empty(B, device=s1.device, dtype=torch.float32)
     b2 = torch.empty(B, device=s1.device, dtype=torch.float32) if s2 is not None else None
     img = torch.empty((B,) + tuple(final.shape[1:]), device=s1.device, dtype=final.dtype) if final is not None else None
-    check(lib().bem_select_scores_f32(_p(final), _p(s1), _p(s2), float(weight), r, _p(best), _p(b1), _p(b2), _p(img), B, N,
+    check(lib().bem_select_scores_f32(_p(final), _p(s1), _p(s2), float(weight), SELECT_RULES[rule], _p(best), _p(b1), _p(b2), _p(img), B, N,
                                       (final[0].numel() if final is not None else 0), _stream()), "select_scores")
     return best, b1, b2, img
 
@@ -1493,11 +1487,9 @@ def mc_mean(raw, target, samples_per_image, h, w, gt_mean):
     _chk(raw, "raw"); _chk(target, "target", optional=True)
     Bn, C, Hp, Wp = raw.shape
     N = samples_per_image
-    if _spi("mc_mean", Bn, N) > _GRID_MAX:
-        raise ValueError(f"mc_mean: at most {_GRID_MAX} images per call, got {Bn // N}")
+    B = _images("mc_mean", Bn, N)
     if C != 3 or not (0 < h <= Hp and 0 < w <= Wp) or (gt_mean and (target is None or tuple(target.shape) != (Bn // N, 3, h, w))):
         raise ValueError("mc_mean: shapes")
-    B = Bn // N
     out = torch.empty(B, 3, h, w, device=raw.device, dtype=raw.dtype)
     ws = torch.empty(2 * B, device=raw.device, dtype=torch.float64) if gt_mean else None
     check(lib().bem_mc_mean_f32(_p(raw), _p(target if gt_mean else None), _p(out), _p(ws), B, N, Hp, Wp, h, w, int(bool(gt_mean)), _stream()), "mc_mean")
@@ -1510,8 +1502,7 @@ class McState:
     deviations of the finished candidates; ``spread=True``).  ``n`` counts the samples per image accumulated so far."""
 
     def __init__(self, B, h, w, device, mean=False, spread=False):
-        if B > _GRID_MAX:
-            raise ValueError(f"McState: at most {_GRID_MAX} images per call, got {B}")
+        _images("McState", B, 1)
         if B < 0 or h < 1 or w < 1:
             raise ValueError("McState: shapes")
         self.B, self.h, self.w, self.n = B, h, w, 0
@@ -1580,8 +1571,7 @@ class BestState:
     def __init__(self, B, image_shape, device, rule):
         if rule not in ("max", "min"):
             raise ValueError(f"select_merge: rule {rule!r} cannot be decided chunk by chunk ('max' or 'min')")
-        if B > _GRID_MAX:
-            raise ValueError(f"select_merge: at most {_GRID_MAX} images per call, got {B}")
+        _images("select_merge", B, 1)
         self.B, self.rule, self.n = B, rule, 0
         self.best = torch.zeros(B, device=device, dtype=torch.int32)
         self.score = torch.zeros(B, device=device, dtype=torch.float32)
@@ -1604,7 +1594,7 @@ def select_merge(state, final, scores, samples_per_image):
         raise ValueError(f"select_merge: {scores.numel()} scores are not {Nc} samples of {B} images")
     if (final is None) != (state.images is None) or (final is not None and tuple(final.shape) != (B * Nc,) + tuple(state.images.shape[1:])):
         raise ValueError("select_merge: shapes")
-    check(lib().bem_select_merge_f32(_p(final), _p(scores), {"max": 1, "min": 2}[state.rule], _p(state.best), _p(state.score), _p(state.images),
+    check(lib().bem_select_merge_f32(_p(final), _p(scores), SELECT_RULES[state.rule], _p(state.best), _p(state.score), _p(state.images),
                                      _p(state.pick), B, Nc, state.n, (state.images[0].numel() if final is not None and B else 0), _stream()),
           "select_merge")
     state.n += Nc

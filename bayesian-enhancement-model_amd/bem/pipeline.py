@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from .modules import SampleCtx, sampling
+from .scorers import first_index
 
 
 class BEMPipeline:
@@ -113,11 +114,7 @@ class BEMPipeline:
     @staticmethod
     def select(psnr_rows: List[float]) -> int:
         """eval.py:284-285 with psnr_weight = 1: index of the first maximum of psnr / max(psnr)."""
-        m = max(psnr_rows)
-        if m == 0:                 # no usable score (no targets): the first candidate, like the reference's empty-score fallback
-            return 0
-        rel = [p / m for p in psnr_rows]
-        return rel.index(max(rel))
+        return first_index(psnr_rows)
 
     @torch.no_grad()
     def enhance(self, imgs, targets, num_samples, gt_mean=True, deterministic=False, sync=True, scorer=None, monte_carlo=False, shard=None,
@@ -151,8 +148,20 @@ class BEMPipeline:
             raise ValueError("enhance: shard together with sample_chunk" + (" / keep='best'" if keep == "best" else "") + " is not supported")
         K = N if sample_chunk is None else min(int(sample_chunk), N)
         streamed = K < N or keep == "best"
-        B, _, h, w = imgs.shape
         tg = None if targets is None else targets.contiguous()
+        r, stats, run = self._collect(imgs, targets, N, K, streamed, gt_mean, deterministic, scorer, monte_carlo, uncertainty, keep, shard, kw)
+        best, img, bp = self._choose(r, run, scorer, targets, N)
+        r.update(best=best, best_images=img, best_psnr=bp)
+        self._statistics(r, stats, streamed, tg, N, imgs.shape[-2:], gt_mean, monte_carlo, uncertainty)
+        if sync:
+            r["best"], r["best_psnr"] = best.cpu().tolist(), bp.cpu().tolist()
+        return r
+
+    def _collect(self, imgs, targets, N, K, streamed, gt_mean, deterministic, scorer, monte_carlo, uncertainty, keep, shard, kw):
+        """Step 1 of ``enhance``: the candidates of all N samples, as streamed chunks of K, as this rank's block of a sample-sharded run, or
+        as the single batch.  Returns (r, stats, run): the candidates dict with ``N``; the McState that the Monte-Carlo mean (streamed
+        only) and the spread accumulate in, or None; the BestState of ``keep='best'`` with every chunk merged, or None."""
+        B, _, h, w = imgs.shape
         stats = ops.McState(B, h, w, imgs.device, mean=monte_carlo and streamed, spread=uncertainty) if (uncertainty or (monte_carlo and streamed)) else None
         run = ops.BestState(B, (3, h, w), imgs.device, _online_rule(scorer)) if keep == "best" else None
         if streamed:
@@ -182,48 +191,56 @@ class BEMPipeline:
             from . import dist as bdist
             rank, world = shard
             kw.pop("rank", None)
-            lo, hi = bdist.shard_samples(num_samples, rank, world)
-            B = imgs.shape[0]
-            r = self.candidates(imgs, targets, max(hi - lo, 1), gt_mean, False, rank=rank, sample_offset=lo, total_samples=num_samples, **kw)
+            lo, hi = bdist.shard_samples(N, rank, world)
+            r = self.candidates(imgs, targets, max(hi - lo, 1), gt_mean, False, rank=rank, sample_offset=lo, total_samples=N, **kw)
             for k_ in ("final", "psnr", "conds") + (("raw",) if monte_carlo else ()):
                 t = r[k_] if hi > lo else r[k_][:0]
-                r[k_] = bdist.gather_samples(t.contiguous(), B, num_samples, rank, world)
+                r[k_] = bdist.gather_samples(t.contiguous(), B, N, rank, world)
             if not monte_carlo:
                 r.pop("raw")
-            r["N"] = num_samples
+            r["N"] = N
         else:
-            r = self.candidates(imgs, targets, num_samples, gt_mean, deterministic, **kw)
-        N = r["N"]
-        if run is not None:
-            best, img, bp = run.best, run.images, run.score
-            if scorer is not None:
-                bp = ops.select_scores(None, r["psnr"], N, rule="max")[1] if targets is None else _gather(r["psnr"], best, N)
-                r["scores2"] = None
+            r = self.candidates(imgs, targets, N, gt_mean, deterministic, **kw)
+        return r, stats, run
+
+    @staticmethod
+    def _choose(r, run, scorer, targets, N):
+        """Step 2 of ``enhance``: (best (B) int32, best images, best PSNR (B)) by the running merge, the scorer or the default PSNR rule;
+        a scorer's score vectors go into ``r`` as ``scores`` / ``scores2``."""
+        if run is not None:                            # chosen chunk by chunk already; its one score vector was assembled with the chunks
+            best, img = run.best, run.images
+            if scorer is None:
+                return best, img, run.score            # the default rule's running score is the PSNR
+            r["scores2"] = None
         elif scorer is not None:
             sel = scorer.select(r["final"], targets, N, psnr=r["psnr"])
             best, img = sel["best"], sel["best_images"]
-            bp = ops.select_scores(None, r["psnr"], N, rule="max")[1] if targets is None else _gather(r["psnr"], best, N)
             r.update(scores=sel["s1"], scores2=sel["s2"])
         else:
             best, bp, img = ops.select_best(r["final"], r["psnr"], N)
             if targets is None:
                 best = torch.zeros_like(best)          # no reference: the reference keeps the first sample (eval.py:291-293)
                 img = r["final"][::N].contiguous()
-        r.update(best=best, best_images=img, best_psnr=bp)
+            return best, img, bp
+        # a scorer chose: the PSNR of its choice, or without targets (every PSNR is 0) what the 'max' rule makes of them
+        bp = ops.select_scores(None, r["psnr"], N, rule="max")[1] if targets is None else _gather(r["psnr"], best, N)
+        return best, img, bp
+
+    @staticmethod
+    def _statistics(r, stats, streamed, tg, N, hw, gt_mean, monte_carlo, uncertainty):
+        """Step 3 of ``enhance``: the Monte-Carlo mean with its PSNR / SSIM and the spread of the candidates, into ``r``.  A streamed run
+        has both in ``stats`` already; the single batch takes the mean in one pass (ops.mc_mean) and accumulates the spread here."""
+        h, w = hw
         if monte_carlo:
-            gm = bool(gt_mean and targets is not None)
-            mc = ops.mc_finish(stats, tg, gm, mean=True)[0] if streamed else ops.mc_mean(r["raw"], tg, N, h, w, gm)
-            r["mc"] = mc
-            if targets is not None:
+            gm = bool(gt_mean and tg is not None)
+            r["mc"] = mc = ops.mc_finish(stats, tg, gm, mean=True)[0] if streamed else ops.mc_mean(r["raw"], tg, N, h, w, gm)
+            if tg is not None:
                 _, r["mc_psnr"] = ops.candidate_finalize(mc, tg, 1, h, w, False)
                 r["mc_ssim"] = ops.ssim(mc, tg, 1) if min(h, w) > 10 else None
         if uncertainty:
             if not streamed:
                 ops.mc_accum(stats, None, r["final"], N)
             _, r["std"], r["std_mean"] = ops.mc_finish(stats, mean=False, spread=True)
-        if sync:
-            r["best"], r["best_psnr"] = best.cpu().tolist(), bp.cpu().tolist()
-        return r
 
 
 def _online_rule(scorer):

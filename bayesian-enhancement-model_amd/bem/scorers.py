@@ -15,7 +15,8 @@ A scorer maps the finished candidates of a batch -- ``final`` (B*N,3,h,w) in [0,
                                pristine-model statistics of a NiqeParams (niqe_pris_params.npz from a BasicSR install).
   UiqmUciqe(uiqm_weight)       UIQM and UCIQE (basicsr/metrics/uciqe_uiqm.py, eval.py:255-260), rule ``index(max(w * uiqm / max(uiqm)
                                + (1 - w) * uciqe / max(uciqe)))`` (eval.py:277-278); ops.uiqm_uciqe on the device.
-All scores stay on the device; ``select`` runs bem_select_scores_f32 (first index on ties, float64 comparisons)."""
+All scores stay on the device; ``select`` runs bem_select_scores_f32 (first index on ties, float64 comparisons).  The selection rules
+are stated twice, once per side: ``first_index`` below for the host and the comment above ``first_better`` in csrc/selection.hip."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -23,6 +24,22 @@ from typing import Callable, Optional
 import torch
 
 from . import ops
+
+
+def first_index(s1_row, s2_row=None, weight=1.0, rule="relative"):
+    """The reference's choice among one image's samples with its Python list semantics (eval.py:268-285): the FIRST index of the best
+    score.  'max' / 'min': of s1.  'relative' / 'weighted': of s1 / max(s1), or weight * s1 / max(s1) + (1 - weight) * s2 / max(s2) with
+    s2.  max() keeps a leading NaN and passes any other over, so a leading NaN wins; the device's 'weighted' rule alone passes that one
+    over too.  A zero maximum (no usable score: PSNR without targets) gives the first sample, where the division would give NaN or -inf
+    for every one."""
+    rel = [float(v) for v in s1_row]
+    if rule not in ("max", "min"):
+        s2 = None if s2_row is None else [float(v) for v in s2_row]
+        m1, m2 = max(rel), (1.0 if s2 is None else max(s2))
+        if m1 == 0 or m2 == 0:
+            return 0
+        rel = [p / m1 for p in rel] if s2 is None else [weight * p / m1 + (1 - weight) * q / m2 for p, q in zip(rel, s2)]
+    return rel.index(min(rel)) if rule == "min" else rel.index(max(rel))
 
 
 class Scorer:

@@ -110,24 +110,6 @@ __global__ void cand_psnr_kernel(const double* __restrict__ ws, float* __restric
     psnr[bn] = has_target ? (m == 0 ? 100.f : (float)(10.0 * log10(1.0 / m))) : 0.f;
 }
 
-// eval.py:284-285 with psnr_weight = 1: scores = psnr / max(psnr) per image, best = first index of the maximum score
-// (python list.index(max(...)) semantics, evaluated in f64 like the reference's python floats).  One thread per image.
-__global__ void select_best_kernel(const float* __restrict__ psnr, int* __restrict__ best, float* __restrict__ best_psnr, int B, int N) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* p = psnr + (int64_t)b * N;
-    double m = (double)p[0];
-    for (int i = 1; i < N; ++i) m = fmax(m, (double)p[i]);
-    int bi = 0;
-    double bs = (double)p[0] / m;
-    for (int i = 1; i < N; ++i) {
-        const double sc = (double)p[i] / m;
-        if (sc > bs) { bs = sc; bi = i; }
-    }
-    best[b] = bi;
-    best_psnr[b] = p[bi];
-}
-
 __global__ void gather_best_kernel(const float* __restrict__ cand, const int* __restrict__ best, float* __restrict__ out, int N, int64_t chw4) {
     const int b = blockIdx.y, k = best[b];
     if (k < 0) return;                                                     // the streaming merge: this image keeps what it has
@@ -201,32 +183,60 @@ __global__ void ssim_final_kernel(const double* __restrict__ acc, float* __restr
     if (i < Bn) out[i] = (float)(acc[i] * inv);
 }
 
-// Generalised selection of eval.py:268-297.  rule 0: first maximum of w s1 / max(s1) + (1 - w) s2 / max(s2) (full reference,
-// :284-285; s2 = NULL means w = 1); rule 1: first maximum of s1 (no-reference CLIP-IQA, :271); rule 2: first minimum of s1 (NIQE,
-// :273-274).  f64 like the reference's python floats; one thread per image.
-__global__ void select_scores_kernel(const float* __restrict__ s1, const float* __restrict__ s2, double w, int rule, int* __restrict__ best,
-                                     float* __restrict__ best_s1, float* __restrict__ best_s2, int B, int N) {
+// ---------------------------------------------------------------- per-image selection (eval.py:268-297) ----------
+// best = the FIRST index of the best score among an image's N samples, as python's list.index(max(...)) / index(min(...)) gives it,
+// compared in f64 like the reference's python floats.  One loop (first_better) serves every rule; a rule is its score and its start:
+//   0 weighted : w s1 / max(s1) + (1 - w) s2 / max(s2) (eval.py:284-285 PSNR / SSIM, :277-278 UIQM / UCIQE), s1 / max(s1) without s2.
+//                Starts from -1e300 at index 0.
+//   1 max      : s1 (CLIP-IQA, :271)          2 min : s1, smaller is better (NIQE, :273-274).
+//                Start from element 0, or -- n_done > 0, the streamed merge -- from the running best_score with "no sample of this chunk".
+//   3 relative : s1 / max(s1) (:284-285 with psnr_weight = 1, the default PSNR rule).  Starts from element 0.
+// The maxima are taken by fmax, which passes NaN over.  This block is the project's statement of the edge cases (the host's is
+// bem.scorers.first_index):
+//   NaN       : a comparison with NaN is false, so no rule ever moves TO a NaN score.  Rules 1, 2 and 3 start from element 0 and keep a
+//               leading NaN (index 0, python's max() / min() likewise); in a merge a NaN running score is kept by every later chunk.
+//               Rule 0 starts below every score and passes NaN over: index 0 only when all scores are NaN (python would keep a leading
+//               one).  In rule 3 a NaN anywhere but first leaves the maximum to the others; all NaN gives index 0.
+//   max == 0  : rules 0 and 3 divide by it: 0 / 0 is NaN and a negative score over 0 is -inf, neither is ever strictly better, so a
+//               zero maximum gives index 0 (all-zero scores: PSNR without a target).
+//   max < 0   : dividing by a negative maximum turns the order of s1 round in rules 0 and 3 (rule 3: the first MINIMUM wins), as in the reference.
+//   ties      : the comparison is strict, the first index wins; a chunked merge changes its choice only for a strictly better score.
+enum { RULE_WEIGHTED = 0, RULE_MAX = 1, RULE_MIN = 2, RULE_RELATIVE = 3 };
+
+template <class Score>
+__device__ __forceinline__ void first_better(Score score, bool smaller, int i0, int i1, double& bs, int& bi) {
+    for (int i = i0; i < i1; ++i) {
+        const double sc = score(i);
+        if (smaller ? sc < bs : sc > bs) { bs = sc; bi = i; }
+    }
+}
+
+// One thread per image over its N samples of this call.  best[b] = n_done + index, best_s1 / best_s2 [b] = the chosen sample's scores;
+// all three stay as they are where a merge (n_done > 0) finds nothing better.  pick[b] (or NULL) = the row of this call to copy, -1 for none.
+__global__ void select_kernel(const float* __restrict__ s1, const float* __restrict__ s2, double w, int rule, int* __restrict__ best,
+                              float* __restrict__ best_s1, float* __restrict__ best_s2, int* __restrict__ pick, int B, int N, int n_done) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const float* p = s1 + (int64_t)b * N;
     const float* q = s2 ? s2 + (int64_t)b * N : nullptr;
     int bi = 0;
-    if (rule == 0) {
+    double bs;
+    if (rule == RULE_MAX || rule == RULE_MIN) {
+        const auto raw = [&](int i) { return (double)p[i]; };
+        if (n_done == 0) bs = raw(0);
+        else { bs = (double)best_s1[b]; bi = -1; }
+        first_better(raw, rule == RULE_MIN, n_done == 0 ? 1 : 0, N, bs, bi);
+    } else {
         double m1 = (double)p[0], m2 = q ? (double)q[0] : 1.0;
         for (int i = 1; i < N; ++i) { m1 = fmax(m1, (double)p[i]); if (q) m2 = fmax(m2, (double)q[i]); }
-        double bs = -1e300;
-        for (int i = 0; i < N; ++i) {
-            const double sc = q ? w * (double)p[i] / m1 + (1.0 - w) * (double)q[i] / m2 : (double)p[i] / m1;
-            if (sc > bs) { bs = sc; bi = i; }
-        }
-    } else {
-        double bs = (double)p[0];
-        for (int i = 1; i < N; ++i) {
-            const double sc = (double)p[i];
-            if (rule == 1 ? sc > bs : sc < bs) { bs = sc; bi = i; }
-        }
+        const auto rel = [&](int i) { return q ? w * (double)p[i] / m1 + (1.0 - w) * (double)q[i] / m2 : (double)p[i] / m1; };
+        const bool lead = rule == RULE_RELATIVE;
+        bs = lead ? rel(0) : -1e300;
+        first_better(rel, false, lead ? 1 : 0, N, bs, bi);
     }
-    best[b] = bi;
+    if (pick) pick[b] = bi;
+    if (bi < 0) return;
+    best[b] = n_done + bi;
     if (best_s1) best_s1[b] = p[bi];
     if (best_s2 && q) best_s2[b] = q[bi];
 }
@@ -366,24 +376,6 @@ __global__ __launch_bounds__(256) void mc_std_mean_kernel(const double* __restri
     if (threadIdx.x == 0) std_mean[b] = s / (double)chw;
 }
 
-// The loop of select_scores_kernel's rules 1 / 2, continued over a chunk: pick[b] = the chunk's row to copy, -1 to keep the running image.
-__global__ void select_merge_kernel(const float* __restrict__ scores, int rule, int* __restrict__ best, float* __restrict__ best_score,
-                                    int* __restrict__ pick, int B, int Nc, int n_done) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* p = scores + (int64_t)b * Nc;
-    int bi = -1, i = 0;
-    double bs;
-    if (n_done == 0) { bs = (double)p[0]; bi = 0; i = 1; }
-    else bs = (double)best_score[b];
-    for (; i < Nc; ++i) {
-        const double sc = (double)p[i];
-        if (rule == 1 ? sc > bs : sc < bs) { bs = sc; bi = i; }
-    }
-    pick[b] = bi;
-    if (bi >= 0) { best[b] = n_done + bi; best_score[b] = p[bi]; }
-}
-
 // best_img[b] = cand[b][best[b]]: 16-byte copies when the planes allow it
 void launch_gather_best(const float* cand, const int* best, float* best_img, int B, int N, int64_t chw, hipStream_t s) {
     const bool v4 = chw % 4 == 0 && (((uintptr_t)cand | (uintptr_t)best_img) & 15) == 0;
@@ -391,6 +383,23 @@ void launch_gather_best(const float* cand, const int* best, float* best_img, int
     dim3 grid((unsigned)std::min<int64_t>(cdiv64(n, 256), 1024), B);
     if (v4) gather_best_kernel<<<grid, 256, 0, s>>>(cand, best, best_img, N, n);
     else gather_best_scalar_kernel<<<grid, 256, 0, s>>>(cand, best, best_img, N, n);
+}
+
+// The checks, the selection launch and the gather of both selection entries.  running: the call continues a BestState (rules 1 / 2 only,
+// best_s1 is the running score and is read when n_done > 0).
+int launch_select(const char* op, bool running, const float* cand, const float* s1, const float* s2, float weight, int rule, int* best,
+                  float* best_s1, float* best_s2, float* best_img, int* pick, int B, int N, int n_done, int64_t chw, void* stream) {
+    BEM_REQUIRE(s1 && best && (!running || (best_s1 && pick)), "%s: null tensor", op);
+    BEM_REQUIRE(B >= 0 && B <= 65535 && N >= 1 && n_done >= 0 && chw >= 0, "%s: bad arguments B=%d Nc=%d n_done=%d", op, B, N, n_done);
+    BEM_REQUIRE(rule >= RULE_WEIGHTED && rule <= RULE_RELATIVE && (rule != RULE_RELATIVE || !s2), "%s: unknown rule %d%s", op, rule,
+                rule == RULE_RELATIVE ? " with a second score" : "");
+    BEM_REQUIRE(!running || rule == RULE_MAX || rule == RULE_MIN, "%s: rule %d cannot be decided chunk by chunk (1 = max, 2 = min)", op, rule);
+    BEM_REQUIRE((cand == nullptr) == (best_img == nullptr), "%s: cand and best_img go together", op);
+    if (B == 0) return BEM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    select_kernel<<<cdiv(B, 64), 64, 0, s>>>(s1, s2, (double)weight, rule, best, best_s1, best_s2, pick, B, N, n_done);
+    if (cand && chw > 0) launch_gather_best(cand, pick ? pick : best, best_img, B, N, chw, s);
+    return bem_check_launch(op);
 }
 
 }  // namespace
@@ -429,18 +438,6 @@ extern "C" int bem_candidate_finalize_f32(const float* pred, const float* target
     return bem_check_launch("candidate_finalize");
 }
 
-extern "C" int bem_select_best_f32(const float* cand, const float* psnr, int* best, float* best_psnr, float* best_img, int B, int N,
-                                   int64_t chw, void* stream) {
-    BEM_REQUIRE(psnr && best && best_psnr, "select_best: null tensor");
-    BEM_REQUIRE(B >= 0 && B <= 65535 && N >= 1 && chw >= 0, "select_best: bad shape B=%d N=%d", B, N);
-    BEM_REQUIRE((cand == nullptr) == (best_img == nullptr), "select_best: cand and best_img go together");
-    if (B == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    select_best_kernel<<<cdiv(B, 64), 64, 0, s>>>(psnr, best, best_psnr, B, N);
-    if (cand && chw > 0) launch_gather_best(cand, best, best_img, B, N, chw, s);
-    return bem_check_launch("select_best");
-}
-
 extern "C" int bem_ssim_f32(const float* pred, const float* target, float* ssim, double* ws, int Bn, int samples_per_image, int h, int w, void* stream) {
     BEM_REQUIRE(pred && target && ssim && ws, "ssim: null tensor");
     BEM_REQUIRE(Bn >= 0 && Bn <= 65535 && samples_per_image >= 1 && Bn % samples_per_image == 0 && h > 10 && w > 10, "ssim: bad shape (images larger than the 11x11 window)");
@@ -455,14 +452,7 @@ extern "C" int bem_ssim_f32(const float* pred, const float* target, float* ssim,
 
 extern "C" int bem_select_scores_f32(const float* cand, const float* s1, const float* s2, float weight, int rule, int* best, float* best_s1,
                                      float* best_s2, float* best_img, int B, int N, int64_t chw, void* stream) {
-    BEM_REQUIRE(s1 && best, "select_scores: null tensor");
-    BEM_REQUIRE(B >= 0 && B <= 65535 && N >= 1 && chw >= 0 && rule >= 0 && rule <= 2, "select_scores: bad arguments");
-    BEM_REQUIRE((cand == nullptr) == (best_img == nullptr), "select_scores: cand and best_img go together");
-    if (B == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    select_scores_kernel<<<cdiv(B, 64), 64, 0, s>>>(s1, s2, (double)weight, rule, best, best_s1, best_s2, B, N);
-    if (cand && chw > 0) launch_gather_best(cand, best, best_img, B, N, chw, s);
-    return bem_check_launch("select_scores");
+    return launch_select("select_scores", false, cand, s1, s2, weight, rule, best, best_s1, best_s2, best_img, nullptr, B, N, 0, chw, stream);
 }
 
 extern "C" int bem_mc_mean_f32(const float* pred, const float* target, float* out, double* ws, int B, int N, int Hp, int Wp, int h, int w,
@@ -523,13 +513,5 @@ extern "C" int bem_mc_finish_f32(const float* sum, const float* m2, const float*
 
 extern "C" int bem_select_merge_f32(const float* cand, const float* scores, int rule, int* best, float* best_score, float* best_img, int* pick,
                                     int B, int Nc, int n_done, int64_t chw, void* stream) {
-    BEM_REQUIRE(scores && best && best_score && pick, "select_merge: null tensor");
-    BEM_REQUIRE(B >= 0 && B <= 65535 && Nc >= 1 && n_done >= 0 && chw >= 0, "select_merge: bad arguments B=%d Nc=%d n_done=%d", B, Nc, n_done);
-    BEM_REQUIRE(rule == 1 || rule == 2, "select_merge: rule %d cannot be decided chunk by chunk (1 = max, 2 = min)", rule);
-    BEM_REQUIRE((cand == nullptr) == (best_img == nullptr), "select_merge: cand and best_img go together");
-    if (B == 0) return BEM_OK;
-    hipStream_t s = (hipStream_t)stream;
-    select_merge_kernel<<<cdiv(B, 64), 64, 0, s>>>(scores, rule, best, best_score, pick, B, Nc, n_done);
-    if (cand && chw > 0) launch_gather_best(cand, pick, best_img, B, Nc, chw, s);
-    return bem_check_launch("select_merge");
+    return launch_select("select_merge", true, cand, scores, nullptr, 1.f, rule, best, best_score, nullptr, best_img, pick, B, Nc, n_done, chw, stream);
 }

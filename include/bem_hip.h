@@ -359,21 +359,18 @@ int bem_candidate_finalize_f32(const float* pred, const float* target, float* fi
                                int Bn, int samples_per_image, int Hp, int Wp, int h, int w, int gt_mean,
                                void* stream);   /* ws: scratch of 7*Bn doubles (zeroed by the call) */
 
-/* Candidate selection of eval.py:284-285 (psnr_weight = 1): per image, score_i = psnr_i / max_j psnr_j, best = FIRST index
- * of the maximum score (python list.index(max(...))); best (B) int32, best_psnr (B), and -- when cand/best_img are given --
- * best_img[b] = cand[b*N + best[b]] (chw floats each).  Everything stays on the device: no host round trip per step. */
-int bem_select_best_f32(const float* cand, const float* psnr, int* best, float* best_psnr, float* best_img, int B, int N,
-                        int64_t chw, void* stream);
-
 /* calculate_ssim(img_as_ubyte(target), img_as_ubyte(pred)) of Enhancement/utils.py:12-57 per candidate: uint8 values rint(255 x), f64,
  * 11x11 Gaussian (sigma 1.5) over the valid region, mean over region and channels.  pred (Bn,3,h,w), target (Bn/spi,3,h,w), h, w > 10;
  * ssim (Bn) f32 out; ws: scratch of Bn doubles (zeroed by the call). */
 int bem_ssim_f32(const float* pred, const float* target, float* ssim, double* ws, int Bn, int samples_per_image, int h, int w, void* stream);
 
-/* Selection rules of eval.py:268-297 on the device, FIRST index on ties (python list.index):
- *   rule 0: max of weight * s1 / max(s1) + (1 - weight) * s2 / max(s2)  (full reference, PSNR / SSIM; s2 NULL = weight 1)
+/* Selection rules of eval.py:268-297 on the device, FIRST index on ties (python list.index), f64 comparisons:
+ *   rule 0: max of weight * s1 / max(s1) + (1 - weight) * s2 / max(s2)  (PSNR / SSIM, UIQM / UCIQE; s2 NULL = weight 1); passes NaN over
  *   rule 1: max of s1 (no-reference, CLIP-IQA)      rule 2: min of s1 (NIQE)
- * best (B) int32; best_s1 / best_s2 (B) or NULL; best_img[b] = cand[b*N + best[b]] when cand / best_img are given. */
+ *   rule 3: max of s1 / max(s1), s2 NULL (eval.py:284-285 with psnr_weight = 1, the eval step's default); keeps a leading NaN like python
+ * NaN, zero and negative maxima: the comment above first_better in csrc/selection.hip.
+ * best (B) int32; best_s1 / best_s2 (B) or NULL; best_img[b] = cand[b*N + best[b]] (chw floats each) when cand / best_img are given.
+ * Everything stays on the device: no host round trip per step. */
 int bem_select_scores_f32(const float* cand, const float* s1, const float* s2, float weight, int rule, int* best, float* best_s1,
                           float* best_s2, float* best_img, int B, int N, int64_t chw, void* stream);
 
@@ -436,7 +433,8 @@ int bem_mc_finish_f32(const float* sum, const float* m2, const float* target, fl
 /* bem_select_scores_f32's rules 1 (max) and 2 (min) over chunks of an image's samples handed over in sample order: best (B) int32,
  * best_score (B) and best_img (B, chw) are the running choice over the n_done samples seen so far (not read when n_done = 0).  They
  * change only where the chunk (scores (B*Nc), cand (B*Nc, chw)) holds a strictly better score, compared in f64 -- the first index wins
- * ties, as in one bem_select_scores_f32 call over all the samples.  cand / best_img may both be NULL; pick: B int32 of scratch. */
+ * ties, as in one bem_select_scores_f32 call over all the samples: it is that call's kernel and loop, started from the running score.
+ * cand / best_img may both be NULL; pick: B int32 of scratch. */
 int bem_select_merge_f32(const float* cand, const float* scores, int rule, int* best, float* best_score, float* best_img, int* pick, int B,
                          int Nc, int n_done, int64_t chw, void* stream);
 

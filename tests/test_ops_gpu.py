@@ -517,7 +517,7 @@ def test_image_prep_kernels(ops):
 
 
 def test_select_best_first_max(ops):
-    """bem_select_best vs BEMPipeline.select (eval.py:284-285): ties -> first index, negative PSNRs divide by a negative max."""
+    """ops.select_best (bem_select_scores_f32, rule 3) vs BEMPipeline.select (eval.py:284-285): ties -> first index, negative PSNRs divide by a negative max."""
     from bem.pipeline import BEMPipeline
     rows = [[20.0, 25.5, 25.5, 3.0], [7.0, 7.0, 7.0, 7.0], [-3.0, -1.0, -2.0, -1.0], [100.0, 99.0, 100.0, 1.0], [1.5, 2.5, 3.5, 4.5]]
     ps = dev(torch.tensor(rows).reshape(-1))

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import selection_cases as C
 import selection_ref as R
 from conftest import load_golden
 from oracle import bem_oracle as O
@@ -209,3 +210,71 @@ def test_finalize_inputs_reach_both_clamps_and_distinct_targets(name):
         assert float((crop < 0).double().mean()) > 0.05 and float((crop > 1).double().mean()) > 0.05
     if B == 2:
         assert float((target[0] - target[1]).abs().min()) > 0.15
+
+
+@pytest.mark.parametrize("N", [1, 64])
+def test_edge_tables_have_a_clear_winner_or_a_written_tie(N):
+    """The tables of test_selection_at_the_workgroup_edge: for every rule the float64 winner of every row leads the runner-up by
+    C.EDGE_GAP relative, or the best score stands twice, bit-equal, in a row marked 'tie'."""
+    s1, s2, ties = C.edge_tables(N)
+    assert s1.shape == s2.shape == (C.EDGE_B, N) and s1.dtype == s2.dtype == torch.float32
+    assert sorted(ties) == ([] if N == 1 else [0, C.EDGE_B - 1])
+    for rule, two, wgt in C.EDGE_RULES if N > 1 else []:
+        for b in range(C.EDGE_B):
+            sc = C.edge_scores(rule, s1[b], s2[b] if two else None, wgt)
+            gp = R.gap(sc)
+            if gp == 0:
+                assert ties.get(b) == "tie", (rule, two, b)
+            else:
+                assert b not in ties and gp >= C.EDGE_GAP * float(sc.abs().max()), (rule, two, b, gp)
+        want = [C.edge_reference(rule, s1[b], s2[b] if two else None, wgt) for b in ties]
+        assert want == ([7, 7] if rule == "min" else [3, 3])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the host's statement
+def test_first_index_is_the_reference_on_every_table_and_rule():
+    from bem.scorers import first_index
+    for name in R.SELECT_CASES:
+        ps, ss, _ = R.select_rows(name)
+        for b in range(ps.shape[0]):
+            assert first_index(ps[b]) == R.select_best(ps[b]), (name, b)
+            for rule, wgt in R.SELECT_RULES:
+                two = ss[b] if rule == "weighted" else None
+                assert first_index(ps[b], two, wgt, rule) == R.select_scores(ps[b], two, wgt, rule), (name, b, rule, wgt)
+    s2 = [0.5, 0.6, 0.7, 0.8]
+    for row in C.NAN_ROWS + [[0.0, 0.0]]:
+        assert first_index(row) == first_index(row, rule="relative") == R.select_best(row), row
+        for rule in ("weighted", "max", "min"):
+            assert first_index(row, rule=rule) == R.select_scores(row, rule=rule), (row, rule)
+        assert first_index(row, s2[:len(row)], 0.5, "weighted") == R.select_scores(row, s2[:len(row)], 0.5), row
+    assert [first_index(r) for r in C.NAN_ROWS] == [0, 2, 0, 0, 1] and first_index([0.0, 0.0]) == 0 and first_index([-3.0, -1.0, -2.0]) == 0
+
+
+def test_host_selection_functions_are_first_index():
+    from bem import dist
+    from bem.pipeline import BEMPipeline
+    from bem.scorers import first_index
+    rows = C.MERGE_ROWS + [[0.0, 0.0, 0.0, 0.0], [-3.0, -1.0, -2.0, -1.0]]
+    want = [first_index(r) for r in rows]
+    assert [BEMPipeline.select(r) for r in rows] == want
+    assert dist.select_best(torch.tensor(rows).reshape(-1), 4) == want
+    for rule in ("max", "min"):
+        assert dist.first_best(rows, rule) == [first_index(r, rule=rule) for r in rows]
+
+
+def test_select_scores_entry_knows_four_rules():
+    """The C entry's checks run before any HIP call (B = 0 returns after them): rules 0..3 pass, rule 3 with a second score and rule 4 do not;
+    bem_select_best_f32 is gone from the library."""
+    import os
+    from bem import native, ops
+    if not os.path.exists(native.LIB_PATH):
+        native.build()
+    lib, p = ops.lib(), 16                      # any non-null value: no pointer is touched
+    call = lambda rule, s2=None, B=0: lib.bem_select_scores_f32(None, p, s2, 1.0, rule, p, p, None, None, B, 4, 0, None)
+    assert [call(r) for r in sorted(ops.SELECT_RULES.values())] == [0, 0, 0, 0] and sorted(ops.SELECT_RULES.values()) == [0, 1, 2, 3]
+    assert call(0, s2=p) == 0
+    for bad, word in ((dict(rule=4), "select_scores: unknown rule 4"), (dict(rule=3, s2=p), "rule 3 with a second score"),
+                      (dict(rule=1, B=65536), "select_scores: bad arguments B=65536")):
+        with pytest.raises(native.BemNativeError, match=word):
+            native.check(call(**bad), "select_scores")
+    assert not hasattr(lib, "bem_select_best_f32")

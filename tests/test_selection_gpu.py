@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import selection_cases as C
 import selection_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -290,6 +291,78 @@ def test_selection_with_nan_scores():
     assert ops.select_scores(None, ps, 4)[0].cpu().tolist() == [2, 2, 0, 0, 1]                      # row 0: Python's rule gives 0
     ss = dev(torch.tensor([[0.5, 0.6, 0.7, 0.8]] * len(rows)).reshape(-1))
     assert ops.select_scores(None, ps, 4, ss, 0.5)[0].cpu().tolist() == [2, 2, 2, 0, 3]
+
+
+def relative(ops, fin, ps, N):
+    """The default PSNR rule under its select_scores spelling, in select_scores' result order."""
+    return ops.select_scores(fin, ps, N, rule="relative")
+
+
+def same_bits(got, want, what):
+    """Equal as bit patterns: NaN where NaN is, and the same one."""
+    assert torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32)), what
+
+
+@pytest.mark.parametrize("rule", ["max", "min"])
+def test_chunked_merge_is_the_one_shot_selection(rule):
+    """select_merge over every split of N = 4 into ordered chunks leaves what one select_scores call over the four samples gives: index,
+    score (NaN included) and image; on the NaN rows of test_selection_with_nan_scores, an all-equal and a strictly decreasing row."""
+    from bem import ops
+    rows, N = C.MERGE_ROWS, 4
+    B = len(rows)
+    ps = dev(torch.tensor(rows))
+    fin = dev(torch.rand(B, N, 3, 2, 2, generator=R.gen(703)))
+    want = [R.select_scores(r, rule=rule) for r in rows]
+    best, b1, _, img = ops.select_scores(fin.flatten(0, 1), ps.reshape(-1), N, rule=rule)
+    assert best.cpu().tolist() == want
+    splits = list(C.compositions(N))
+    assert len(splits) == 8 and (4,) in splits and (1, 1, 1, 1) in splits
+    for split in splits:
+        st, lo = ops.BestState(B, (3, 2, 2), "cuda", rule), 0
+        for k in split:
+            ops.select_merge(st, fin[:, lo:lo + k].contiguous().flatten(0, 1), ps[:, lo:lo + k].contiguous().reshape(-1), k)
+            lo += k
+        assert st.n == N and st.best.cpu().tolist() == want, (rule, split, st.best.cpu().tolist())
+        same_bits(st.score, b1, f"select_merge {rule} {split} score")
+        bit_equal(st.images, img.cpu(), f"select_merge {rule} {split} image")
+
+
+@pytest.mark.parametrize("N", [1, 64])
+def test_selection_at_the_workgroup_edge(N):
+    """65 images: the second workgroup holds one thread with work.  Every rule against the float64 reference row by row;
+    test_edge_tables_have_a_clear_winner_or_a_written_tie holds the tables to a clear winner or a written tie."""
+    from bem import ops
+    s1, s2, _ = C.edge_tables(N)
+    B = C.EDGE_B
+    fin = torch.rand(B * N, 1, 1, 1, generator=R.gen(704))
+    fin_d, s1_d, s2_d = dev(fin), dev(s1.reshape(-1)), dev(s2.reshape(-1))
+    rows = torch.arange(B) * N
+    for rule, two, wgt in C.EDGE_RULES:
+        want = torch.tensor([C.edge_reference(rule, s1[b], s2[b] if two else None, wgt) for b in range(B)])
+        if rule == "relative":
+            best, b1, b2, img = relative(ops, fin_d, s1_d, N)
+        else:
+            best, b1, b2, img = ops.select_scores(fin_d, s1_d, N, s2_d if two else None, wgt, rule)
+        assert best.cpu().tolist() == want.tolist(), (N, rule, two)
+        bit_equal(b1, s1.reshape(-1)[rows + want], f"edge {rule} s1")
+        bit_equal(img, fin[rows + want], f"edge {rule} image")
+        assert (b2 is None) == (not two)
+        if two:
+            bit_equal(b2, s2.reshape(-1)[rows + want], f"edge {rule} s2")
+
+
+def test_relative_rule_is_select_best():
+    """select_scores(rule='relative') and select_best return the same tensors: the tables of test_selection_rules and a negative maximum."""
+    from bem import ops
+    tables = [R.select_rows(name)[0] for name in R.SELECT_CASES] + [torch.tensor([[-3.0, -1.0, -2.0]])]
+    for ps in tables:
+        B, N = ps.shape
+        fin_d, ps_d = dev(torch.rand(B * N, 3, 3, 5, generator=R.gen(705))), dev(ps.reshape(-1))
+        best, b1, b2, img = relative(ops, fin_d, ps_d, N)
+        best0, bp0, img0 = ops.select_best(fin_d, ps_d, N)
+        assert b2 is None and torch.equal(best, best0) and torch.equal(img, img0)
+        same_bits(b1, bp0, "relative score")
+    assert best.cpu().tolist() == [0]                                     # [-3, -1, -2] / -1: the order turns round
 
 
 @pytest.mark.parametrize("side,aligned", [(296, True), (296, False), (592, True)])
