@@ -249,13 +249,22 @@ def _ss2d_torch(x0, x1, xd0, xd1, dtw, dtb, A, Ds, blocked=False):
     return ys
 
 
-@pytest.mark.parametrize("B,C,L,R", [(2, 8, 192, 3), (1, 5, 77, 2), (1, 4, 1030, 1), (1, 3, 4100, 3), (1, 2, 9000, 2),
-                                     (3, 7, 64, 5), (2, 6, 16, 10), (2, 3, 4, 10), (1, 4, 256, 3), (1, 4, 300, 3),       # Stage-I planes: one wavefront per row
+_SCAN_BWD = [(2, 8, 192, 3), (1, 5, 77, 2), (1, 4, 1030, 1), (1, 3, 4100, 3), (1, 2, 9000, 2),
+             (3, 7, 64, 5), (2, 6, 16, 10), (2, 3, 4, 10), (1, 4, 256, 3), (1, 4, 300, 3),       # Stage-I planes: one wavefront per row
+             # whole-row channel-blocked forms (full and partial channel groups)
+             (2, 5, 1024, 2), (1, 6, 1024, 1), (1, 5, 4096, 3), (1, 9, 1024, 5), (1, 3, 256, 10), (1, 5, 16384, 3)]
+# the two whole-row forms without a case above: (L = 4096, R = 5) and (L = 1024, R = 10)
+_SCAN_BWD_ROWS = [(1, 5, 4096, 5), (1, 3, 1024, 10)]
+# x_dbl as the training path hands it over (bem/autograd.py: xd.view(B,4,M,L)[:, :2], twice the contiguous batch stride), B = 2: the
+# workgroup-per-channel kernel (L = 16), the wavefront-per-row one (64), the 256- and 1024-thread tiled ones (300, 4100), a whole-row form
+_SCAN_BWD_STRIDED = [(2, 6, 16, 10), (2, 7, 64, 5), (2, 4, 300, 3), (2, 3, 4100, 3), (2, 5, 1024, 2)]
 
-                                     # whole-row channel-blocked forms (full and partial channel groups)
-                                     (2, 5, 1024, 2), (1, 6, 1024, 1), (1, 5, 4096, 3), (1, 9, 1024, 5), (1, 3, 256, 10), (1, 5, 16384, 3)])
-def test_ss2d_scan_bwd(dev, B, C, L, R):
+
+@pytest.mark.parametrize("B,C,L,R,strided", [c + (False,) for c in _SCAN_BWD + _SCAN_BWD_ROWS] + [c + (True,) for c in _SCAN_BWD_STRIDED],
+                         ids=["-".join(map(str, c)) for c in _SCAN_BWD + _SCAN_BWD_ROWS] + ["-".join(map(str, c)) + "-strided" for c in _SCAN_BWD_STRIDED])
+def test_ss2d_scan_bwd(dev, B, C, L, R, strided):
     from bem import ops
+    added = strided or (B, C, L, R) in _SCAN_BWD_ROWS       # the later cases take the blocked reference throughout: seconds, not minutes
     g = G(8)
     x0 = torch.randn(B, C, L, generator=g, requires_grad=True)
     x1 = torch.randn(B, C, L, generator=g, requires_grad=True)
@@ -268,14 +277,21 @@ def test_ss2d_scan_bwd(dev, B, C, L, R):
     A = -torch.exp(Alog).view(-1)
     # L >= 8192: the per-step loop of the oracle takes minutes under autograd; the blocked closed form of the same recurrence stands in for it
     # (L = 300 runs both and compares them)
-    y0, y1 = _ss2d_torch(x0, x1, xd0, xd1, dtw, dtb, A, Ds, blocked=L >= 8192)
-    if L == 300:
+    y0, y1 = _ss2d_torch(x0, x1, xd0, xd1, dtw, dtb, A, Ds, blocked=L >= 8192 or added)
+    if L == 300 and not added:
         with torch.no_grad():
             z0, z1 = _ss2d_torch(x0, x1, xd0, xd1, dtw, dtb, A, Ds, blocked=True)
         close(z0, y0, 1e-5, 1e-6, "blocked reference vs loop"); close(z1, y1, 1e-5, 1e-6, "blocked reference vs loop")
     dy0, dy1 = torch.randn(B, C, L, generator=g), torch.randn(B, C, L, generator=g)
     (y0 * dy0).sum().add((y1 * dy1).sum()).backward()
     d = lambda t: t.detach().to(dev).contiguous()
+    if strided:
+        wide = [torch.full((B, 4, R + 2, L), 3.5, device=dev) for _ in range(2)]
+        for w_, t in zip(wide, (xd0, xd1)):
+            w_[:, :2].copy_(t.detach())
+        xdv = {id(xd0): wide[0][:, :2], id(xd1): wide[1][:, :2]}
+        assert xdv[id(xd0)].stride(0) == 2 * xd0.stride(0) and not xdv[id(xd0)].is_contiguous()
+        dc, d = d, lambda t: xdv[id(t)] if id(t) in xdv else dc(t)
     f0, f1 = ops.ss2d_scan(d(x0), d(x1), d(xd0), d(xd1), d(dtw), d(dtb), d(A), d(Ds))
     close(f0, y0, 2e-4, 1e-5, "fwd y0"); close(f1, y1, 2e-4, 1e-5, "fwd y1")
     dAl, dDs = torch.zeros(4 * C, device=dev), torch.zeros(4 * C, device=dev)
