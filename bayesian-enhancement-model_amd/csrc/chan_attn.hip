@@ -6,43 +6,80 @@ namespace {
 
 // ---------------------------------------------------------------- channel attention ----------
 // stats[b] = { S[32][32] = F1 F2^T, s1[32] = F1 1, s2[32] = F2 1 } accumulated in f64.
+//
+// S goes through v_mfma_f64_16x16x4_f64 (products of f32 values are exact in f64, the sums stay f64): four 16x16 tiles per image, the
+// pixels as k.  Lane (c = lane & 15, g = lane >> 4) supplies A[c][k = g] and B[k = g][c]; it loads four consecutive pixels
+// pb + 4g .. pb + 4g + 3 of channels c and c + 16 of both maps as float4, and MFMA step s takes component s of all of them, so A and B
+// agree on which pixel is k = g of step s.  No LDS in the product loop; the next 16 pixels are loaded ahead of the current 16 MFMAs.
+// The channel sums are f64 adds on the same registers (8 adds beside 16 MFMAs of 64 cycles each).
+// The four waves of a workgroup take consecutive 16-pixel groups (256 contiguous bytes of every channel row per step) of a `chunk` of
+// pixels, join in LDS and add one partial of every statistic to the zeroed `stats`.
 constexpr int ATT_C = 32;
-constexpr int ATT_CHUNK = 2048;
-__global__ __launch_bounds__(256) void attn_stats_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
-                                                         double* __restrict__ stats, int L) {
-    __shared__ double t1[ATT_C][65], t2[ATT_C][65];     // converted once when the tile is staged: the product loop is then f64 FMAs only (it was
-                                                        // 4 v_cvt_f64_f32 per 4 FMAs: the conversions, not the arithmetic, set the kernel's time)
-    const int b = blockIdx.y;
-    const int p0 = blockIdx.x * ATT_CHUNK;
-    const int i0 = (threadIdx.x >> 4) * 2, j0 = (threadIdx.x & 15) * 2;
-    double a00 = 0, a01 = 0, a10 = 0, a11 = 0, r0 = 0, r1 = 0, c0 = 0, c1 = 0;
-    const float* F1 = f1 + (int64_t)b * ATT_C * L;
-    const float* F2 = f2 + (int64_t)b * ATT_C * L;
-    const int pend = min(p0 + ATT_CHUNK, L);
-    for (int ps = p0; ps < pend; ps += 64) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < ATT_C * 64; i += 256) {
-            const int c = i >> 6, pp = i & 63;
-            const int p = ps + pp;
-            t1[c][pp] = p < pend ? (double)F1[(int64_t)c * L + p] : 0.0;
-            t2[c][pp] = p < pend ? (double)F2[(int64_t)c * L + p] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int pp = 0; pp < 64; ++pp) {
-            const double u0 = t1[i0][pp], u1 = t1[i0 + 1][pp], v0 = t2[j0][pp], v1 = t2[j0 + 1][pp];
-            a00 = fma(u0, v0, a00); a01 = fma(u0, v1, a01); a10 = fma(u1, v0, a10); a11 = fma(u1, v1, a11);
-            if (j0 == 0) { r0 += u0; r1 += u1; }
-            if (i0 == 0) { c0 += v0; c1 += v1; }
-        }
+constexpr int ATT_STATS = ATT_C * ATT_C + 2 * ATT_C;
+constexpr int ATT_CHUNK_MAX = 2048, ATT_CHUNK_MIN = 256;   // pixels per workgroup, multiples of 64 (4 waves x 16 pixels)
+constexpr int ATT_MIN_WG = 512;                            // two workgroups per CU: the chunk halves until the launch has that many
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+// pixels p .. p + 3 of one channel row, zero past pend.  vec: every row base and p are 16-byte aligned and pend - p is a multiple of 4.
+__device__ __forceinline__ void att_load4(const float* __restrict__ row, int64_t p, int64_t pend, bool vec, float (&v)[4]) {
+    if (vec) {
+        const float4 t = p < pend ? *reinterpret_cast<const float4*>(row + p) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) v[s] = p + s < pend ? row[p + s] : 0.f;
     }
-    double* S = stats + (int64_t)b * (ATT_C * ATT_C + 2 * ATT_C);
-    atomicAdd(&S[i0 * ATT_C + j0], a00);
-    atomicAdd(&S[i0 * ATT_C + j0 + 1], a01);
-    atomicAdd(&S[(i0 + 1) * ATT_C + j0], a10);
-    atomicAdd(&S[(i0 + 1) * ATT_C + j0 + 1], a11);
-    if (j0 == 0) { atomicAdd(&S[ATT_C * ATT_C + i0], r0); atomicAdd(&S[ATT_C * ATT_C + i0 + 1], r1); }
-    if (i0 == 0) { atomicAdd(&S[ATT_C * ATT_C + ATT_C + j0], c0); atomicAdd(&S[ATT_C * ATT_C + ATT_C + j0 + 1], c1); }
+}
+
+__global__ __launch_bounds__(256) void attn_stats_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                         double* __restrict__ stats, int L, int chunk, int vec) {
+    __shared__ double part[4][ATT_STATS];
+    const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int c = lane & 15, g = lane >> 4;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk, pend = min(p0 + chunk, (int64_t)L);
+    const float* rows[4] = {f1 + ((int64_t)b * ATT_C + c) * L, f1 + ((int64_t)b * ATT_C + c + 16) * L,
+                            f2 + ((int64_t)b * ATT_C + c) * L, f2 + ((int64_t)b * ATT_C + c + 16) * L};
+    f64x4 acc[2][2] = {};
+    double sum[4] = {0, 0, 0, 0};
+    float cur[4][4], nxt[4][4];
+    int64_t pb = p0 + wave * 16;                                      // wave-uniform: every lane of the wave runs every MFMA
+#pragma unroll
+    for (int r = 0; r < 4; ++r) att_load4(rows[r], pb + 4 * g, pend, vec, cur[r]);
+    for (; pb < pend; pb += 64) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) att_load4(rows[r], pb + 64 + 4 * g, pend, vec, nxt[r]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const double a0 = (double)cur[0][s], a1 = (double)cur[1][s], b0 = (double)cur[2][s], b1 = (double)cur[3][s];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+            sum[0] += a0; sum[1] += a1; sum[2] += b0; sum[3] += b1;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) cur[r][s] = nxt[r][s];
+    }
+    // C/D of the f64 MFMA: register q of a lane is row (lane >> 4) + 4 q, column lane & 15 of its tile
+    double* mine = part[wave];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mine[(16 * ti + g + 4 * q) * ATT_C + 16 * tj + c] = acc[ti][tj][q];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                                     // the four pixel groups g of a channel sit 16 lanes apart
+        double v = sum[r];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (g == 0) mine[ATT_C * ATT_C + 16 * r + c] = v;             // s1[c], s1[c + 16], s2[c], s2[c + 16]
+    }
+    __syncthreads();
+    double* S = stats + (int64_t)b * ATT_STATS;
+    for (int i = threadIdx.x; i < ATT_STATS; i += 256) atomicAdd(&S[i], (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]));
 }
 
 // One workgroup of 32x32 threads per image; thread (i, j) owns entry [i][j] of every 32x32 product.
@@ -160,9 +197,13 @@ extern "C" int bem_attn_stats_f64(const float* f1, const float* f2, double* stat
     BEM_REQUIRE(B >= 0 && B <= 65535 && L > 0, "attn_stats: bad shape");
     if (B == 0) return BEM_OK;
     hipStream_t s = (hipStream_t)stream;
-    BEM_ZERO(stats, sizeof(double) * (size_t)B * (ATT_C * ATT_C + 2 * ATT_C), s, "attn_stats");
-    dim3 grid(cdiv(L, ATT_CHUNK), B);
-    attn_stats_kernel<<<grid, 256, 0, s>>>(f1, f2, stats, L);
+    BEM_ZERO(stats, sizeof(double) * (size_t)B * ATT_STATS, s, "attn_stats");
+    int chunk = ATT_CHUNK_MAX;
+    while (chunk > ATT_CHUNK_MIN && (int64_t)B * cdiv64(L, chunk) < ATT_MIN_WG) chunk >>= 1;
+    // float4 loads need every channel row 16-byte aligned; otherwise (L % 4 != 0: the rows of every second channel are not) scalar loads
+    const int vec = L % 4 == 0 && (((uintptr_t)f1 | (uintptr_t)f2) & 15) == 0;
+    dim3 grid((unsigned)cdiv64(L, chunk), B);
+    attn_stats_kernel<<<grid, 256, 0, s>>>(f1, f2, stats, L, chunk, vec);
     return bem_check_launch("attn_stats");
 }
 

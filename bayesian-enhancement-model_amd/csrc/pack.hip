@@ -64,40 +64,74 @@ __global__ __launch_bounds__(256) void pack_x6_jobs_kernel(const packjob* __rest
 // Bayesian weight sets straight into operand order: w[set][row][k] = mu + log1p(exp(rho)) * eps, eps injected or drawn
 // with the sampler's own Philox stream (element index i = set*M*K + row*K + k, as bem_bnn_sample_f32 numbers it), split
 // and stored like pack_x6_kernel does -- the natural-order copy (one write + one read per weight and sample) is skipped.
-__device__ __forceinline__ void sample_pack_x6_item(int64_t i, const float* __restrict__ mu, const float* __restrict__ rho,
+// ALIGNED: every lane's first element opens a counter block (g0 & 3 == 0), so 8 elements span two blocks and the third is not in the
+// instruction stream; otherwise up to three.  Either way a lane evaluates only the blocks its live elements read -- none for a lane
+// of padding (row >= M or k0 >= K), one when four or fewer elements are live.
+template <bool ALIGNED>
+__device__ __forceinline__ void sample_pack_x6_draw(int64_t set, int mt, int kb, int lane, const float* __restrict__ mu, const float* __restrict__ rho,
                                                     const float* __restrict__ eps_in, u32x4* __restrict__ Wp, int M, int K, int MT, int KB,
                                                     uint64_t seed, uint64_t stream_id, int sigma_given) {
-    const int lane = (int)(i & 63);
-    const int64_t blk = i >> 6;
-    const int kb = (int)(blk % KB), mt = (int)((blk / KB) % MT);
-    const int64_t set = blk / ((int64_t)KB * MT);
     const int row = mt * 32 + (lane & 31), k0 = kb * 16 + (lane >> 5) * 8;
     float v[8];
     // the lane's 8 consecutive k of one row are 8 consecutive element indices: at most 3 Philox counter blocks
     const int64_t g0 = set * M * K + (int64_t)row * K + k0;
-    float z[3][4];
-    if (!eps_in && row < M) {
+    const int off = ALIGNED ? 0 : (int)(g0 & 3);                          // position of the first element in its block
+    const int live = row < M ? min(8, K - k0) : 0;                        // <= 0: the lane holds padding only
+    constexpr int NQ = ALIGNED ? 2 : 3;
+    float z[NQ][4];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) philox_normal4((g0 >> 2) + q, seed, stream_id, z[q]);
+    for (int q = 0; q < NQ; ++q)                                          // block q is read by elements 4q - off .. 4q - off + 3
+        if (!eps_in && live > 0 && q <= ((off + live - 1) >> 2)) philox_normal4((g0 >> 2) + q, seed, stream_id, z[q]);
+    // mu and sigma of the lane's elements.  Aligned, they are one or two 16-byte vectors per tensor: as eight dword loads each, a wave's
+    // load instruction touches 32 rows for 4 bytes apiece, and those cache-line lookups, not the arithmetic, were the kernel's time.
+    const int64_t idx0 = (int64_t)row * K + k0;
+    float mv[8], sv[8];
+    if (ALIGNED && (((uintptr_t)mu | (uintptr_t)rho) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {                                     // live is 0, 4 or 8 here
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (4 * q < live) { a = *reinterpret_cast<const float4*>(mu + idx0 + 4 * q); b = *reinterpret_cast<const float4*>(rho + idx0 + 4 * q); }
+            mv[4 * q] = a.x; mv[4 * q + 1] = a.y; mv[4 * q + 2] = a.z; mv[4 * q + 3] = a.w;
+            sv[4 * q] = b.x; sv[4 * q + 1] = b.y; sv[4 * q + 2] = b.z; sv[4 * q + 3] = b.w;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { mv[e] = e < live ? mu[idx0 + e] : 0.f; sv[e] = e < live ? rho[idx0 + e] : 0.f; }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         v[e] = 0.f;
-        if (row < M && k0 + e < K) {
-            const int64_t idx = (int64_t)row * K + k0 + e, gi = g0 + e;
-            const int off = (int)(g0 & 3);                                // position of the first element in its block
+        if (e < live) {
             // z[(off + e) >> 2][(off + e) & 3] with compile-time indices (a runtime index would put z into scratch)
-            const float zsel = off == 0 ? z[e >> 2][e & 3] : off == 1 ? z[(e + 1) >> 2][(e + 1) & 3]
-                             : off == 2 ? z[(e + 2) >> 2][(e + 2) & 3] : z[(e + 3) >> 2][(e + 3) & 3];
-            const float eps = eps_in ? eps_in[gi] : zsel;
+            float zsel;
+            if constexpr (ALIGNED) zsel = z[e >> 2][e & 3];
+            else zsel = off == 0 ? z[e >> 2][e & 3] : off == 1 ? z[(e + 1) >> 2][(e + 1) & 3]
+                      : off == 2 ? z[(e + 2) >> 2][(e + 2) & 3] : z[(e + 3) >> 2][(e + 3) & 3];
+            const float eps = eps_in ? eps_in[g0 + e] : zsel;
             // sigma = log1p(exp(rho)) does not depend on the sample: callers that draw many sets pass it precomputed
-            v[e] = mu[idx] + (sigma_given ? rho[idx] : log1pf(expf(rho[idx]))) * eps;
+            v[e] = mv[e] + (sigma_given ? sv[e] : log1pf(expf(sv[e]))) * eps;
         }
     }
     u32x4 h, m, l;
     split8(v, h, m, l);
     u32x4* o = Wp + ((set * MT + mt) * KB + kb) * 3 * 64 + lane;
     o[0] = h; o[64] = m; o[128] = l;
+}
+
+__device__ __forceinline__ void sample_pack_x6_item(int64_t i, const float* __restrict__ mu, const float* __restrict__ rho,
+                                                    const float* __restrict__ eps_in, u32x4* __restrict__ Wp, int M, int K, int MT, int KB,
+                                                    uint64_t seed, uint64_t stream_id, int sigma_given) {
+    const int lane = (int)(i & 63);
+    // work items come in runs of 256 from a multiple of 256, so a wave holds one 64-lane block: its (set, row tile, k block) is decoded
+    // once per wave on the scalar unit instead of three 64-bit divisions per lane
+    const uint64_t ub = (uint64_t)(i >> 6);
+    const int64_t blk = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(ub >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)ub));
+    const int kb = (int)(blk % KB), mt = (int)((blk / KB) % MT);
+    const int64_t set = blk / ((int64_t)KB * MT);
+    // K % 4 == 0 makes set M K, row K and k0 multiples of 4 for every lane of the launch (every 1x1 tensor of the Stage-I net): the
+    // branch is uniform over the tensor
+    if ((K & 3) == 0) sample_pack_x6_draw<true>(set, mt, kb, lane, mu, rho, eps_in, Wp, M, K, MT, KB, seed, stream_id, sigma_given);
+    else sample_pack_x6_draw<false>(set, mt, kb, lane, mu, rho, eps_in, Wp, M, K, MT, KB, seed, stream_id, sigma_given);
 }
 
 __global__ void sample_pack_x6_kernel(const float* __restrict__ mu, const float* __restrict__ rho, const float* __restrict__ eps_in,
