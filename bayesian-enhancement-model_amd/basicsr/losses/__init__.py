@@ -3,7 +3,9 @@
 ``L1Loss`` runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn).  ``PerceptualLoss``
 (VGG19 features, criterion l1) is bem.percep's module: one autograd node of HIP kernels (bem.autograd.PerceptualFn); its weights are
 read from a torchvision state dict on disk (bem.percep.weights_path), never fetched.  ``SSIMLoss`` is one tiled HIP kernel forward (plus
-the fixed-order sum of its partials) and one backward (bem.autograd.SSIMLossFn)."""
+the fixed-order sum of its partials) and one backward (bem.autograd.SSIMLossFn).  ``LPIPSLoss`` is the metric of bem.lpips (v0.1, AlexNet)
+without its quantisation, as one autograd node of HIP kernels (bem.autograd.LPIPSFn); its two weight files are found on disk
+(bem.lpips.find_weight_files), never fetched."""
 from copy import deepcopy
 
 import torch.nn as nn
@@ -11,9 +13,10 @@ import torch.nn as nn
 from basicsr.utils.registry import LOSS_REGISTRY
 from basicsr.utils.registry import ARCH_REGISTRY
 from bem import autograd as _ag
+from bem.lpips import LPIPS
 from bem.percep import PerceptualLoss, VGGFeatureExtractor
 
-__all__ = ["build_loss", "L1Loss", "SSIMLoss", "PerceptualLoss", "VGGFeatureExtractor"]
+__all__ = ["build_loss", "L1Loss", "SSIMLoss", "LPIPSLoss", "PerceptualLoss", "VGGFeatureExtractor"]
 
 LOSS_REGISTRY.register(PerceptualLoss)
 if "VGGFeatureExtractor" not in ARCH_REGISTRY:
@@ -55,6 +58,28 @@ class SSIMLoss(nn.Module):
         if weight is not None:
             raise NotImplementedError("SSIMLoss: element-wise weights are not used on the BEM path")
         return _ag.ssim_loss(pred, target, self.loss_weight)
+
+
+@LOSS_REGISTRY.register()
+class LPIPSLoss(nn.Module):
+    """loss_weight * mean_b d(target_b, pred_b), d what ``lpips.LPIPS(net='alex')(target, pred, normalize=normalize)`` computes (bem.lpips:
+    no quantisation, no clipping).  ``normalize=True``: images in [0,1], as the training step holds them; False: already in [-1,1].
+    Gradient goes to pred alone; the AlexNet and linear-layer weights are frozen buffers, absent from any state dict.  ``weights_dir``
+    names the directory of the two weight files (otherwise BEM_LPIPS_WEIGHTS / experiments/pretrained_models, bem.lpips)."""
+
+    def __init__(self, loss_weight=1.0, reduction="mean", net="alex", normalize=True, weights_dir=None):
+        super().__init__()
+        if reduction != "mean":
+            raise ValueError(f"Unsupported reduction mode: {reduction}. The HIP path implements 'mean' (over the batch).")
+        if net != "alex":
+            raise ValueError(f"Unsupported net: {net}. The HIP path implements 'alex' (the trunk the evaluation scripts report).")
+        self.loss_weight, self.reduction, self.net, self.normalize = loss_weight, reduction, net, bool(normalize)
+        self.lpips = LPIPS(net=net, weights_dir=weights_dir)
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        if weight is not None:
+            raise NotImplementedError("LPIPSLoss: element-wise weights are not used on the BEM path")
+        return _ag.lpips_loss(pred, target, self)
 
 
 def build_loss(opt):

@@ -8,6 +8,7 @@
 
   python basicsr/train.py --opt Options/DecompDualBranch2DDWavelet_4.yml --synthetic 64 [--auto_resume] [--debug]
       [--force_yml train:total_iter=200 logger:save_checkpoint_freq=50] [--launcher pytorch] [--vgg_weights vgg19-dcbb9e9d.pth]
+      [--lpips_weights DIR]
 
 What is the hot path runs on the HIP kernels (``optimize_parameters`` of the two model classes: forward, backward, clip, AdamW with no
 host synchronisation inside the step; validation through the inference kernels).  What is control plane stays small and host-side:
@@ -68,6 +69,10 @@ def train_pipeline(root_path, argv=None):
     opt, args = parse_options(root_path, is_train=True, argv=argv)
     opt["root_path"] = root_path
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if (opt.get("train") or {}).get("lpips_opt"):
+        # the weight files of the LPIPS term are looked for now: a missing one stops the run before directories, data or a model exist
+        from bem.lpips import find_weight_files
+        find_weight_files(opt["train"]["lpips_opt"].get("weights_dir"))
 
     resume_state = load_resume_state(opt, experiments_root=osp.dirname(opt["path"]["experiments_root"]))
     if resume_state is None and opt["rank"] == 0:

@@ -82,7 +82,9 @@ def parse_options(root_path, is_train=True, argv=None):
     ``--force_yml a:b=v`` walks the keys instead of exec'ing a string.  Two extra flags select the tensor dataset shim of basicsr.data
     (without them a ``Dataset_PairedImage_Mask`` option file trains from its image folders): ``--synthetic N`` and ``--pairs file.pt``; ``--vgg_weights PATH`` names the VGG19
     state dict of ``train.perceptual_opt`` (bem.percep.weights_path) by SETTING the environment variable ``BEM_VGG19_WEIGHTS`` of this
-    process, which is not restored: a caller that parses options in-process and goes on afterwards saves and restores it itself."""
+    process, which is not restored: a caller that parses options in-process and goes on afterwards saves and restores it itself.
+    ``--lpips_weights DIR`` names the directory of the two weight files of ``train.lpips_opt`` (bem.lpips.find_weight_files) the same
+    way, through ``BEM_LPIPS_WEIGHTS``."""
     import argparse
     import random
 
@@ -98,10 +100,15 @@ def parse_options(root_path, is_train=True, argv=None):
     p.add_argument("--pairs", default=None, help="train / validate on a .pt file of dict(lq, gt) tensors (basicsr.data shim)")
     p.add_argument("--vgg_weights", default=None, help="torchvision vgg19 state dict for train.perceptual_opt (sets BEM_VGG19_WEIGHTS; "
                                                        "default experiments/pretrained_models/vgg19-dcbb9e9d.pth)")
+    p.add_argument("--lpips_weights", default=None, help="directory with alexnet-owt-7be5be79.pth and alex.pth for train.lpips_opt (sets "
+                                                         "BEM_LPIPS_WEIGHTS; default experiments/pretrained_models/)")
     args = p.parse_args(argv)
     if args.vgg_weights:
         import os
         os.environ["BEM_VGG19_WEIGHTS"] = os.path.abspath(args.vgg_weights)
+    if args.lpips_weights:
+        import os
+        os.environ["BEM_LPIPS_WEIGHTS"] = os.path.abspath(args.lpips_weights)
     with open(args.opt, "r") as f:
         opt = yaml.load(f, Loader=ordered_yaml()[0])
     if args.launcher == "none":

@@ -281,6 +281,55 @@ def perceptual_loss(pred, gt, mod):
     return PerceptualFn.apply(pred, gt.detach(), mod)          # basic_loss.py:210
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# LPIPS (v0.1, AlexNet) as a loss term
+# ------------------------------------------------------------------------------------------------------------------
+class LPIPSFn(Function):
+    """mod.loss_weight * mean_b d(gt_b, pred_b), d the distance of ``mod.lpips`` (a bem.lpips.LPIPS) on unquantised inputs: in [0,1] with
+    ``mod.normalize``, in [-1,1] without.  Forward: the launches of LPIPS.forward and one bem_lpips_mean_f32.  Backward: the pred rows only,
+    against the frozen weights -- per layer from the top the head backward (which adds the gradient from the layer above and applies
+    the ReLU mask) and the convolution's input gradient, a pool backward before layers 1 and 0, the input stage's adjoint last; none
+    for gt.  Saved: the five 2B-row features (the head backward needs the reference rows too)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mod):
+        net = mod.lpips
+        pred, gt = pred.contiguous(), gt.contiguous()
+        if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != gt.shape:
+            raise ValueError(f"lpips_loss: two (B,3,H,W) tensors of one shape required, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+        B, _, H, W = pred.shape
+        ys = net.features(ops.lpips_prep(gt, pred, quantise=False, normalize=mod.normalize), H, W)
+        out = ws = None
+        for i, y in enumerate(ys):
+            out, ws = ops.lpips_layer(y, getattr(net, f"lin{i}"), ws=ws, out=out, first=i == 0)
+        if ctx.needs_input_grad[0]:
+            ctx.mod, ctx.hw = mod, (H, W)
+            ctx.save_for_backward(*ys)
+        return ops.lpips_mean(ws, B, float(mod.loss_weight)).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        mod, (H, W), ys = ctx.mod, ctx.hw, ctx.saved_tensors
+        net, B = mod.lpips, ys[0].shape[0] // 2
+        wb_, pads = net.conv_operands_bwd(), [p for _, _, p in net.conv_operands()]
+        gmul, scale = g.reshape(1).contiguous().float(), float(mod.loss_weight) / B
+        gin = None
+        for i in (4, 3, 2, 1):
+            d = ops.lpips_layer_bwd(ys[i], getattr(net, f"lin{i}"), gin, gmul, scale)
+            gin = ops.conv2d(d, wb_[i], None, pad=pads[i])
+            if i <= 2:                                               # conv2 and conv3 read a pooled feature
+                gin = ops.relu_pool3s2_bwd(ys[i - 1][B:], gin)
+        # layer 0 is a crop of conv1's block grid: its gradient goes back into the whole grid, zero around the crop
+        Ho, Wo = ops.lpips_conv1_hw(H, W)
+        d = torch.empty(B, ys[0].shape[1], Ho + 2, (Wo + 3) // 2 * 2, device=gin.device, dtype=torch.float32)
+        ops.lpips_layer_bwd(ys[0], net.lin0, gin, gmul, scale, out=d, origin=(1, 1))
+        return ops.lpips_prep_bwd(ops.conv2d(d, wb_[0], None, pad=pads[0]), H, W, normalize=mod.normalize), None, None
+
+
+def lpips_loss(pred, gt, mod):
+    return LPIPSFn.apply(pred, gt.detach(), mod)
+
+
 class IwtHamiltonFn(Function):
     @staticmethod
     def forward(ctx, q1w, q2w):

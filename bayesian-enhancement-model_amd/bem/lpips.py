@@ -1,5 +1,6 @@
-"""LPIPS v0.1 with the AlexNet trunk (Zhang et al. 2018), forward only: the ``--lpips`` metric of Enhancement/eval.py:143-145,301-306 and
-Enhancement/cal_metrics_with_imgs.py:39-41,51-55, with the call signature of ``lpips.LPIPS(net='alex')``.
+"""LPIPS v0.1 with the AlexNet trunk (Zhang et al. 2018): the ``--lpips`` metric of Enhancement/eval.py:143-145,301-306 and
+Enhancement/cal_metrics_with_imgs.py:39-41,51-55, with the call signature of ``lpips.LPIPS(net='alex')``, forward only; the loss term
+``train.lpips_opt`` differentiates the same distance through bem.autograd.LPIPSFn, which takes its weights from this module.
 
 Input stage, the two pools and the distance heads are the kernels of csrc/lpips.hip; the five convolutions run on the convolution kernels
 bem.ops.conv2d dispatches to.  Weights come from two files the user supplies -- torchvision's ``alexnet-owt-7be5be79.pth`` and the ``lpips``
@@ -112,11 +113,11 @@ class LPIPS(nn.Module):
                                      persistent=False)
             self.register_buffer(f"lin{i}", lin_state_dict[f"lin{i}.model.1.weight"].detach().to(torch.float32).reshape(-1).contiguous().clone(),
                                  persistent=False)
-        self._ops = None
+        self._ops = self._ops_bwd = None
         self.eval()
 
     def _apply(self, fn, *a, **k):
-        self._ops = None                   # the operand forms below belong to the buffers they were packed from
+        self._ops = self._ops_bwd = None   # the operand forms below belong to the buffers they were packed from
         return super()._apply(fn, *a, **k)
 
     def conv_operands(self):
@@ -127,6 +128,15 @@ class LPIPS(nn.Module):
                 self._ops = [(ops.ConvWeight(conv1_block_weight(self.conv0_weight) if i == 0 else getattr(self, f"conv{i}_weight")),
                               getattr(self, f"conv{i}_bias"), 1 if i == 0 else c[5]) for i, c in enumerate(ALEX_CONVS)]
         return self._ops
+
+    def conv_operands_bwd(self):
+        """[ConvWeight] per convolution for its input gradient: the weight flipped along both taps and transposed, conv1's from its block
+        form ((64,48,3,3) -> (48,64,3,3)); the gradient is ops.conv2d(d, this, None, pad=conv_operands' pad).  Held like the forward forms."""
+        if self._ops_bwd is None:
+            with torch.no_grad():
+                self._ops_bwd = [ops.ConvWeight((conv1_block_weight(self.conv0_weight) if i == 0 else getattr(self, f"conv{i}_weight"))
+                                                .flip(2, 3).transpose(0, 1).contiguous()) for i in range(len(ALEX_CONVS))]
+        return self._ops_bwd
 
     def features(self, xs, H, W):
         """The five ReLU outputs for the block-form input of ops.lpips_prep; the first is a crop of conv1's block grid (a view, not a copy)."""

@@ -1952,6 +1952,75 @@ def lpips_layer(feat, lin, ws=None, out=None, first=True):
     return out, ws
 
 
+def lpips_mean(ws, B, weight=1.0):
+    """loss (1,) = weight * mean of the B distances whose f64 running sums the last lpips_layer call left in ws[:B]."""
+    _chk(ws, "ws", dtype=torch.float64)
+    if not 1 <= B <= ws.numel():
+        raise ValueError(f"lpips_mean: {B} distances in a workspace of {ws.numel()}")
+    loss = torch.empty(1, device=ws.device, dtype=torch.float32)
+    check(lib().bem_lpips_mean_f32(_p(ws), _p(loss), B, float(weight), _stream()), "lpips_mean")
+    return loss
+
+
+def lpips_layer_bwd(feat, lin, gin=None, gmul=None, scale=1.0, out=None, origin=(0, 0)):
+    """Head backward of one layer for the pred rows: feat (2B,C,h,w) and lin as lpips_layer takes them, ``gin`` (B,C,h,w) the gradient reaching
+    the same post-ReLU feature from the layer above, ``gmul`` the device scalar dL/dloss (None = 1), ``scale`` = loss_weight / B.  Returns
+    (y_pred > 0) ? gin + g : 0, the gradient at the convolution's output before its ReLU (include/bem_hip.h: bem_lpips_layer_bwd_f32).
+    ``out`` (B,C,oh,ow), unit stride along its rows, is written as a whole: the result at rows / columns ``origin`` onwards, zero around it."""
+    bs, cs, rs = _plane_view("lpips_layer_bwd", feat, 2)
+    _chk(lin, "lin"); _chk(gin, "gin", optional=True); _chk(gmul, "gmul", optional=True)
+    B2, C, h, w = feat.shape
+    if B2 % 2 or B2 == 0 or lin.numel() != C:
+        raise ValueError(f"lpips_layer_bwd: feat {tuple(feat.shape)} needs an even number of rows and lin {tuple(lin.shape)} one weight per channel")
+    B = B2 // 2
+    if gin is not None and tuple(gin.shape) != (B, C, h, w):
+        raise ValueError(f"lpips_layer_bwd: gin {tuple(gin.shape)} is not the pred half {(B, C, h, w)} of feat")
+    if gmul is not None and gmul.numel() != 1:
+        raise ValueError("lpips_layer_bwd: gmul is one device scalar")
+    if out is None:
+        out = torch.empty(B, C, h + origin[0], w + origin[1], device=feat.device, dtype=torch.float32)
+    obs, ocs, ors = _plane_view("lpips_layer_bwd", out, 2)
+    oh, ow = out.shape[2:]
+    if tuple(out.shape[:2]) != (B, C) or min(origin) < 0 or origin[0] + h > oh or origin[1] + w > ow:
+        raise ValueError(f"lpips_layer_bwd: out {tuple(out.shape)} does not hold a {(B, C, h, w)} gradient at {tuple(origin)}")
+    check(lib().bem_lpips_layer_bwd_f32(_p(feat), bs, cs, rs, _p(lin), _p(gin), _p(gmul), float(scale), _p(out), obs, ocs, ors, B, C, h, w,
+                                        oh, ow, int(origin[0]), int(origin[1]), _stream()), "lpips_layer_bwd")
+    return out
+
+
+def relu_pool3s2_bwd(y, dpool):
+    """Gradient of maxpool3s2(y) with respect to y (B,C,H,W), which may be a crop of a wider tensor: dpool at each window's first maximum
+    in row-major order (torch's rule), summed where windows overlap, zero elsewhere -> (B,C,H,W) contiguous.  The mask of the ReLU that
+    made y is left to lpips_layer_bwd, which takes the result as its ``gin``."""
+    bs, cs, rs = _plane_view("relu_pool3s2_bwd", y, 2)
+    _chk(dpool, "dpool")
+    B, C, H, W = y.shape
+    if H < 3 or W < 3:
+        raise ValueError(f"relu_pool3s2_bwd: planes of at least 3 x 3 required, got {tuple(y.shape)}")
+    if B != 1 and bs != C * cs:
+        raise ValueError(f"relu_pool3s2_bwd: planes are not evenly strided ({y.stride()})")
+    if tuple(dpool.shape) != (B, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1):
+        raise ValueError(f"relu_pool3s2_bwd: dpool {tuple(dpool.shape)} is not the pooled shape of y {tuple(y.shape)}")
+    dy = torch.empty(B, C, H, W, device=y.device, dtype=torch.float32)
+    check(lib().bem_relu_pool3s2_bwd_f32(_p(y), cs, rs, _p(dpool), _p(dy), B * C, H, W, _stream()), "relu_pool3s2_bwd")
+    return dy
+
+
+def lpips_prep_bwd(gxs, H, W, quantise=False, normalize=False):
+    """dpred (B,3,H,W) from gxs (B,48,Hb,Wb), the gradient of the pred rows of lpips_prep's output; ``normalize`` as the forward took it.
+    The quantising input stage has no gradient: ``quantise`` is refused by the library."""
+    _chk(gxs, "gxs")
+    if H < LPIPS_MIN_HW or W < LPIPS_MIN_HW:
+        raise ValueError(f"lpips_prep_bwd: images of at least {LPIPS_MIN_HW} x {LPIPS_MIN_HW} required, got {H} x {W}")
+    Ho, Wo = lpips_conv1_hw(H, W)
+    if gxs.dim() != 4 or gxs.shape[0] < 1 or tuple(gxs.shape[1:]) != (48, Ho + 2, (Wo + 3) // 2 * 2):
+        raise ValueError(f"lpips_prep_bwd: gxs {tuple(gxs.shape)} is not the block form (B, 48, {Ho + 2}, {(Wo + 3) // 2 * 2}) of {H} x {W} images")
+    B = gxs.shape[0]
+    dpred = torch.empty(B, 3, H, W, device=gxs.device, dtype=torch.float32)
+    check(lib().bem_lpips_prep_bwd_f32(_p(gxs), _p(dpred), B, H, W, 1 if quantise else 2 if normalize else 0, _stream()), "lpips_prep_bwd")
+    return dpred
+
+
 def _ln_bwd_cost(x1, x2, dres, want_n, **_):
     return 4.0 * x1.numel() * (3 + (x2 is not None) + (dres is not None) + bool(want_n)), 0.0
 

@@ -697,7 +697,7 @@ int bem_relu_bwd_f32(const float* y, const float* dy, float* out, int64_t n, voi
 int bem_relu_f32(const float* x, float* out, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * LPIPS v0.1 with the AlexNet trunk, forward only (csrc/lpips.hip; the metric of Enhancement/eval.py:143-145,301-306 and
+ * LPIPS v0.1 with the AlexNet trunk (csrc/lpips.hip; the metric of Enhancement/eval.py:143-145,301-306 and
  * Enhancement/cal_metrics_with_imgs.py:39-41,51-55).  The five convolutions are bem_conv3x3_x6_f32 / bem_conv_taps_x6_f32 / bem_conv2d_f32.
  * ------------------------------------------------------------------------------------------- */
 
@@ -723,6 +723,37 @@ int bem_maxpool3s2_f32(const float* x, int64_t x_pstride, int64_t x_rstride, flo
 int64_t bem_lpips_layer_ws_elems(int B, int h, int w);
 int bem_lpips_layer_f32(const float* feat, int64_t f_bstride, int64_t f_cstride, int64_t f_rstride, const float* lin, double* ws,
                         int64_t ws_elems, float* out, int B, int C, int h, int w, int first, void* stream);
+
+/* LPIPS as a loss term (basicsr.losses.LPIPSLoss over bem.autograd.LPIPSFn): loss_weight * mean_b d(ref_b, pred_b) and its gradient with
+ * respect to pred, input modes 0 and 2 of bem_lpips_prep_f32.  Each kernel writes every output element once: a call repeats bit for bit. */
+
+/* loss[0] = weight * mean of acc[0,B), acc the f64 running sums in the workspace of the last bem_lpips_layer_f32 call (ws[0,B)). */
+int bem_lpips_mean_f32(const double* acc, float* loss, int B, float weight, void* stream);
+
+/* Head backward of one layer, pred rows [B,2B) only; feat / lin / strides as bem_lpips_layer_f32 takes them.  Per pixel in f64 from the f32
+ * features: n = sqrt(sum_c y^2), r = 1 / (n + 1e-10), a = y_ref r_ref, b = y_pred r_pred, D_c = -2 lin_c (a_c - b_c) (the two products
+ * rounded separately: equal images give exactly 0), g_k = r_pred D_k - y_pred,k (r_pred / n_pred) sum_c b_c D_c, the second term 0 where
+ * n_pred = 0; times scale * gmul[0] / (h w) with scale = loss_weight / B and gmul the device scalar dL/dloss (NULL = 1).
+ * gin (or NULL): (B,C,h,w) contiguous, the gradient that reaches the same post-ReLU feature from the layer above.
+ * dz (B,C,oh,ow) at its batch / channel / row strides: (y_pred > 0) ? gin + g : 0 -- the gradient at the convolution's output, before the
+ * ReLU -- at rows [oy0, oy0+h) and columns [ox0, ox0+w), zero at every other position of the oh x ow extent (layer 0: conv1's block grid
+ * around its crop, oy0 = ox0 = 1).  A pixel whose pred features are all zero gets 0, where autograd of y / (|y| + eps) gives NaN. */
+int bem_lpips_layer_bwd_f32(const float* feat, int64_t f_bstride, int64_t f_cstride, int64_t f_rstride, const float* lin, const float* gin,
+                            const float* gmul, float scale, float* dz, int64_t d_bstride, int64_t d_cstride, int64_t d_rstride, int B, int C,
+                            int h, int w, int oh, int ow, int oy0, int ox0, void* stream);
+
+/* Backward of bem_maxpool3s2_f32: y (planes,H,W) at y_pstride / y_rstride is the pool's input, dpool (planes,(H-3)/2+1,(W-3)/2+1) the
+ * gradient of its output, dy (planes,H,W) contiguous.  A gather: each input pixel adds dpool of those of the up to four windows covering
+ * it whose first maximum in row-major order it is (torch's rule; ties go to the first); pixels no window covers get 0.  y is a ReLU
+ * output in the loss, but the mask y > 0 is NOT applied here: bem_lpips_layer_bwd_f32 applies it to its gin.  H, W >= 3, H*W < 2^31,
+ * planes < 2^31. */
+int bem_relu_pool3s2_bwd_f32(const float* y, int64_t y_pstride, int64_t y_rstride, const float* dpool, float* dy, int64_t planes, int H,
+                             int W, void* stream);
+
+/* Adjoint of bem_lpips_prep_f32 for the pred rows: gxs (B,48,Hb,Wb) contiguous, the gradient of the block-form operand;
+ * dpred[b,c,y,x] = k * gxs[b, 16 c + 4 ((y+2) % 4) + (x+2) % 4, (y+2) / 4, (x+2) / 4] / scale_c (one true f32 division), k = 2 in mode 2
+ * and 1 in mode 0.  Mode 1 quantises and has no gradient: refused.  H, W >= 31, H*W < 2^31. */
+int bem_lpips_prep_bwd_f32(const float* gxs, float* dpred, int B, int H, int W, int mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training batches from the device-resident image store (csrc/batch_assemble.hip): Dataset_PairedImage_Mask.__getitem__ for a whole
