@@ -18,6 +18,7 @@ from basicsr.models.base_model import BaseModel
 from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
 from bem import ops
+from bem.archs import AttnDrop, attn_drop_stream_id
 
 
 @MODEL_REGISTRY.register()
@@ -74,10 +75,28 @@ class ImageEnhancer(BaseModel):
         ops.bilinear_up(self.conds, s, dst=x, dst_c0=3)
         return x
 
+    attn_drop_masks = None      # parity runs: the keep flags of the next step's decomposition calls, one (B,2,32,32) tensor per call
+
+    def _attn_drop(self, current_iter):
+        """The frozen decomposition's attention dropout (QD model3, live in train() mode) draws from the device Philox stream in a key space
+        of its own (bem.archs.attn_drop_stream_id: bit 61), a function of (manual_seed, rank, iteration) with the iteration feed_train_data
+        derived: replicas never share a draw and a resumed run continues the sequence.  Returns the decomposition, or None without one."""
+        dec = getattr(self.get_bare_model(self.net_g), "decomp", None)
+        if dec is None or not dec.cross_attn.p > 0:
+            return None
+        it = int(getattr(self, "_cond_calls", 0) or current_iter)
+        dec.attn_drop = AttnDrop(int(self.opt.get("manual_seed", 0) or 0), attn_drop_stream_id(int(self.opt.get("rank", 0)), it), self.attn_drop_masks)
+        return dec
+
     def optimize_parameters(self, current_iter):
         self.optimizer_g.zero_grad()
         x = self._net_input()
-        _, preds = self.net_g(x, mask=None)                           # the Decomp* archs ignore the MIM mask (DDWavelet_arch.py:301)
+        dec = self._attn_drop(current_iter)
+        try:
+            _, preds = self.net_g(x, mask=None)                       # the Decomp* archs ignore the MIM mask (DDWavelet_arch.py:301)
+        finally:
+            if dec is not None:
+                dec.attn_drop = None                                  # the record is this forward's alone
         loss_dict = OrderedDict()
         # :183-191: l_total = l_pix + l_percep (+ l_ssim, my_loss.py:37-38, + l_lpips) over the configured terms; preds feeds each of them,
         # its gradients are summed by bem_add_f32 (ag.fork_n; one term alone takes preds itself)

@@ -51,12 +51,34 @@ def conv_down(c):
 # Quaternion-Retinex decomposition (frozen)
 # ------------------------------------------------------------------------------------------------
 class _CrossAttnParams(nn.Module):
-    """SymmetricCrossAttention (QD/model4.py:81-139) parameter holder; evaluated folded (bem_attn_fold)."""
+    """SymmetricCrossAttention (QD/model4.py:81-139) parameter holder; evaluated folded (bem_attn_fold).  ``p``: the probability of its
+    attn_drop (QD/model3.py:98: 0.1; model2 builds it with 0.0, model1 / model4 have none), live in train() mode only."""
 
-    def __init__(self, dim):
+    def __init__(self, dim, p=0.0):
         super().__init__()
+        self.p = float(p)
         for n in ("q1_proj", "k2_proj", "v2_proj", "q2_proj", "k1_proj", "v1_proj", "out1", "out2"):
             setattr(self, n, nn.Conv2d(dim, dim, 1))
+
+
+def attn_drop_stream_id(rank, iteration, call=0):
+    """Philox stream id of one decomposition call's attention-dropout draw, in a key space of its own:
+    bit 61 | rank : 16 bits at bit 44 | iteration : 36 bits at bit 8 | call index within the forward : 8 bits.
+    The weight samples' ids (SampleCtx.next_stream) end at bit 59 and the condition noise sets bit 62, so no two kinds of draw share a
+    stream."""
+    if not (0 <= rank < 1 << 16 and 0 <= iteration < 1 << 36 and 0 <= call < 1 << 8):
+        raise ValueError(f"attn_drop_stream_id: rank {rank}, iteration {iteration} or call {call} outside the 16 / 36 / 8 bit fields")
+    return (1 << 61) | (rank << 44) | (iteration << 8) | call
+
+
+class AttnDrop:
+    """What identifies the attention-dropout draws of ONE forward of a net: its owner (ImageEnhancer.optimize_parameters) sets it as
+    ``decomp.attn_drop`` before the forward.  ``base_stream_id`` = attn_drop_stream_id(rank, iteration); the decomposition counts its calls
+    within the forward into the low 8 bits (the *DD archs decompose the image and the condition).  ``masks``: injected keep flags, one
+    (B,2,32,32) tensor of 0 / 1 per call in call order (parity runs) instead of the in-kernel draw."""
+
+    def __init__(self, seed=0, base_stream_id=1 << 61, masks=None):
+        self.seed, self.base_stream_id, self.masks, self.calls = int(seed), int(base_stream_id), masks, 0
 
 
 class Decomp(nn.Module):
@@ -81,7 +103,8 @@ class Decomp(nn.Module):
         d = 2 if model == "model2" else 1        # QD/model2.py:171-181: the second convolution of each branch is dilated
         self.branch_q1 = nn.Sequential(Conv2dK(nf, nf, 3, padding=1), nn.ReLU(inplace=True), Conv2dK(nf, nf, 3, padding=d, dilation=d))
         self.branch_q2 = nn.Sequential(Conv2dK(nf, nf, 3, padding=1), nn.ReLU(inplace=True), Conv2dK(nf, nf, 3, padding=d, dilation=d))
-        self.cross_attn = _CrossAttnParams(nf)
+        self.cross_attn = _CrossAttnParams(nf, p=0.1 if model == "model3" else 0.0)
+        self.attn_drop = None                    # AttnDrop of the forward under way, set by the net's owner; None: process-wide counter
         self.fuse = nn.Conv2d(nf * 2, nf, 1)
         self.conv_out = Conv2dK(nf, 32, 3, padding=1)
         self.sharpening = Conv2dK(32, 32, 3, padding=1, bias=True)
@@ -128,6 +151,28 @@ class Decomp(nn.Module):
             return d
         return ops.derived(self).get("prep", srcs, prep)
 
+    _drop_calls = 0     # process-wide count of dropout draws made without an AttnDrop record: successive calls never share a stream
+
+    def _next_drop(self):
+        """ops.attn_fold's ``drop`` for this call: None unless the attention dropout is live (train() mode, p > 0; nn.Dropout follows
+        module.training alone, so grad mode does not matter -- QD/model3.py:98,124-131, and the wavelet-domain MyDecomp keeps the same
+        cross_attn, DecompDualBranchDDWavelet_arch.py:55-143)."""
+        p = self.cross_attn.p
+        if not (self.training and p > 0):
+            return None
+        rec = self.attn_drop
+        if rec is None:
+            Decomp._drop_calls += 1
+            return p, 0, (1 << 61) | (Decomp._drop_calls & ((1 << 44) - 1))
+        call, rec.calls = rec.calls, rec.calls + 1
+        if rec.masks is not None:
+            if call >= len(rec.masks):
+                raise BemNativeError(f"Decomp: call {call} of this forward has no injected dropout mask ({len(rec.masks)} given)")
+            return p, rec.masks[call]
+        if call >= 1 << 8:
+            raise BemNativeError("Decomp: more than 256 decomposition calls under one AttnDrop record (set a fresh one per forward)")
+        return p, rec.seed, rec.base_stream_id | call
+
     def forward(self, x, c0=0):
         """x (B,Ct,H,W); channels [c0, c0+3) hold the RGB image to decompose."""
         _need_cuda(x)
@@ -139,16 +184,13 @@ class Decomp(nn.Module):
         P = self._prepared()
         feat = self.conv_in(d)
         if self.model == "model3" and not self.wavelet_out:
-            if self.training and torch.is_grad_enabled():
-                raise BemNativeError("Decomp model3: its attention dropout is active in train() mode (QD/model3.py:98,127); only the eval-mode "
-                                     "(identity) form is on the HIP path")
             mid = self.mid_conv(self.down_conv(feat, relu=True), relu=True)
             feat = ops.add(feat, self.up_conv._forward_nograd(mid))
         dil = self.branch_q1[2].dilation[0]
         b1, b2 = self.branch_q1[2], self.branch_q2[2]
         f1 = ops.conv2d(self.branch_q1[0](feat, relu=True), b1.conv_weight(), b1.bias.detach(), pad=dil, dilation=dil, res1=feat)
         f2 = ops.conv2d(self.branch_q2[0](feat, relu=True), b2.conv_weight(), b2.bias.detach(), pad=dil, dilation=dil, res1=feat)
-        Wp, bias = ops.attn_fold(f1, f2, P["aw"], P["fw"], P["fb"])
+        Wp, bias = ops.attn_fold(f1, f2, P["aw"], P["fw"], P["fb"], drop=self._next_drop())
         fused = ops.pw_gemm(f1, Wp, 32, x2=f2, in_mode=2, bias=bias)
         out = ops.conv2d(fused, P["co_w"], P["co_b"], pad=1)
         out = ops.conv2d(out, P["sh_w"], P["sh_b"], pad=1, res1=out)

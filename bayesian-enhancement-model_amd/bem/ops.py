@@ -21,6 +21,9 @@ from .native import PwArgs, check, lib
 from .tables import UIQM_WIDTH, lab_tables, niqe_gamma_table, niqe_resize_table, pil_resize_table, uiqm_resized_rows  # noqa: F401  (host builders; callers of ops.<name> keep working)
 
 
+_U64 = (1 << 64) - 1
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -949,19 +952,38 @@ def hamilton_full(q1, q2):
     return out
 
 
-def attn_fold(f1, f2, attn_w, fuse_w, fuse_b):
-    """Channel cross attention + fuse conv folded into per-image (32x64) weights: returns (Wp (B, x6-packed(32,64)), bias (B,32))."""
+def attn_fold(f1, f2, attn_w, fuse_w, fuse_b, drop=None):
+    """Channel cross attention + fuse conv folded into per-image (32x64) weights: returns (Wp (B, x6-packed(32,64)), bias (B,32)).
+    drop: the attention dropout of QD/model3.py:98,124-131 on the two softmaxed maps, (p, seed, stream_id) for keep flags drawn in the
+    kernel (Philox, bem_attn_fold_drop_f32) or (p, mask) with mask (B,2,32,32) of 0 / 1 values, map 0 = attn_1, map 1 = attn_2."""
     for n, t in (("f1", f1), ("f2", f2), ("attn_w", attn_w), ("fuse_w", fuse_w), ("fuse_b", fuse_b)):
         _chk(t, n)
+    mask = None
+    if drop is not None:
+        if len(drop) == 2:
+            (p, mask), seed, stream_id = drop, 0, 0
+            _chk(mask, "mask")
+        elif len(drop) == 3:
+            p, seed, stream_id = drop
+        else:
+            raise ValueError("attn_fold: drop is (p, seed, stream_id) or (p, mask)")
+        if not 0.0 <= float(p) < 1.0:
+            raise ValueError(f"attn_fold: dropout probability {p} is not in [0, 1)")
     B, C, H, W = f1.shape
     if C != 32 or f2.shape != f1.shape or attn_w.numel() != 8 * (32 * 32 + 32) or fuse_w.numel() != 32 * 64 or fuse_b.numel() != 32:
         raise ValueError("attn_fold: shapes")
+    if mask is not None and tuple(mask.shape) != (B, 2, 32, 32):
+        raise ValueError(f"attn_fold: mask {tuple(mask.shape)} is not (B, 2, 32, 32) = {(B, 2, 32, 32)}")
     L = H * W
     stats = torch.empty(B, 32 * 32 + 64, device=f1.device, dtype=torch.float64)
     check(lib().bem_attn_stats_f64(_p(f1), _p(f2), _p(stats), B, L, _stream()), "attn_stats")
     Wn = torch.empty(B, 32, 64, device=f1.device, dtype=torch.float32)
     bias = torch.empty(B, 32, device=f1.device, dtype=torch.float32)
-    check(lib().bem_attn_fold_f32(_p(stats), _p(attn_w), _p(fuse_w), _p(fuse_b), _p(Wn), _p(bias), B, L, _stream()), "attn_fold")
+    if drop is None:
+        check(lib().bem_attn_fold_f32(_p(stats), _p(attn_w), _p(fuse_w), _p(fuse_b), _p(Wn), _p(bias), B, L, _stream()), "attn_fold")
+    else:
+        check(lib().bem_attn_fold_drop_f32(_p(stats), _p(attn_w), _p(fuse_w), _p(fuse_b), _p(mask), float(p), int(seed) & _U64, int(stream_id) & _U64,
+                                           _p(Wn), _p(bias), B, L, _stream()), "attn_fold_drop")
     return pack_pw_weight(Wn, x6=True), bias
 
 

@@ -90,9 +90,22 @@ __device__ __forceinline__ double mm(const double (*A)[33], const double (*Bm)[3
     return s;
 }
 
+// Attention dropout (QD/model3.py:98,124-131: nn.Dropout(0.1) on both softmaxed maps, live in train() mode).  Everything after the softmax
+// is linear in the map, so the dropout is one factor on the entry thread (i, j) writes to X: keep / (1 - p), in f64.  The keep flag is
+// read from `mask` (B, 2, 32, 32; map 0 = attn_1, map 1 = attn_2; 0 or 1) or, without one, drawn from Philox4x32-10 laid out like
+// philox_normal4: element e = ((b * 2 + br) * 1024 + i * 32 + j) is word e & 3 of counter block e >> 2 under (seed, stream_id),
+// u = (word >> 8) * 2^-24 in [0, 1), kept iff u >= p (compared in f32).  The eval form carries none of it.
+template <bool DROP> struct AttDrop {};
+template <> struct AttDrop<true> {
+    const float* mask;
+    float p;
+    uint64_t seed, stream_id;
+};
+
+template <bool DROP>
 __global__ __launch_bounds__(1024) void attn_fold_kernel(const double* __restrict__ stats, const float* __restrict__ aw,
                                                          const float* __restrict__ fw, const float* __restrict__ fb,
-                                                         float* __restrict__ Wp, float* __restrict__ bias_out, int L) {
+                                                         float* __restrict__ Wp, float* __restrict__ bias_out, int L, const AttDrop<DROP> drop) {
     __shared__ double X[ATT_C][33], Y[ATT_C][33], Z[ATT_C][33], M1[ATT_C][33], M2[ATT_C][33];
     __shared__ double va[ATT_C], vb[ATT_C], c1[ATT_C], c2[ATT_C], rowred[ATT_C];
     const int i = threadIdx.x >> 5, j = threadIdx.x & 31;
@@ -150,7 +163,21 @@ __global__ __launch_bounds__(1024) void attn_fold_kernel(const double* __restric
         __syncthreads();
         const double pr = e / rowred[i];
         __syncthreads();
-        X[i][j] = pr;                              // attn
+        if constexpr (DROP) {
+            const int64_t el = ((int64_t)b * 2 + br) * (ATT_C * ATT_C) + i * ATT_C + j;
+            bool keep;
+            if (drop.mask) {
+                keep = drop.mask[el] != 0.f;
+            } else {
+                uint32_t c[4] = {(uint32_t)(el >> 2), (uint32_t)((uint64_t)(el >> 2) >> 32), (uint32_t)drop.stream_id, (uint32_t)(drop.stream_id >> 32)};
+                philox4x32_10(c, (uint32_t)drop.seed, (uint32_t)(drop.seed >> 32));
+                const uint32_t wd = (el & 2) ? ((el & 1) ? c[3] : c[2]) : ((el & 1) ? c[1] : c[0]);      // selects, not an indexed array
+                keep = (float)(wd >> 8) * (1.0f / 16777216.0f) >= drop.p;
+            }
+            X[i][j] = keep ? pr * (1.0 / (1.0 - (double)drop.p)) : 0.0;   // attn, dropped out
+        } else {
+            X[i][j] = pr;                          // attn
+        }
         Y[i][j] = Wm(mv, i, j);                    // Wv
         Z[i][j] = Wm(mo, i, j);                    // Wo
         __syncthreads();
@@ -212,6 +239,17 @@ extern "C" int bem_attn_fold_f32(const double* stats, const float* attn_w, const
     BEM_REQUIRE(stats && attn_w && fuse_w && fuse_b && Wp_out && bias_out, "attn_fold: null tensor");
     BEM_REQUIRE(B >= 0 && L > 0, "attn_fold: bad shape");
     if (B == 0) return BEM_OK;
-    attn_fold_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(stats, attn_w, fuse_w, fuse_b, Wp_out, bias_out, L);
+    attn_fold_kernel<false><<<B, 1024, 0, (hipStream_t)stream>>>(stats, attn_w, fuse_w, fuse_b, Wp_out, bias_out, L, AttDrop<false>{});
     return bem_check_launch("attn_fold");
+}
+
+extern "C" int bem_attn_fold_drop_f32(const double* stats, const float* attn_w, const float* fuse_w, const float* fuse_b, const float* mask,
+                                      float p, uint64_t seed, uint64_t stream_id, float* Wp_out, float* bias_out, int B, int L, void* stream) {
+    BEM_REQUIRE(stats && attn_w && fuse_w && fuse_b && Wp_out && bias_out, "attn_fold_drop: null tensor");
+    BEM_REQUIRE(B >= 0 && L > 0, "attn_fold_drop: bad shape");
+    BEM_REQUIRE(p >= 0.f && p < 1.f, "attn_fold_drop: p must be in [0, 1)");
+    if (B == 0) return BEM_OK;
+    attn_fold_kernel<true><<<B, 1024, 0, (hipStream_t)stream>>>(stats, attn_w, fuse_w, fuse_b, Wp_out, bias_out, L,
+                                                                 AttDrop<true>{mask, p, seed, stream_id});
+    return bem_check_launch("attn_fold_drop");
 }

@@ -269,6 +269,15 @@ int bem_attn_fold_f32(const double* stats, const float* attn_w /* 8 x (32x32 + 3
                       const float* fuse_w /* (32,64) */, const float* fuse_b /* (32) */,
                       float* W_out /* (B, 32, 64) */, float* bias_out /* (B,32) */, int B, int L,
                       void* stream);
+/* Step 2 with the attention dropout of QD/model3.py:98,124-131 (nn.Dropout(0.1) on attn_1 and attn_2 after the softmax, live in train()
+ * mode): every softmaxed entry is multiplied by keep / (1 - p) in f64 before the fold, which is linear in the maps.  keep comes from
+ * `mask` (B, 2, 32, 32) of 0 / 1 values, map 0 = attn_1 and map 1 = attn_2, or, with mask NULL, from Philox4x32-10 under
+ * (seed, stream_id): element e = ((b * 2 + map) * 1024 + i * 32 + j) is word e & 3 of counter block e >> 2 (the layout of the weight
+ * sampler), u = (word >> 8) * 2^-24, kept iff u >= p in f32.  0 <= p < 1; p = 0 without a mask gives bem_attn_fold_f32's result bit
+ * for bit. */
+int bem_attn_fold_drop_f32(const double* stats, const float* attn_w, const float* fuse_w, const float* fuse_b,
+                           const float* mask_or_null, float p, uint64_t seed, uint64_t stream_id,
+                           float* W_out, float* bias_out, int B, int L, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout / resampling helpers.
