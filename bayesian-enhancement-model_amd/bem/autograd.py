@@ -185,7 +185,7 @@ def _vgg_walk(vgg, x, keep=None, rows=None):
     feats = {}
     for i, n in enumerate(names):
         if n.startswith("conv"):
-            cw, bias, _ = w[n]
+            cw, bias = w[n]
             has_relu = i + 1 < len(names)
             if n in want:
                 feats[n] = pre = ops.conv2d(x, cw, bias, relu=False)
@@ -266,7 +266,7 @@ class PerceptualFn(Function):
                 if n in feats:
                     gf = dfeat(n)
                     d = gf if d is None else ops.add(d, gf)
-                d, masked = ops.conv2d(d, w[n][2], None), False
+                d, masked = ops.conv2d(d, w[n][0].input_grad(), None), False
         return ops.vgg_prep_bwd(d, B, vgg.use_input_norm, vgg.range_norm), None, None
 
 
@@ -311,19 +311,19 @@ class LPIPSFn(Function):
     def backward(ctx, g):
         mod, (H, W), ys = ctx.mod, ctx.hw, ctx.saved_tensors
         net, B = mod.lpips, ys[0].shape[0] // 2
-        wb_, pads = net.conv_operands_bwd(), [p for _, _, p in net.conv_operands()]
+        cw = net.conv_operands()
         gmul, scale = g.reshape(1).contiguous().float(), float(mod.loss_weight) / B
         gin = None
         for i in (4, 3, 2, 1):
             d = ops.lpips_layer_bwd(ys[i], getattr(net, f"lin{i}"), gin, gmul, scale)
-            gin = ops.conv2d(d, wb_[i], None, pad=pads[i])
+            gin = ops.conv2d(d, cw[i][0].input_grad(), None, pad=cw[i][2])
             if i <= 2:                                               # conv2 and conv3 read a pooled feature
                 gin = ops.relu_pool3s2_bwd(ys[i - 1][B:], gin)
         # layer 0 is a crop of conv1's block grid: its gradient goes back into the whole grid, zero around the crop
         Ho, Wo = ops.lpips_conv1_hw(H, W)
         d = torch.empty(B, ys[0].shape[1], Ho + 2, (Wo + 3) // 2 * 2, device=gin.device, dtype=torch.float32)
         ops.lpips_layer_bwd(ys[0], net.lin0, gin, gmul, scale, out=d, origin=(1, 1))
-        return ops.lpips_prep_bwd(ops.conv2d(d, wb_[0], None, pad=pads[0]), H, W, normalize=mod.normalize), None, None
+        return ops.lpips_prep_bwd(ops.conv2d(d, cw[0][0].input_grad(), None, pad=cw[0][2]), H, W, normalize=mod.normalize), None, None
 
 
 def lpips_loss(pred, gt, mod):
@@ -405,10 +405,6 @@ class ConvT2x2Fn(Function):
 # ------------------------------------------------------------------------------------------------------------------
 # dense convolutions (3x3 stride 1 pad 1; 4x4 stride 2 pad 1)
 # ------------------------------------------------------------------------------------------------------------------
-def _wflip3(w):
-    return w.detach().flip(2, 3).transpose(0, 1).contiguous()          # (Cin, Cout, 3, 3): correlation with the flipped kernel
-
-
 def _wT4(w):
     """Input gradient of the 4x4 stride-2 pad-1 convolution as a 3x3 convolution over dout producing 4*Cin phase channels
     (PixelShuffle order ci*4 + py*2 + px), then pixel_shuffle2."""
@@ -448,7 +444,7 @@ class Conv2dFn(Function):
                 raise NotImplementedError("Conv2dFn: input gradient of a channel-sliced input")
             k = tuple(w.shape[2:])
             if (k, s, p) == ((3, 3), 1, 1):
-                dx = ops.conv2d(dout, ops.derived(h).get("flip", [w], lambda: ops.ConvWeight(_wflip3(w))), None, stride=1, pad=1)
+                dx = ops.conv2d(dout, h.conv_weight().input_grad(), None, stride=1, pad=1)     # correlation with the flipped kernel
             elif (k, s, p) == ((4, 4), 2, 1):
                 d4 = ops.conv2d(dout, ops.derived(h).get("T4", [w], lambda: ops.ConvWeight(_wT4(w))), None, stride=1, pad=1)
                 dx = ops.pixel_shuffle2(d4)

@@ -113,30 +113,22 @@ class LPIPS(nn.Module):
                                      persistent=False)
             self.register_buffer(f"lin{i}", lin_state_dict[f"lin{i}.model.1.weight"].detach().to(torch.float32).reshape(-1).contiguous().clone(),
                                  persistent=False)
-        self._ops = self._ops_bwd = None
+        self._ops = None
         self.eval()
 
     def _apply(self, fn, *a, **k):
-        self._ops = self._ops_bwd = None   # the operand forms below belong to the buffers they were packed from
+        self._ops = None                   # the operand forms below belong to the buffers they were packed from
         return super()._apply(fn, *a, **k)
 
     def conv_operands(self):
         """[(ConvWeight, bias, pad)] per convolution, conv1 in its block form; packed on first use and held for the life of the module (the
-        weights are frozen, so nothing invalidates a packed form)."""
+        weights are frozen, so nothing invalidates a packed form).  The input gradient of a convolution is ops.conv2d(d, its ConvWeight's
+        input_grad(), None, pad=its pad); conv1's comes from its block form ((64,48,3,3) -> (48,64,3,3))."""
         if self._ops is None:
             with torch.no_grad():
                 self._ops = [(ops.ConvWeight(conv1_block_weight(self.conv0_weight) if i == 0 else getattr(self, f"conv{i}_weight")),
                               getattr(self, f"conv{i}_bias"), 1 if i == 0 else c[5]) for i, c in enumerate(ALEX_CONVS)]
         return self._ops
-
-    def conv_operands_bwd(self):
-        """[ConvWeight] per convolution for its input gradient: the weight flipped along both taps and transposed, conv1's from its block
-        form ((64,48,3,3) -> (48,64,3,3)); the gradient is ops.conv2d(d, this, None, pad=conv_operands' pad).  Held like the forward forms."""
-        if self._ops_bwd is None:
-            with torch.no_grad():
-                self._ops_bwd = [ops.ConvWeight((conv1_block_weight(self.conv0_weight) if i == 0 else getattr(self, f"conv{i}_weight"))
-                                                .flip(2, 3).transpose(0, 1).contiguous()) for i in range(len(ALEX_CONVS))]
-        return self._ops_bwd
 
     def features(self, xs, H, W):
         """The five ReLU outputs for the block-form input of ops.lpips_prep; the first is a crop of conv1's block grid (a view, not a copy)."""

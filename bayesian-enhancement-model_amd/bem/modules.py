@@ -111,7 +111,7 @@ class DwConv2d(nn.Conv2d):
 
 
 class Conv2dK(nn.Conv2d):
-    """Dense conv (3x3 s1 p1 or 4x4 s2 p1) on the direct-conv kernel."""
+    """Dense conv through ops.conv2d (holder); ops.conv2d_route names the kernel form a call takes."""
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)

@@ -396,7 +396,7 @@ def transpose_planes_into(src, dst, dst_c0):
 # --------------------------------------------------------------------------- pointwise GEMM ---
 # Two packed operand formats: "x6" (three bf16 limbs per f32 value, six limb products on v_mfma_f32_32x32x16_bf16, bem_pw_gemm_x6_f32 --
 # f32-level error at 6/16 of the f32 matrix-pipe cost), what every pointwise GEMM consumes; and "f32" (v_mfma_f32_32x32x2_f32 operand
-# order, pack_pw_weight(x6=False)), the weight format of the implicit-GEMM convolutions (bem_conv2d_mfma_f32).
+# order, pack_pw_weight(x6=False)), the weight format of the implicit-GEMM convolutions (ConvWeight.f32).
 # Bumped whenever parameters are rewritten behind torch's back (the fused optimizer step, bem.train.BemAdamW): every Derived
 # cache (packed / transposed / flipped copies of weights) is keyed on it as well as on the tensors' data_ptr / _version.
 WEIGHT_EPOCH = [0]
@@ -759,30 +759,42 @@ def dwconv3x3(x, w, bias=None, mode=0):
     return out
 
 
+# Which kernel form takes a dense convolution is the library's decision (bem_conv2d_route; its comment in bem_hip.h is the route table).  These two
+# constants only build its `allow` argument: tests and scripts/lpips_rate.py clear one to reach the kernels that stand behind the x6 / f32-MFMA forms.
 USE_CONV_MFMA = True
 USE_CONV_X6 = True
-# 4x4 stride-2 convs take the coalesced-row x6 kernel (conv_x6.hip) where bem_conv4x4s2_fast_supported allows, the f32-MFMA im2col kernel otherwise
 
 
 class ConvWeight:
     """A dense-conv weight (Cout, Cin, KH, KW) and the operand forms conv2d's matrix-core kernels read, each packed on first request and
     kept as long as this object.  Whoever owns the weight keeps the ConvWeight (modules.Conv2dK.conv_weight: in its Derived cache)."""
 
-    def __init__(self, w):
-        self.w, self._x6, self._f32 = w, None, None
+    def __init__(self, w, input_grad=None):
+        self.w, self._x6, self._f32, self._grad = w, None, None, input_grad      # input_grad: given where it is not the flip of w itself
 
     def x6(self):
-        """(KH*KW taps, x6-packed (Cout, Cin)), tap = ky * KW + kx: the shifted-tap 3x3 and the coalesced-row 4x4 convolutions."""
+        """(KH*KW taps, x6-packed (Cout, Cin)), tap = ky * KW + kx: the row and the shifted-tap forms."""
         if self._x6 is None:
             w = self.w
             self._x6 = pack_pw_weight(w.permute(2, 3, 0, 1).reshape(w.shape[2] * w.shape[3], w.shape[0], w.shape[1]).contiguous(), x6=True)
         return self._x6
 
     def f32(self):
-        """Packed (Cout, Cin*KH*KW) f32 operand of the implicit-GEMM convolution (bem_conv2d_mfma_f32)."""
+        """Packed (Cout, Cin*KH*KW) f32 operand of the implicit-GEMM form."""
         if self._f32 is None:
             self._f32 = pack_pw_weight(self.w.reshape(self.w.shape[0], -1).contiguous(), x6=False)
         return self._f32
+
+    def input_grad(self):
+        """ConvWeight of a stride-1 convolution's input gradient (taps flipped, channel axes swapped): dx = conv2d(dy, this, None, pad=K - 1 - pad)."""
+        if self._grad is None:
+            self._grad = ConvWeight(self.w.flip(2, 3).transpose(0, 1).contiguous())
+        return self._grad
+
+
+# BEM_CONV_* of bem_hip.h -> the form's name and the operand form of the weight its kernel reads
+_CONV_FORMS = {1: ("rows", ConvWeight.x6), 2: ("taps", ConvWeight.x6), 3: ("mfma", ConvWeight.f32), 4: ("direct", lambda cw: cw.w)}
+_CONV_ROUTES = {}           # bem_conv2d_route's answers, by everything it reads
 
 
 def _conv_out_hw(H, W, KH, KW, stride, pad, dilation=1):
@@ -797,14 +809,10 @@ def _conv2d_cost(x, w, stride, pad, res1, res2, dilation, **_):
     return 4.0 * B * (Ci * H * W + Co * Ho * Wo * (1 + nres)) + 4.0 * Co * Ci * KH * KW, 2.0 * B * Co * Ci * KH * KW * Ho * Wo
 
 
-@_bracket(_conv2d_cost)
-def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
-    """Dense conv.  ``cin_slice=(c0, Cin)`` convolves channels [c0, c0+Cin) of a wider contiguous x.
-    ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
-    Runs as an implicit GEMM on the matrix cores (Cout <= 160), else on the direct VALU kernel.
-    dilation 2 (3x3, pad 2) and 3x3 stride 2 exist in the shifted-tap form only (QD model2 / model3).
-    5x5 stride 1 (LPIPS conv2) exists for Cin % 8 == 0: 25 shifted taps where the width is even and pad is 2, the direct kernel otherwise.
-    ``w``: a ConvWeight, whose packed forms are reused, or a plain (Cout, Cin, KH, KW) tensor, packed for this call alone."""
+def _conv2d_ask(x, w, bias, stride, pad, res1, res2, cin_slice, dilation, res1_rep):
+    """conv2d's operand check and its question to bem_conv2d_route -> (BEM_CONV_* form, ConvWeight, (pointer, batch stride) of the sliced x, output
+    shape); a convolution no kernel takes raises the library's reason.  out, conv2d's own allocation, is NULL to the route.  The route reads a pointer's
+    low four bits only, so _CONV_ROUTES keeps the answer per argument tuple (asking costs 2 us of host time, in every launch-bound step)."""
     cw = w if isinstance(w, ConvWeight) else ConvWeight(w)
     w = cw.w
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias", optional=True)
@@ -818,50 +826,42 @@ def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, c
             raise ValueError("conv2d: channel slice out of range")
     elif Ct != Cin:
         raise ValueError(f"conv2d: input has {Ct} channels, weight expects {Cin}")
-    Ho, Wo = _conv_out_hw(H, W, KH, KW, stride, pad, dilation)
-    out = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=x.dtype)
-    res1_rep = int(res1_rep)
-    if res1_rep < 1 or (res1_rep != 1 and res1 is None):
-        raise ValueError("conv2d: res1_rep must be >= 1 and needs res1")
-    xp, xbs = _pslice(x, c0)
-    res_shapes = (("res1", res1, (B // res1_rep if B % res1_rep == 0 else -1,) + tuple(out.shape[1:])), ("res2", res2, tuple(out.shape)))
-    if dilation != 1 or (KH, KW, stride) == (3, 3, 2):
-        if (KH, KW) != (3, 3) or pad != dilation or Wo % 2 or Cin % 8 or (c0 * H * W) % 2:
-            raise ValueError("conv2d: dilated / strided 3x3 convolutions run in the tap form only (pad = dilation, even output width, Cin % 8 == 0)")
-        for n, r, shp in res_shapes:
-            if r is not None and tuple(r.shape) != shp:
-                raise ValueError(f"conv2d: {n} shape")
-        check(lib().bem_conv_taps_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 3, stride,
-                                         dilation, int(relu), res1_rep, _stream()), "conv_taps_x6")
-        return out
-    for n, r, shp in res_shapes:
-        if r is not None and tuple(r.shape) != shp:
-            raise ValueError(f"conv2d: {n} shape")
     if bias is not None and bias.shape != (Cout,):
         raise ValueError("conv2d: bias shape")
-    if USE_CONV_X6 and (KH, KW, stride, pad) == (3, 3, 1, 1) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
-        # nine shifted 1x1 taps on the bf16-limb GEMM machinery (conv_x6.hip)
-        check(lib().bem_conv3x3_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
-                                       Cout, int(relu), res1_rep, _stream()), "conv3x3_x6")
-        return out
-    if USE_CONV_X6 and (KH, KW, stride, pad) == (5, 5, 1, 2) and W % 2 == 0 and Cin % 8 == 0 and (c0 * H * W) % 2 == 0:
-        # 25 shifted 1x1 taps on the same machinery (LPIPS conv2); odd widths: the direct kernel at the end
-        check(lib().bem_conv_taps_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, 5, 1, 1, int(relu),
-                                         res1_rep, _stream()), "conv_taps_x6")
-        return out
-    conv4_fast = (KH, KW, stride, pad) == (4, 4, 2, 1) and res1 is None and res2 is None and (c0 * H * W) % 4 == 0 \
-        and xbs % 4 == 0 and x.data_ptr() % 16 == 0 and lib().bem_conv4x4s2_fast_supported(Cin, H, W) == 1
-    if conv4_fast:
-        # the coalesced-row form (conv_x6.hip; power-of-two output widths <= 64); other shapes: the f32-MFMA implicit GEMM below
-        check(lib().bem_conv4x4s2_x6_f32(xp, xbs, _p(cw.x6()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
-                                         Cout, int(relu), _stream()), "conv4x4s2_x6")
-        return out
-    if USE_CONV_MFMA and Cout <= 160 and ((KH, KW, stride) in ((3, 3, 1), (4, 4, 2))):
-        check(lib().bem_conv2d_mfma_f32(xp, xbs, _p(cw.f32()), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W,
-                                        Cout, KH, KW, stride, pad, int(relu), res1_rep, _stream()), "conv2d_mfma")
-        return out
-    check(lib().bem_conv2d_f32(xp, xbs, _p(w), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW,
-                               stride, pad, int(relu), res1_rep, _stream()), "conv2d")
+    if res1_rep < 1 or (res1_rep != 1 and res1 is None):
+        raise ValueError("conv2d: res1_rep must be >= 1 and needs res1")
+    oshape = (B, Cout) + _conv_out_hw(H, W, KH, KW, stride, pad, dilation)
+    for n, r, shp in (("res1", res1, (B // res1_rep if B % res1_rep == 0 else -1,) + oshape[1:]), ("res2", res2, oshape)):
+        if r is not None and tuple(r.shape) != shp:
+            raise ValueError(f"conv2d: {n} shape")
+    xs = _pslice(x, c0)
+    key = (Cout, Cin, KH, KW, H, W, xs[1], stride, pad, dilation, USE_CONV_X6, USE_CONV_MFMA, (xs[0].value or 0) & 15,
+           None if res1 is None else res1.data_ptr() & 15, None if res2 is None else res2.data_ptr() & 15)
+    form = _CONV_ROUTES.get(key) or _CONV_ROUTES.setdefault(key, lib().bem_conv2d_route(
+        *xs, _p(res1), _p(res2), None, Cin, H, W, Cout, KH, KW, stride, pad, dilation, USE_CONV_X6 | 2 * USE_CONV_MFMA))
+    if form == 0:
+        raise native.BemNativeError(lib().bem_last_error().decode())
+    return form, cw, xs, oshape
+
+
+def conv2d_route(x, w, stride=1, pad=1, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
+    """The kernel form conv2d runs for these operands, "rows", "taps", "mfma" or "direct", without running anything."""
+    return _CONV_FORMS[_conv2d_ask(x, w, None, stride, pad, res1, res2, cin_slice, dilation, res1_rep)[0]][0]
+
+
+@_bracket(_conv2d_cost)
+def conv2d(x, w, bias=None, stride=1, pad=1, relu=False, res1=None, res2=None, cin_slice=None, dilation=1, res1_rep=1):
+    """Dense conv.  ``cin_slice=(c0, Cin)`` convolves channels [c0, c0+Cin) of a wider contiguous x.
+    ``res1_rep=n``: res1 has B / n rows and output row b adds res1[b // n] (a per-image term shared by the n samples of an image).
+    Which kernel runs, and which convolutions none takes (BemNativeError): bem_conv2d_route; conv2d_route asks it alone.
+    ``w``: a ConvWeight, whose packed forms are reused, or a plain (Cout, Cin, KH, KW) tensor, packed for this call alone."""
+    res1_rep = int(res1_rep)
+    form, cw, xs, oshape = _conv2d_ask(x, w, bias, stride, pad, res1, res2, cin_slice, dilation, res1_rep)
+    out = torch.empty(oshape, device=x.device, dtype=x.dtype)
+    name, operand = _CONV_FORMS[form]
+    (B, _, H, W), (Cout, Cin, KH, KW) = x.shape, cw.w.shape
+    check(lib().bem_conv2d_f32(form, *xs, _p(operand(cw)), _p(bias), _p(res1), _p(res2), _p(out), B, Cin, H, W, Cout, KH, KW, stride, pad, dilation,
+                               int(relu), res1_rep, _stream()), "conv2d " + name)
     return out
 
 

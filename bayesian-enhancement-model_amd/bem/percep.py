@@ -83,8 +83,8 @@ class VGGFeatureExtractor(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def conv_operands(self):
-        """{conv name: (forward ConvWeight, bias, ConvWeight of the flipped, transposed weight for the input gradient)}, made on first
-        use and held here for the life of the module: the weights are frozen, so no optimizer step invalidates a packed form."""
+        """{conv name: (ConvWeight, bias)}, made on first use and held here for the life of the module: the weights are frozen, so no
+        optimizer step invalidates a packed form.  The input gradients read ConvWeight.input_grad()."""
         if self._ops is None:
             with torch.no_grad():
                 d = {}
@@ -92,11 +92,12 @@ class VGGFeatureExtractor(nn.Module):
                     if not n.startswith("conv"):
                         continue
                     w = getattr(self, n + "_weight")
-                    wf = w
-                    if n == "conv1_1":           # eight input channels (five of zeros): the Cin % 8 == 0 matrix-core route
+                    cw = ops.ConvWeight(w)
+                    if n == "conv1_1":           # eight input channels (five of zeros): the Cin % 8 == 0 matrix-core route; its gradient weight is the 3-channel one
                         wf = torch.zeros(w.shape[0], 8, 3, 3, device=w.device, dtype=w.dtype)
                         wf[:, :3] = w
-                    d[n] = (ops.ConvWeight(wf), getattr(self, n + "_bias"), ops.ConvWeight(w.flip(2, 3).transpose(0, 1).contiguous()))
+                        cw = ops.ConvWeight(wf, input_grad=cw.input_grad())
+                    d[n] = (cw, getattr(self, n + "_bias"))
                 self._ops = d
         return self._ops
 

@@ -1,6 +1,7 @@
-// Spatial convolutions: depthwise 3x3 (with fused SiLU / gated-GELU / PostSmooth epilogues) and a
-// dense direct convolution (3x3 s1, 4x4 s2, ...) staged through LDS.
+// Spatial convolutions: depthwise 3x3 (with fused SiLU / gated-GELU / PostSmooth epilogues), the dense convolution's direct and f32-MFMA
+// forms, both staged through LDS, and at the end of the file its route table (bem_conv2d_route) and one entry (bem_conv2d_f32).
 #include "bem_common.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -605,57 +606,89 @@ extern "C" int bem_dwconv3x3_f32(const float* x, const float* w, int64_t w_bstri
     return bem_check_launch("dwconv3x3");
 }
 
-extern "C" int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w, const float* bias,
-                              const float* res1, const float* res2, float* out, int B, int Cin, int H, int W,
-                              int Cout, int KH, int KW, int stride, int pad, int relu, int res1_rep, void* stream) {
-    BEM_REQUIRE(x && w && out && res1_rep >= 1, "conv2d: null tensor or res1_rep < 1");
-    BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv2d: bad shape");
+// The two forms that stage input patches in LDS, behind one set of checks: the f32-MFMA implicit GEMM (w packed, Cout <= 160) and the direct kernel.
+static int conv_patch_launch(bool mfma, const float* x, int64_t x_bstride, const float* w, const float* bias, const float* res1, const float* res2,
+                             float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu, int res1_rep, void* stream) {
+    const char* what = mfma ? "conv2d_mfma" : "conv2d";
+    const bool k31 = KH == 3 && KW == 3 && stride == 1, k42 = KH == 4 && KW == 4 && stride == 2;
+    const bool k51 = !mfma && KH == 5 && KW == 5 && stride == 1 && Cin % 8 == 0;       // the channel counts the 5x5 tap form takes at even widths: this is its odd-width half
+    BEM_REQUIRE(x && w && out && res1_rep >= 1, "%s: null tensor or res1_rep < 1", what);
+    BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && (!mfma || Cout <= 160) && H > 0 && W > 0, "%s: bad shape%s", what, mfma ? " (Cout <= 160)" : "");
+    BEM_REQUIRE(k31 || k42 || k51, "%s: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2%s)", what, KH, KW, stride, mfma ? "" : ", and 5x5 s1 for Cin % 8 == 0");
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    BEM_REQUIRE(Ho > 0 && Wo > 0, "conv2d: empty output");
+    BEM_REQUIRE(Ho > 0 && Wo > 0, "%s: empty output", what);
     if (B == 0) return BEM_OK;
-    const int tilesX = cdiv(Wo, TW), tilesY = cdiv(Ho, TH);
-    dim3 grid(tilesX * tilesY, cdiv(Cout, COB), B);
+    const int tilesX = cdiv(Wo, TW), tiles = tilesX * cdiv(Ho, TH), KS = cdiv(Cin * KH * KW, 2), MT = cdiv(Cout, 32);
     hipStream_t s = (hipStream_t)stream;
-    if (KH == 3 && KW == 3 && stride == 1)
-        conv2d_kernel<3, 3, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
-    else if (KH == 4 && KW == 4 && stride == 2)
-        conv2d_kernel<4, 4, 2><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
-    else if (KH == 5 && KW == 5 && stride == 1 && Cin % 8 == 0)       // the channel counts the 5x5 tap form takes at even widths: this is its odd-width half
-        conv2d_kernel<5, 5, 1><<<grid, 256, 0, s>>>(x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, res1_rep);
-    else
-        BEM_REQUIRE(false, "conv2d: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2, and 5x5 s1 for Cin %% 8 == 0)", KH, KW, stride);
-    return bem_check_launch("conv2d");
+#define BEM_CONV_ARGS x, x_bstride, w, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX
+#define BEM_DIRECT(KH_, KW_, S_) conv2d_kernel<KH_, KW_, S_><<<dim3(tiles, cdiv(Cout, COB), B), 256, 0, s>>>(BEM_CONV_ARGS, res1_rep)
+#define BEM_MFMA(KERNEL, KH_, KW_, S_, MTW_) KERNEL<KH_, KW_, S_, MTW_><<<dim3(tiles, B), 256, 0, s>>>(BEM_CONV_ARGS, KS, res1_rep)
+    if (!mfma) {
+        if (k31) BEM_DIRECT(3, 3, 1);
+        else if (k42) BEM_DIRECT(4, 4, 2);
+        else BEM_DIRECT(5, 5, 1);
+    } else if (k31) {
+        if (MT == 1) BEM_MFMA(conv2d_mfma_pipe_kernel, 3, 3, 1, 1);
+        else if (MT == 2) BEM_MFMA(conv2d_mfma_pipe_kernel, 3, 3, 1, 2);
+        else if (MT == 3) BEM_MFMA(conv2d_mfma_kernel, 3, 3, 1, 3);
+        else BEM_MFMA(conv2d_mfma_kernel, 3, 3, 1, 5);
+    } else {
+        if (MT == 1) BEM_MFMA(conv2d_mfma_kernel, 4, 4, 2, 1);
+        else if (MT == 2) BEM_MFMA(conv2d_mfma_kernel, 4, 4, 2, 2);
+        else if (MT == 3) BEM_MFMA(conv2d_mfma_kernel, 4, 4, 2, 3);
+        else BEM_MFMA(conv2d_mfma_kernel, 4, 4, 2, 5);
+    }
+#undef BEM_MFMA
+#undef BEM_DIRECT
+#undef BEM_CONV_ARGS
+    return bem_check_launch(what);
 }
 
-extern "C" int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias,
-                                   const float* res1, const float* res2, float* out, int B, int Cin, int H, int W,
-                                   int Cout, int KH, int KW, int stride, int pad, int relu, int res1_rep, void* stream) {
-    BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "conv2d_mfma: null tensor or res1_rep < 1");
-    BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && Cout <= 160 && H > 0 && W > 0, "conv2d_mfma: bad shape (Cout <= 160)");
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    BEM_REQUIRE(Ho > 0 && Wo > 0, "conv2d_mfma: empty output");
-    if (B == 0) return BEM_OK;
-    const int tilesX = cdiv(Wo, TW), tilesY = cdiv(Ho, TH);
-    const int KS = cdiv(Cin * KH * KW, 2), MT = cdiv(Cout, 32);
-    dim3 grid(tilesX * tilesY, B);
-    hipStream_t s = (hipStream_t)stream;
-#define BEM_CONV_LAUNCH(KH_, KW_, S_, MTW_) \
-    conv2d_mfma_kernel<KH_, KW_, S_, MTW_><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep)
-    if (KH == 3 && KW == 3 && stride == 1) {
-        if (MT <= 2) {
-            if (MT == 1) conv2d_mfma_pipe_kernel<3, 3, 1, 1><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
-            else conv2d_mfma_pipe_kernel<3, 3, 1, 2><<<grid, 256, 0, s>>>(x, x_bstride, Wp, bias, res1, res2, out, Cin, H, W, Cout, Ho, Wo, pad, relu, tilesX, KS, res1_rep);
-        }
-        else if (MT == 3) BEM_CONV_LAUNCH(3, 3, 1, 3);
-        else BEM_CONV_LAUNCH(3, 3, 1, 5);
-    } else if (KH == 4 && KW == 4 && stride == 2) {
-        if (MT == 1) BEM_CONV_LAUNCH(4, 4, 2, 1);
-        else if (MT == 2) BEM_CONV_LAUNCH(4, 4, 2, 2);
-        else if (MT == 3) BEM_CONV_LAUNCH(4, 4, 2, 3);
-        else BEM_CONV_LAUNCH(4, 4, 2, 5);
-    } else {
-        BEM_REQUIRE(false, "conv2d_mfma: unsupported kernel %dx%d stride %d (have 3x3 s1, 4x4 s2)", KH, KW, stride);
+extern "C" int bem_conv2d_route(const float* x, int64_t x_bstride, const float* res1, const float* res2, const float* out,
+                                int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int dilation, int allow) {
+#define BEM_REFUSE(...) do { snprintf(bem_err_buf, sizeof(bem_err_buf), __VA_ARGS__); return 0; } while (0)
+    if (Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) BEM_REFUSE("conv2d: bad shape");
+    const bool k31 = KH == 3 && stride == 1, k32 = KH == 3 && stride == 2, k42 = KH == 4 && stride == 2, k51 = KH == 5 && stride == 1;
+    // The route table: the first row that matches decides (the comment of bem_conv2d_route in bem_hip.h is its only other statement).
+    // 0  not square, (K, stride) none of (3,1) (3,2) (4,2) (5,1), or a dilation other than 1 / 2: refused
+    if (KH != KW || !(k31 || k32 || k42 || k51) || (dilation != 1 && dilation != 2))
+        BEM_REFUSE("conv2d: no kernel for %dx%d stride %d dilation %d (have 3x3 s1 / s2, 4x4 s2, 5x5 s1; dilation 1 or 2)", KH, KW, stride, dilation);
+    const int Wo = (W + 2 * pad - dilation * (KH - 1) - 1) / stride + 1;
+    const bool cin8 = Cin % 8 == 0, x8 = ((uintptr_t)x & 7) == 0;
+    // 1  dilated, or 3x3 stride 2: the tap form or nothing (QD model2 / model3); the allow bits do not apply
+    if (dilation != 1 || k32) {
+        if (KH == 3 && pad == dilation && !(stride == 2 && dilation == 2) && Wo % 2 == 0 && cin8 && x8) return BEM_CONV_TAPS;
+        BEM_REFUSE("conv2d: dilated / strided 3x3 convolutions run in the tap form only (pad = dilation, even output width, Cin %% 8 == 0, "
+                   "x 8-byte aligned; got %dx%d stride %d pad %d dilation %d, Wo=%d Cin=%d)", KH, KW, stride, pad, dilation, Wo, Cin);
     }
-#undef BEM_CONV_LAUNCH
-    return bem_check_launch("conv2d_mfma");
+    const bool x6 = (allow & BEM_CONV_ALLOW_X6) && W % 2 == 0 && cin8 && x8;
+    // 2  3x3 s1 p1 on the x6 matrix cores: rows for W a power of two in 4 .. 128 with x, out and the residuals on 16 bytes, else nine taps
+    if (k31 && pad == 1 && x6) return conv_rows_shape(3, Cin, H, W) && conv_rows_aligned(x, x_bstride, out, res1, res2) ? BEM_CONV_ROWS : BEM_CONV_TAPS;
+    // 3  5x5 s1 p2 (LPIPS conv2) at even widths: 25 taps
+    if (k51 && pad == 2 && x6) return BEM_CONV_TAPS;
+    // 4  4x4 s2 p1 without residuals, even H and W, Wo a power of two in 2 .. 64, x on 16 bytes: rows; the allow bits do not apply
+    if (k42 && pad == 1 && !res1 && !res2 && conv_rows_shape(4, Cin, H, W) && conv_rows_aligned(x, x_bstride, nullptr, nullptr, nullptr)) return BEM_CONV_ROWS;
+    // 5  the f32-MFMA implicit GEMM, any padding
+    if ((allow & BEM_CONV_ALLOW_MFMA) && Cout <= 160 && (k31 || k42)) return BEM_CONV_MFMA;
+    // 6  the direct kernel; its 5x5 is the odd-width half of row 3
+    if (k31 || k42 || (k51 && cin8)) return BEM_CONV_DIRECT;
+    BEM_REFUSE("conv2d: 5x5 convolutions need Cin %% 8 == 0 (got %d)", Cin);
+#undef BEM_REFUSE
+}
+
+extern "C" int bem_conv2d_f32(int form, const float* x, int64_t x_bstride, const float* w, const float* bias, const float* res1, const float* res2,
+                              float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int dilation, int relu,
+                              int res1_rep, void* stream) {
+    // a forced form is checked by its launcher; what a launcher's arguments cannot say is checked here
+    BEM_REQUIRE(form >= BEM_CONV_ROWS && form <= BEM_CONV_DIRECT && KH == KW, "conv2d: form %d (bem_conv2d_route gives it) or a %dx%d kernel", form, KH, KW);
+    switch (form) {
+    case BEM_CONV_ROWS:
+        BEM_REQUIRE(((KH == 3 && stride == 1) || (KH == 4 && stride == 2)) && pad == 1 && dilation == 1, "conv2d: the row form takes 3x3 s1 p1 and 4x4 s2 p1");
+        return conv_rows_launch(KH, x, x_bstride, w, bias, res1, res2, out, B, Cin, H, W, Cout, relu, res1_rep, stream);
+    case BEM_CONV_TAPS:
+        return conv_taps_launch(x, x_bstride, w, bias, res1, res2, out, B, Cin, H, W, Cout, KH, stride, pad, dilation, relu, res1_rep, stream);
+    default:
+        BEM_REQUIRE(dilation == 1, "conv2d: dilation %d exists in the tap form only", dilation);
+        return conv_patch_launch(form == BEM_CONV_MFMA, x, x_bstride, w, bias, res1, res2, out, B, Cin, H, W, Cout, KH, KW, stride, pad, relu, res1_rep, stream);
+    }
 }

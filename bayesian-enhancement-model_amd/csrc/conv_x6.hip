@@ -1,6 +1,6 @@
-// Dense convolutions on the bf16-limb (x6) matrix cores, two forms behind bem_conv3x3_x6_f32 / bem_conv4x4s2_x6_f32 / bem_conv_taps_x6_f32
-// (dispatch at the end of the file): the row form (conv_rows_x6_kernel, below) where the shape allows, shifted 1x1 taps (conv_taps_x6_kernel,
-// second half) otherwise.  Limb arithmetic and operand layout: x6_common.h and the header of pw_gemm_x6.hip.
+// Dense convolutions on the bf16-limb (x6) matrix cores, the forms BEM_CONV_ROWS and BEM_CONV_TAPS of bem_conv2d_f32 (which shape takes
+// which: bem_conv2d_route, conv.hip): the row form (conv_rows_x6_kernel, below) and shifted 1x1 taps (conv_taps_x6_kernel, second half).
+// Limb arithmetic and operand layout: x6_common.h and the header of pw_gemm_x6.hip.
 //
 // Row form: the 4x4 stride-2 pad-1 down-sampling convs of
 // the U-Nets (DecompDualBranchDDWavelet_arch.py:40-41) and the 3x3 stride-1 pad-1 convs of the decomposition nets and the first / last layers
@@ -16,10 +16,10 @@
 //     3 KS MTW 1-KiB operand blocks of a step (k-block, input row) in LDS by LDS-DMA, double-buffered, requested one step ahead.
 //   * the input rows of the next step are requested (into registers) before the matrix work of the current one.
 // One workgroup = 4 waves = 128 NPX consecutive output pixels x MTW row blocks of 32 output channels; two workgroups per CU.
-// Shapes: Wo / NPX (the lanes of an output row) a power of two <= 32, so that no row crosses a half-wave: Wo in {2 .. 64} for the 4x4 stride-2
-// form (W = 2 Wo, H = 2 Ho), W in {4 .. 128} for 3x3; Cin % 8 == 0.  Wp = bem_pack_pw_weight_x6 of the (KS^2, Cout, Cin) tap matrices,
-// tap = KS ky + kx -- the format of bem_conv4x4s2_x6_f32 / bem_conv3x3_x6_f32.
+// Shapes (conv_rows_shape): Wo / NPX (the lanes of an output row) a power of two <= 32, so that no row crosses a half-wave; Cin % 8 == 0.
+// Wp = bem_pack_pw_weight_x6 of the (KS^2, Cout, Cin) tap matrices, tap = KS ky + kx.
 #include "bem_common.h"
+#include "conv_launch.h"
 #include "scan_common.h"
 #include "x6_common.h"
 
@@ -144,13 +144,12 @@ for (int m = 0; m < MTW; ++m)
 
 }  // namespace
 
-// return 1 when the shape is one the row form takes (the callers fall back to the shifted-tap form otherwise)
-extern "C" int bem_conv4x4s2_fast_supported(int Cin, int H, int W) {
-    const int Wo = W / 2;
-    return Cin % 8 == 0 && H % 2 == 0 && W % 2 == 0 && Wo >= 2 && Wo <= 64 && (Wo & (Wo - 1)) == 0;
+bool conv_rows_shape(int KS, int Cin, int H, int W) {
+    const int S = KS == 4 ? 2 : 1, Wo = W / S, lanes = Wo * S / 4;                     // lanes of an output row
+    return Cin > 0 && Cin % 8 == 0 && H > 0 && H % S == 0 && W % S == 0 && lanes >= 1 && lanes <= 32 && (Wo & (Wo - 1)) == 0;
 }
-extern "C" int bem_conv3x3_rows_supported(int Cin, int H, int W) {
-    return Cin % 8 == 0 && H > 0 && W >= 4 && W <= 128 && (W & (W - 1)) == 0;
+bool conv_rows_aligned(const float* x, int64_t x_bstride, const float* out, const float* res1, const float* res2) {
+    return (((uintptr_t)x | (uintptr_t)out | (uintptr_t)res1 | (uintptr_t)res2) & 15) == 0 && x_bstride % 4 == 0;
 }
 
 // KS = 4: the 4x4 stride-2 form; KS = 3: 3x3 stride 1.  Row blocks of output channels in pairs where the registers allow (4x4), singly else.
@@ -159,10 +158,8 @@ int conv_rows_launch(int KS, const float* x, int64_t x_bstride, const float* Wp,
     const char* what = KS == 4 ? "conv4x4s2_x6" : "conv3x3_x6";
     BEM_REQUIRE(x && Wp && out, "%s: null tensor", what);
     BEM_REQUIRE(res1_rep >= 1, "%s: res1_rep %d", what, res1_rep);
-    BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && (KS == 4 ? bem_conv4x4s2_fast_supported(Cin, H, W) : bem_conv3x3_rows_supported(Cin, H, W)),
-                "%s: shape outside the row form", what);
-    BEM_REQUIRE((((uintptr_t)Wp | (uintptr_t)x | (uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 15) == 0 && (x_bstride % 4) == 0,
-                "%s: alignment (x, packed weights, out and residuals 16 bytes)", what);
+    BEM_REQUIRE(B >= 0 && B <= 65535 && Cout > 0 && (KS == 3 || KS == 4) && conv_rows_shape(KS, Cin, H, W), "%s: shape outside the row form", what);
+    BEM_REQUIRE(((uintptr_t)Wp & 15) == 0 && conv_rows_aligned(x, x_bstride, out, res1, res2), "%s: alignment (x, packed weights, out and residuals 16 bytes)", what);
     const int S = KS == 4 ? 2 : 1, Ho = H / S, Wo = W / S;
     BEM_REQUIRE((int64_t)Cout * Ho * Wo < (1ll << 30) && (int64_t)Cin * H * W < (1ll << 30), "%s: plane set too large for 32-bit lane offsets", what);
     if (B == 0) return BEM_OK;
@@ -330,14 +327,14 @@ for (int m = 0; m < MTW; ++m)
 
 }  // namespace
 
-static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                            float* out, int B, int Cin, int H, int W, int Cout, int KH, int stride, int dil, int relu, int res1_rep, void* stream,
-                            const char* what) {
+int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2, float* out,
+                     int B, int Cin, int H, int W, int Cout, int KH, int stride, int pad, int dil, int relu, int res1_rep, void* stream) {
+    const char* what = "conv_taps_x6";
     BEM_REQUIRE(x && Wp && out && res1_rep >= 1, "%s: null tensor or res1_rep < 1", what);
     BEM_REQUIRE(B >= 0 && B <= 65535 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad shape", what);
-    BEM_REQUIRE((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1) || (KH == 5 && stride == 1 && dil == 1),
+    // "same" padding of the (dilated) window; 1 for the strided 3x3
+    BEM_REQUIRE(((KH == 3 && stride == 1 && (dil == 1 || dil == 2)) || (KH == 3 && stride == 2 && dil == 1) || (KH == 5 && stride == 1 && dil == 1)) && pad == dil * (KH - 1) / 2,
                 "%s: supported forms are 3x3 s1 (dilation 1 / 2, padding = dilation), 3x3 s2 p1 and 5x5 s1 p2", what);
-    const int pad = dil * (KH - 1) / 2;                         // "same" padding of the (dilated) window; 1 for the strided 3x3
     const int Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
     BEM_REQUIRE(Ho > 0 && Wo > 0 && Wo % 2 == 0 && Cin % 8 == 0 && H * W >= 2, "%s: needs an even output width and Cin %% 8 == 0 (got Wo=%d Cin=%d)", what, Wo, Cin);
     BEM_REQUIRE(((uintptr_t)Wp & 15) == 0 && (((uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 7) == 0,
@@ -361,31 +358,4 @@ static int conv_taps_launch(const float* x, int64_t x_bstride, const float* Wp, 
         else conv_taps_x6_kernel<2, 3, 3, 2><<<grid, 256, 0, s>>>(k);
     }
     return bem_check_launch(what);
-}
-
-static bool rows_aligned(const float* x, int64_t x_bstride, const float* out, const float* res1, const float* res2) {
-    return x && out && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)(res1 ? res1 : out) | (uintptr_t)(res2 ? res2 : out)) & 15) == 0 && x_bstride % 4 == 0;
-}
-
-extern "C" int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                                  const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream) {
-    // the row form where the shape allows; nine shifted taps otherwise
-    if (Cin > 0 && bem_conv3x3_rows_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2))
-        return conv_rows_launch(3, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, res1_rep, stream);
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, 3, 1, 1, relu, res1_rep, stream, "conv3x3_x6");
-}
-
-
-extern "C" int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                                    const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream) {
-    // the row form; shapes outside it (bem_conv4x4s2_fast_supported == 0) belong to bem_conv2d_mfma_f32
-    BEM_REQUIRE(Cin > 0 && bem_conv4x4s2_fast_supported(Cin, H, W) && rows_aligned(x, x_bstride, out, res1, res2),
-                "conv4x4s2_x6: needs W = 2 Wo with Wo a power of two <= 64, even H, Cin %% 8 == 0 and 16-byte aligned tensors");
-    return conv_rows_launch(4, x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, relu, 1, stream);
-}
-
-extern "C" int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                                    float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
-                                    void* stream) {
-    return conv_taps_launch(x, x_bstride, Wp, bias, res1, res2, out, B, Cin, H, W, Cout, K, stride, dilation, relu, res1_rep, stream, "conv_taps_x6");
 }

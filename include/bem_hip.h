@@ -153,7 +153,7 @@ typedef struct {
     int B; int M; int K; int L;
 } bem_pw_args;
 /* natural (nsets, M, K) row-major -> packed f32-MFMA operand order (nsets, MT, KS, 64), MT = ceil(M/32), KS = ceil(K/2):
- * the weight format of the implicit-GEMM convolutions (bem_conv2d_mfma_f32). */
+ * the weight format of the implicit-GEMM convolutions (BEM_CONV_MFMA of bem_conv2d_f32). */
 int bem_pack_pw_weight_f32(const float* W, float* Wp, int nsets, int M, int K, void* stream);
 int64_t bem_pw_packed_elems(int M, int K);
 
@@ -200,44 +200,40 @@ int bem_upfuse_x6_f32(const float* f, const float* skip, const float* Wc_packed,
 int bem_dwconv3x3_f32(const float* x, const float* w, int64_t w_bstride, const float* bias,
                       int64_t bias_bstride, float* out, int B, int Cout, int H, int W, int mode, void* stream);
 
-/* Dense direct convolution KHxKW, given stride / zero padding (nn.Conv2d semantics), optional bias,
- * ReLU and up to two residual tensors added after the activation:
+/* Dense convolution KHxKW, given stride / zero padding / dilation (nn.Conv2d semantics), optional bias, ReLU and up to two residual
+ * tensors added after the activation:
  *   out = relu?(conv(x) + bias) + res1 + res2.      x (B,Cin,H,W) -> out (B,Cout,Ho,Wo)
  * x may be a channel slice of a wider tensor: x_bstride = elements between batch items.
- * res1_rep >= 1 (here and in the convolutions below): output row b adds res1 row b / res1_rep, so res1 has B / res1_rep rows -- a term
- * that is the same for the res1_rep Monte-Carlo samples of an image is computed once per image.  1: one residual row per output row. */
-int bem_conv2d_f32(const float* x, int64_t x_bstride, const float* w, const float* bias, const float* res1,
-                   const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                   int stride, int pad, int relu, int res1_rep, void* stream);
+ * res1_rep >= 1: output row b adds res1 row b / res1_rep, so res1 has B / res1_rep rows -- a term that is the same for the res1_rep
+ * Monte-Carlo samples of an image is computed once per image.  1: one residual row per output row.
+ * bem_conv2d_f32 runs the kernel form it is given, with w in that form's operand format, and rejects a form whose conditions the arguments miss. */
+#define BEM_CONV_ROWS 1     /* coalesced rows on the bf16-limb (x6) matrix cores (conv_x6.hip), f32-level error (bem_pw_gemm_x6_f32); w as for TAPS */
+#define BEM_CONV_TAPS 2     /* KH*KW shifted 1x1 taps on the same machinery; w = bem_pack_pw_weight_x6 of the (KH*KW, Cout, Cin) tap matrices, tap = ky*KW + kx */
+#define BEM_CONV_MFMA 3     /* implicit GEMM on the f32 matrix cores; w = bem_pack_pw_weight_f32 of the (Cout, Cin*KH*KW) view of the weight */
+#define BEM_CONV_DIRECT 4   /* VALU kernel staged through LDS; w = the plain (Cout,Cin,KH,KW) weight */
+int bem_conv2d_f32(int form, const float* x, int64_t x_bstride, const float* w, const float* bias, const float* res1, const float* res2,
+                   float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad, int dilation, int relu,
+                   int res1_rep, void* stream);
 
-/* The same convolution as an implicit GEMM on the f32 matrix cores; Wp = the (Cout, Cin*KH*KW) view of the weight
- * packed by bem_pack_pw_weight_f32.  Cout <= 160; 3x3 stride 1 and 4x4 stride 2. */
-int bem_conv2d_mfma_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                        const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int KH, int KW,
-                        int stride, int pad, int relu, int res1_rep, void* stream);
-
-/* The 3x3 stride-1 pad-1 case as nine shifted 1x1 taps on the bf16-limb GEMM (see bem_pw_gemm_x6_f32): no im2col patch,
- * f32-level error.  Wp = bem_pack_pw_weight_x6 of the (9, Cout, Cin) tap matrices, tap = ky*3 + kx (nsets = 9).
- * W even, Cin % 8 == 0; x_bstride as above; out = relu?(conv + bias) + res1 + res2. */
-int bem_conv3x3_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                       const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, int res1_rep, void* stream);
-/* The 4x4 stride-2 pad-1 down-sampling convolution (DecompDualBranchDDWavelet_arch.py:40-41) on the same machinery, tap = ky*4 + kx; even output
- * width, Cin % 8 == 0.  Shapes bem_conv4x4s2_fast_supported accepts (W = 2 Wo with Wo a power of two <= 64, even H; x and x_bstride 16-byte
- * aligned; no residual inputs) run the coalesced-row kernel of conv4_x6.hip: one aligned 16-byte load per lane, channel and input row, the two
- * outer columns from the neighbour lanes, tap weights staged in LDS by LDS-DMA; other shapes run the 16 shifted taps. */
-int bem_conv4x4s2_fast_supported(int Cin, int H, int W);
-/* 1 when bem_conv3x3_x6_f32 runs its row form (conv_x6.hip: W a power of two in 4 .. 128, Cin % 8 == 0, 16-byte aligned tensors), the
- * same kernel family with four output pixels per lane; other shapes run the nine shifted taps. */
-int bem_conv3x3_rows_supported(int Cin, int H, int W);
-int bem_conv4x4s2_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1,
-                         const float* res2, float* out, int B, int Cin, int H, int W, int Cout, int relu, void* stream);
-
-/* The general entry of the tap form: K x K taps with `stride` and `dilation`; supported: 3x3 s1 d1 (pad 1), 3x3 s1 d2 (pad 2: the dilated
- * branch convolutions of QD/model2.py:171-181), 3x3 s2 d1 (pad 1: down_conv of QD/model3.py:176), 5x5 s1 d1 (pad 2: the second AlexNet convolution of
- * LPIPS).  Wp as above (K*K tap matrices, tap = ky*K + kx). */
-int bem_conv_taps_x6_f32(const float* x, int64_t x_bstride, const float* Wp, const float* bias, const float* res1, const float* res2,
-                         float* out, int B, int Cin, int H, int W, int Cout, int K, int stride, int dilation, int relu, int res1_rep,
-                         void* stream);
+/* Which form takes a convolution: BEM_CONV_*, or 0 with bem_last_error() saying why no kernel does.  Host arithmetic on the arguments alone:
+ * no pointer is read (only whether it is NULL and its low four bits count), nothing is launched.  x is the pointer after the channel slice;
+ * out NULL = an allocation of the caller's own (aligned).
+ * allow: the forms that may be chosen where a rule says "x6 allowed" / "MFMA allowed" (tests and measurements reach the other kernels by
+ * clearing a bit).  K = KH, Wo = output width; the first row that matches decides:
+ *   0  KH != KW, (K, stride) none of (3,1) (3,2) (4,2) (5,1), or dilation not 1 / 2                                    -> refused
+ *   1  dilation != 1, or K = 3 stride 2 (QD/model2.py:171-181, QD/model3.py:176): K = 3, pad = dilation, (stride, dilation) one of
+ *      (1,1) (1,2) (2,1), Wo even, Cin % 8 == 0, x 8-byte aligned -> TAPS, else refused; the allow bits do not apply
+ *   2  K = 3, s1, p1, x6 allowed, W even, Cin % 8 == 0, x 8-byte aligned: W a power of two in 4 .. 128, x / out / res1 / res2 16-byte
+ *      aligned and x_bstride % 4 == 0 -> ROWS, else TAPS
+ *   3  K = 5, s1, p2 (LPIPS conv2), x6 allowed, W even, Cin % 8 == 0, x 8-byte aligned                                 -> TAPS
+ *   4  K = 4, s2, p1, no res1 / res2, Cin % 8 == 0, H and W even, Wo a power of two in 2 .. 64, x 16-byte aligned, x_bstride % 4 == 0 -> ROWS; no allow bit applies
+ *   5  MFMA allowed, Cout <= 160, (K, stride) one of (3,1) (4,2), any pad                                              -> MFMA
+ *   6  (K, stride) one of (3,1) (4,2), or (5,1) with Cin % 8 == 0                                                     -> DIRECT
+ *   7  anything else                                                                                                   -> refused */
+#define BEM_CONV_ALLOW_X6 1
+#define BEM_CONV_ALLOW_MFMA 2
+int bem_conv2d_route(const float* x, int64_t x_bstride, const float* res1, const float* res2, const float* out, int Cin, int H, int W,
+                     int Cout, int KH, int KW, int stride, int pad, int dilation, int allow);
 
 /* ---------------------------------------------------------------------------------------------
  * Quaternion / Haar primitives (basicsr/QD/model4.py:7-37,216-232; QD/quaternion.py:3-17).
@@ -707,7 +703,7 @@ int bem_relu_f32(const float* x, float* out, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * LPIPS v0.1 with the AlexNet trunk (csrc/lpips.hip; the metric of Enhancement/eval.py:143-145,301-306 and
- * Enhancement/cal_metrics_with_imgs.py:39-41,51-55).  The five convolutions are bem_conv3x3_x6_f32 / bem_conv_taps_x6_f32 / bem_conv2d_f32.
+ * Enhancement/cal_metrics_with_imgs.py:39-41,51-55).  The five convolutions are bem_conv2d_f32.
  * ------------------------------------------------------------------------------------------- */
 
 /* Input stage for both images at once, written as the operand of the first convolution.  ref, pred (B,3,H,W), H, W >= 31 (below that the

@@ -33,9 +33,9 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 # kernel-name regex (demangled) -> reason.  Everything else must have ScratchSize == 0.
 ALLOW_SCRATCH = {
-    r"conv2d_mfma_kernel<3, 3, 1": "f32-MFMA im2col 3x3 with three or more M-tiles: only with ops.USE_CONV_X6 off / odd widths (the default 3x3 paths are the x6 row and tap kernels)",
+    r"conv2d_mfma_kernel<3, 3, 1": "f32-MFMA im2col 3x3 with three or more M-tiles: row 5 of the route table (bem_conv2d_route, bem_hip.h), behind the x6 row and tap kernels",
     r"conv2d_mfma_pipe_kernel<3, 3, 1, 1>": "3x3 with Cin % 8 != 0 and Cout <= 32 (Stage-I first_conv at 16x16): 36 B, launch-bound size",
-    r"conv2d_mfma_kernel<4, 4, 2": "f32-MFMA im2col 4x4 stride-2: only for shapes the coalesced-row x6 kernel (conv_x6.hip) does not take (output widths that are not a power of two <= 64, e.g. config 5)",
+    r"conv2d_mfma_kernel<4, 4, 2": "f32-MFMA im2col 4x4 stride-2: row 5 of the route table, only what the coalesced-row x6 kernel (row 4) does not take, e.g. config 5",
     r"attn_fold_kernel": "one 1024-thread workgroup per image folding 8 32x32 matrices: 8 B, ~40 us per step",
     r"sample_pack_x6_kernel": "Stage-I weight sampling (Philox + Box-Muller + limb split per element, transcendental-bound): 48 B, 0.4 % of the step",
     r"pw_x6_res_lds_kernel<10": "K = 160 resident with the M-tiles' weights shared through LDS (level-2 project_in): 8-12 B parked across the LayerNorm statistics of the prologue, none in the M-tile loop",
@@ -49,7 +49,7 @@ ALLOW_SCRATCH = {
 
 # check 2 exemptions: kernel-name regex -> reason
 ALLOW_LDS_PK = {
-    r"^conv2d_kernel<": "direct VALU convolution: fallback for shapes no matrix-core kernel takes (or ops.USE_CONV_MFMA off); not dispatched by the shipped nets",
+    r"^conv2d_kernel<": "direct VALU convolution: row 6 of the route table (bem_conv2d_route, bem_hip.h), what no matrix-core kernel takes; not dispatched by the shipped nets",
 }
 
 PK = re.compile(r"^v_pk_(add|mul|fma)_f32\b")

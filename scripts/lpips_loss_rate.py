@@ -59,7 +59,8 @@ def main():
     os.environ[WEIGHTS_ENV] = wdir
     crit = build_loss(dict(type="LPIPSLoss", loss_weight=0.5)).to(dev)
     net = crit.lpips
-    cw, cb = net.conv_operands(), net.conv_operands_bwd()
+    cw = net.conv_operands()
+    cb = [c[0].input_grad() for c in cw]
     lines = [f"lpips_loss_rate: {torch.cuda.get_device_name(0)}, median of {a.iters} after 2 warm-up runs, HIP events, seeded weights",
              "command: python scripts/lpips_loss_rate.py"]
 

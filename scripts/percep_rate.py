@@ -108,7 +108,7 @@ def main():
         def b_blk():
             t = dy
             for n in reversed(names):
-                t = ops.conv2d(t, w[n][2], None)
+                t = ops.conv2d(t, w[n][0].input_grad(), None)
         tf, tb = timed(f_blk, a.iters), timed(b_blk, a.iters)
         fl = sum(2.0 * co * ci * 9 * H * H for co, ci, _, _ in shapes)
         lines.append(f"{blk:>5}  {H:>3}x{H:<3}  {len(names):>7}  {tf:6.2f}  {2 * B * fl / tf / 1e9:8.1f}  {tb:6.2f}  {B * fl / tb / 1e9:8.1f}")

@@ -215,6 +215,4 @@ def test_lpips_entries_reject_before_any_hip_call(lib):
     bad = list(ok)
     bad[3] = 6
     assert lib.bem_lpips_layer_f32(*bad) == 1 and b"strides" in lib.bem_last_error()
-    # the 5x5 tap form: odd widths and channel counts off the 8-grid are refused, not run
-    assert lib.bem_conv_taps_x6_f32(p, 64 * 7 * 7, p, None, None, None, p, 1, 64, 7, 7, 192, 5, 1, 1, 1, 1, None) == 1 and b"even output width" in lib.bem_last_error()
-    assert lib.bem_conv_taps_x6_f32(p, 64 * 7 * 8, p, None, None, None, p, 1, 64, 7, 8, 192, 5, 2, 1, 1, 1, None) == 1 and b"5x5 s1 p2" in lib.bem_last_error()
+    # the 5x5 tap form's refusals (odd widths, stride 2): tests/test_conv_route_cpu.py::test_forced_form_refuses_without_a_device

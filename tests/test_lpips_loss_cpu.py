@@ -159,12 +159,13 @@ def test_unsupported_settings_raise_by_name(kw, name, weights_dir):
 def test_backward_operands_are_the_flipped_transposed_weights(weights_dir):
     from basicsr.losses import build_loss
     net = build_loss(dict(type="LPIPSLoss", weights_dir=weights_dir)).lpips
-    ops_b = net.conv_operands_bwd()
-    assert ops_b is net.conv_operands_bwd() and len(ops_b) == 5                    # held by the module
+    grads = lambda: [cw.input_grad() for cw, _, _ in net.conv_operands()]
+    ops_b = grads()
+    assert all(a is b for a, b in zip(ops_b, grads())) and len(ops_b) == 5         # held by the module, with the forward forms
     assert [tuple(o.w.shape) for o in ops_b] == [(48, 64, 3, 3), (64, 192, 5, 5), (192, 384, 3, 3), (384, 256, 3, 3), (256, 256, 3, 3)]
     assert torch.equal(ops_b[1].w[3, 7], net.conv1_weight[7, 3].flip(0, 1))
     net.float()                                                                     # moving the module drops the packed forms
-    assert net.conv_operands_bwd() is not ops_b
+    assert not any(a is b for a, b in zip(ops_b, grads()))
 
 
 def test_condition_generator_refuses_lpips_opt_before_any_gpu_call():

@@ -325,8 +325,9 @@ def test_conv2d(ops, cfg, monkeypatch):
 
 @pytest.mark.parametrize("cfg", [(2, 32, 32, 16, 16, True), (1, 40, 16, 9, 14, False), (2, 8, 40, 33, 6, True), (1, 24, 80, 8, 130, False), (1, 32, 32, 128, 128, True)])
 def test_conv3x3_x6_taps(ops, cfg):
-    """3x3 convolution as nine shifted bf16-limb GEMM taps (bem_conv3x3_x6_f32): borders, half-filled last k-block (Cin % 16 == 8),
-    1 / 2 / 3 M-tiles, relu + two residuals, channel-slice input; against F.conv2d in float64 with the f32 run as the yardstick."""
+    """3x3 convolution as nine shifted bf16-limb GEMM taps: borders, half-filled last k-block (Cin % 16 == 8), 1 / 2 / 3 M-tiles, relu +
+    two residuals, channel-slice input; against F.conv2d in float64 with the f32 run as the yardstick.  Two of the five cases (W = 16 and
+    W = 128, powers of two) are row-form shapes and run that kernel; the other three run the taps."""
     B, Ci, Co, H, W, relu = cfg
     g = torch.Generator().manual_seed(Ci + Co + H)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, 3, 3, generator=g) * (Ci * 9) ** -0.5, torch.randn(Co, generator=g)
@@ -335,7 +336,9 @@ def test_conv3x3_x6_taps(ops, cfg):
         y = F.conv2d(x.to(dt), w.to(dt), b.to(dt), padding=1)
         return (F.relu(y) if relu else y) + r1.to(dt) + r2.to(dt)
     r64, r32 = run(torch.float64), run(torch.float32)
-    y = ops.conv2d(dev(x), dev(w), dev(b), stride=1, pad=1, relu=relu, res1=dev(r1), res2=dev(r2))
+    xd, wd, r1d, r2d = dev(x), dev(w), dev(r1), dev(r2)
+    assert ops.conv2d_route(xd, wd, stride=1, pad=1, res1=r1d, res2=r2d) == ("rows" if W in (16, 128) else "taps")
+    y = ops.conv2d(xd, wd, dev(b), stride=1, pad=1, relu=relu, res1=r1d, res2=r2d)
     close(y, r32, 1e-4, 2e-5, f"conv3x3 x6 {cfg}")
     e32 = (r32.double() - r64).abs().mean().item()
     if ops.USE_CONV_X6:        # the limb form's own accuracy claim (the f32-MFMA fallback sits at ~1.3x)
@@ -840,7 +843,6 @@ def test_conv4x4s2_coalesced_rows(ops, cfg):
     half-filled last k-block (Cin % 16 == 8), output rows of 2 .. 64 pixels (1 .. 32 lanes per row: every DPP neighbour / padding case),
     odd output heights, a partly empty last wave, relu, a channel-slice input; against F.conv2d in float64 with the f32 run as yardstick."""
     B, Ci, Co, H, W, relu = cfg
-    assert ops.lib().bem_conv4x4s2_fast_supported(Ci, H, W) == 1
     g = torch.Generator().manual_seed(Ci + Co + H + W)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, 4, 4, generator=g) * (Ci * 16) ** -0.5, torch.randn(Co, generator=g)
 
@@ -848,7 +850,9 @@ def test_conv4x4s2_coalesced_rows(ops, cfg):
         y = F.conv2d(x.to(dt), w.to(dt), b.to(dt), stride=2, padding=1)
         return F.relu(y) if relu else y
     r64, r32 = run(torch.float64), run(torch.float32)
-    y = ops.conv2d(dev(x), dev(w), dev(b), stride=2, pad=1, relu=relu)
+    xd, wd = dev(x), dev(w)
+    assert ops.conv2d_route(xd, wd, stride=2, pad=1) == "rows"
+    y = ops.conv2d(xd, wd, dev(b), stride=2, pad=1, relu=relu)
     close(y, r32, 1e-4, 2e-5, f"conv4x4s2 {cfg}")
     e32 = (r32.double() - r64).abs().mean().item()
     e = (y.cpu().double() - r64).abs().mean().item()
@@ -866,7 +870,6 @@ def test_conv3x3_row_form(ops, cfg):
     heights that leave the last wave partly empty, one / two / three row blocks of output channels, half-filled last k-block, relu and
     both residual inputs, a channel-slice input; against F.conv2d in float64 with the f32 run as yardstick."""
     B, Ci, Co, H, W, relu = cfg
-    assert ops.lib().bem_conv3x3_rows_supported(Ci, H, W) == 1
     g = torch.Generator().manual_seed(Ci + Co + H + W)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, 3, 3, generator=g) * (Ci * 9) ** -0.5, torch.randn(Co, generator=g)
     r1, r2 = torch.randn(B, Co, H, W, generator=g), torch.randn(B, Co, H, W, generator=g)
@@ -875,7 +878,9 @@ def test_conv3x3_row_form(ops, cfg):
         y = F.conv2d(x.to(dt), w.to(dt), b.to(dt), padding=1)
         return (F.relu(y) if relu else y) + r1.to(dt) + r2.to(dt)
     r64, r32 = run(torch.float64), run(torch.float32)
-    y = ops.conv2d(dev(x), dev(w), dev(b), stride=1, pad=1, relu=relu, res1=dev(r1), res2=dev(r2))
+    xd, wd, r1d, r2d = dev(x), dev(w), dev(r1), dev(r2)
+    assert ops.conv2d_route(xd, wd, stride=1, pad=1, res1=r1d, res2=r2d) == "rows"
+    y = ops.conv2d(xd, wd, dev(b), stride=1, pad=1, relu=relu, res1=r1d, res2=r2d)
     close(y, r32, 1e-4, 2e-5, f"conv3x3 rows {cfg}")
     e32 = (r32.double() - r64).abs().mean().item()
     e = (y.cpu().double() - r64).abs().mean().item()

@@ -43,7 +43,7 @@ def conv_close(a, b, what):
 
 
 # ----------------------------------------------------------------------------- res1_rep ---
-def _res1_rep_case(ops, H, W, what):
+def _res1_rep_case(ops, H, W, what, route):
     B, rep, Ci, Co = 6, 3, 16, 40
     g = torch.Generator().manual_seed(H * W)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, 3, 3, generator=g) * (Ci * 9) ** -0.5, torch.randn(Co, generator=g)
@@ -51,6 +51,7 @@ def _res1_rep_case(ops, H, W, what):
     y64 = F.conv2d(x.double(), w.double(), b.double(), padding=1)
     r1x = r1.double().repeat_interleave(rep, 0)
     xd, wd, bd, r1d, r2d = dev(x), dev(w), dev(b), dev(r1), dev(r2)
+    assert ops.conv2d_route(xd, wd, pad=1, res1=r1d, res1_rep=rep) == route
     conv_close(ops.conv2d(xd, wd, bd, pad=1, res1=r1d, res1_rep=rep), y64 + r1x, f"{what}: res1_rep {rep}")
     conv_close(ops.conv2d(xd, wd, bd, pad=1, relu=True, res1=r1d, res2=r2d, res1_rep=rep), F.relu(y64) + r1x + r2.double(),
                f"{what}: relu + res1_rep {rep} + res2")
@@ -69,20 +70,18 @@ def _res1_rep_case(ops, H, W, what):
 def test_res1_rep_row_form(ops):
     """B = 6 rows share 2 residual rows (res1_rep = 3), 16 -> 40 channels at 32x32: the row-form kernel (one k-block, two row blocks of
     output channels)."""
-    assert ops.lib().bem_conv3x3_rows_supported(16, 32, 32) == 1
-    _res1_rep_case(ops, 32, 32, "row form 32x32")
+    _res1_rep_case(ops, 32, 32, "row form 32x32", "rows")
 
 
 @pytest.mark.parametrize("kernel", ["taps", "mfma", "direct"])
 def test_res1_rep_other_kernels(ops, kernel, monkeypatch):
     """24x40 is outside the row form (W no power of two): the nine-tap x6 kernel takes it; with that switched off the f32-MFMA
     implicit GEMM, and with both off the direct kernel."""
-    assert ops.lib().bem_conv3x3_rows_supported(16, 24, 40) == 0
     if kernel != "taps":
         monkeypatch.setattr(ops, "USE_CONV_X6", False)
     if kernel == "direct":
         monkeypatch.setattr(ops, "USE_CONV_MFMA", False)
-    _res1_rep_case(ops, 24, 40, f"{kernel} 24x40")
+    _res1_rep_case(ops, 24, 40, f"{kernel} 24x40", kernel)
 
 
 # ----------------------------------------------------------------------------- split first_conv ---
