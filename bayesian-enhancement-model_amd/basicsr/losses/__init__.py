@@ -1,11 +1,12 @@
 """build_loss (basicsr/losses/__init__.py) for the losses of the hot path's training step.
 
 ``L1Loss`` runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn).  ``PerceptualLoss``
-(VGG19 features, criterion l1) is bem.percep's module: one autograd node of HIP kernels (bem.autograd.PerceptualFn); its weights are
+(VGG19 features, criterion l1 or l2) is bem.percep's module: one autograd node of HIP kernels (bem.autograd.PerceptualFn); its weights are
 read from a torchvision state dict on disk (bem.percep.weights_path), never fetched.  ``SSIMLoss`` is one tiled HIP kernel forward (plus
 the fixed-order sum of its partials) and one backward (bem.autograd.SSIMLossFn).  ``LPIPSLoss`` is the metric of bem.lpips (v0.1, AlexNet)
 without its quantisation, as one autograd node of HIP kernels (bem.autograd.LPIPSFn); its two weight files are found on disk
-(bem.lpips.find_weight_files), never fetched."""
+(bem.lpips.find_weight_files), never fetched.  ``CombinedLoss`` is the reference's six-term recipe (my_loss.py:51-74): its four
+per-pixel statistics in one HIP pass (bem.autograd.PixStatLossFn) beside ``SSIMLoss`` and ``PerceptualLoss`` with criterion l2."""
 from copy import deepcopy
 
 import torch.nn as nn
@@ -14,9 +15,11 @@ from basicsr.utils.registry import LOSS_REGISTRY
 from basicsr.utils.registry import ARCH_REGISTRY
 from bem import autograd as _ag
 from bem.lpips import LPIPS
+from bem.ops import PIXSTAT_VALUES
 from bem.percep import PerceptualLoss, VGGFeatureExtractor
 
-__all__ = ["build_loss", "L1Loss", "SSIMLoss", "LPIPSLoss", "PerceptualLoss", "VGGFeatureExtractor"]
+__all__ = ["build_loss", "L1Loss", "SSIMLoss", "LPIPSLoss", "CombinedLoss", "PerceptualLoss", "VGGFeatureExtractor"]
+_PIXSTAT_AT = {name: i for i, name in enumerate(PIXSTAT_VALUES)}
 
 LOSS_REGISTRY.register(PerceptualLoss)
 if "VGGFeatureExtractor" not in ARCH_REGISTRY:
@@ -80,6 +83,79 @@ class LPIPSLoss(nn.Module):
         if weight is not None:
             raise NotImplementedError("LPIPSLoss: element-wise weights are not used on the BEM path")
         return _ag.lpips_loss(pred, target, self)
+
+
+@LOSS_REGISTRY.register()
+class CombinedLoss(nn.Module):
+    """basicsr/losses/my_loss.py:51-74, the reference's own loss recipe with its weights as defaults:
+        loss_weight * (alpha1 smooth_l1 + alpha2 VGG19[:16]-MSE + alpha3 histogram + alpha4 (1 - SSIM) + alpha5 psnr_loss + alpha6 color_loss)
+    Three autograd nodes: the four per-pixel statistics in one pass (bem.autograd.PixStatLossFn, csrc/pixstat_loss.hip), ``SSIMLoss`` and
+    ``PerceptualLoss({'relu3_3': 1}, criterion='l2')`` on the raw images (``vgg19.features[:16]`` with F.mse_loss, my_loss.py:12-19); their
+    gradients into pred are summed by bem_add_f32 (ag.fork_n).  A zero alpha switches its part off entirely: alpha2 = 0 needs no VGG file,
+    alpha4 = 0 allows images below 11x11.  ``vgg_weights`` names the torchvision vgg19 state dict (otherwise bem.percep.weights_path);
+    ``state_dict`` hands one over directly (keys features.0 .. features.14).  After a forward ``parts`` holds the unweighted values of
+    the active parts as device scalars, in the order of PARTS."""
+    ALPHAS = ("alpha1", "alpha2", "alpha3", "alpha4", "alpha5", "alpha6")
+    PARTS = ("smooth_l1", "percep", "hist", "psnr", "color", "ssim")              # the part alpha1 .. alpha6 weighs
+
+    def __init__(self, alpha1=1.00, alpha2=0.06, alpha3=0.05, alpha4=0.5, alpha5=0.0083, alpha6=0.25, loss_weight=1.0, vgg_weights=None,
+                 state_dict=None):
+        super().__init__()
+        for k, v in zip(self.ALPHAS, (alpha1, alpha2, alpha3, alpha4, alpha5, alpha6)):
+            if not v >= 0:
+                raise ValueError(f"CombinedLoss: {k}={v}: a weight of the recipe is >= 0 (0 switches its part off)")
+            setattr(self, k, float(v))
+        if not loss_weight > 0:
+            raise ValueError(f"CombinedLoss: loss_weight={loss_weight} must be positive (set an alpha to 0 to switch a part off)")
+        if not any(getattr(self, k) > 0 for k in self.ALPHAS):
+            raise ValueError("CombinedLoss: alpha1 .. alpha6 are all 0: no part is left")
+        self.loss_weight = float(loss_weight)
+        self.percep = self.ssim = None
+        if self.alpha2 > 0:
+            if state_dict is None and vgg_weights is not None:
+                from bem.percep import load_vgg19_state_dict
+                state_dict = load_vgg19_state_dict(vgg_weights)
+            self.percep = PerceptualLoss({"relu3_3": 1}, use_input_norm=False, range_norm=False, criterion="l2",
+                                         perceptual_weight=self.alpha2 * self.loss_weight, state_dict=state_dict)
+        if self.alpha4 > 0:
+            self.ssim = SSIMLoss(loss_weight=self.alpha4 * self.loss_weight)
+        self.pix_alphas = tuple(a * self.loss_weight for a in (self.alpha1, self.alpha3, self.alpha5, self.alpha6))
+        self.parts = {}
+
+    @staticmethod
+    def find_weights(opt):
+        """For a ``train.combined_opt`` block: the path of the VGG19 state dict its alpha2 part will read (FileNotFoundError if the file
+        is missing), None where that part is off.  The training driver asks before a model exists."""
+        from bem.percep import find_vgg19_weights
+        if not opt.get("alpha2", 0.06) > 0 or opt.get("state_dict") is not None:
+            return None
+        return find_vgg19_weights(opt.get("vgg_weights"))
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        if weight is not None:
+            raise NotImplementedError("CombinedLoss: element-wise weights are not used on the BEM path")
+        pix = any(a > 0 for a in self.pix_alphas)
+        heads = iter(_ag.fork_n(pred, int(pix) + (self.percep is not None) + (self.ssim is not None)))
+        terms, parts = [], {}
+        if pix:
+            l, vals = _ag.pixstat_loss(next(heads), target, self.pix_alphas)
+            terms.append(l)
+            for name, a in zip(("smooth_l1", "hist", "psnr", "color"), self.pix_alphas):
+                if a > 0:
+                    parts[name] = vals[_PIXSTAT_AT[name]]
+        if self.percep is not None:
+            l, _ = self.percep(next(heads), target)
+            terms.append(l)
+            parts["percep"] = l.detach() / self.percep.perceptual_weight
+        if self.ssim is not None:
+            l = self.ssim(next(heads), target)
+            terms.append(l)
+            parts["ssim"] = l.detach() / self.ssim.loss_weight
+        self.parts = {k: parts[k] for k in self.PARTS if k in parts}
+        total = terms[0]
+        for l in terms[1:]:
+            total = _ag.AddFn.apply(total, l)
+        return total
 
 
 def build_loss(opt):

@@ -44,6 +44,10 @@ class ConditionGenerator(BaseModel):
             raise NotImplementedError("ConditionGenerator: lpips_opt is not available for Stage I: its predictions are 8x8 planes, below the "
                                       "31x31 that LPIPSLoss's AlexNet trunk needs; remove `lpips_opt` (the Stage-I option files of the "
                                       "reference train on the pixel loss)")
+        if train_opt.get("combined_opt"):
+            raise NotImplementedError("ConditionGenerator: combined_opt is not available for Stage I: its predictions are 8x8 planes, smaller than "
+                                      "the 11x11 window of CombinedLoss's SSIM part and below what its VGG19 trunk can take; remove "
+                                      "`combined_opt` (the Stage-I option files of the reference train on the pixel loss)")
         self.cri_perceptual = None
         if self.cri_pix is None:
             raise ValueError("Both pixel and perceptual losses are None.")

@@ -5,7 +5,8 @@
 The step runs entirely on the HIP path: condition upsample + concat (bem.ops), forward / backward (bem.autograd), global-norm clip +
 AdamW on one flat buffer (bem.train.BemAdamW), the pixel loss and -- with ``train.perceptual_opt`` -- the VGG19 perceptual loss
 (bem.percep) and -- with ``train.ssim_opt`` -- the SSIM term of basicsr/losses/my_loss.py:37-38 (csrc/ssim_loss.hip) and -- with
-``train.lpips_opt`` -- the LPIPS term (bem.lpips, csrc/lpips.hip), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
+``train.lpips_opt`` -- the LPIPS term (bem.lpips, csrc/lpips.hip) and -- with ``train.combined_opt`` -- the six-term recipe of
+basicsr/losses/my_loss.py:51-74 (basicsr.losses.CombinedLoss, csrc/pixstat_loss.hip), with no host synchronisation inside ``optimize_parameters`` -- loss values and the
 gradient norm come back as device scalars (read them when logging).  AMP (`use_amp`) is not offered: the path is f32.
 ``train.ema_decay > 0`` keeps ``net_g_ema`` (BaseModel), which is validated instead of net_g (:239-247)."""
 from collections import OrderedDict
@@ -19,6 +20,8 @@ from basicsr.utils.registry import MODEL_REGISTRY
 from bem import autograd as ag
 from bem import ops
 from bem.archs import AttnDrop, attn_drop_stream_id
+
+_ALL_NONE = "Pixel, perceptual, SSIM, LPIPS and combined losses are all None."
 
 
 @MODEL_REGISTRY.register()
@@ -41,8 +44,10 @@ class ImageEnhancer(BaseModel):
         self.cri_perceptual = build_loss(train_opt["perceptual_opt"]).to(self.device) if train_opt.get("perceptual_opt") else None
         self.cri_ssim = build_loss(train_opt["ssim_opt"]).to(self.device) if train_opt.get("ssim_opt") else None
         self.cri_lpips = build_loss(train_opt["lpips_opt"]).to(self.device) if train_opt.get("lpips_opt") else None
-        if self.cri_pix is None and self.cri_perceptual is None and self.cri_ssim is None and self.cri_lpips is None:
-            raise ValueError("Pixel, perceptual, SSIM and LPIPS losses are all None.")
+        if train_opt.get("combined_opt"):                              # without the block the model has no such attribute
+            self.cri_combined = build_loss(train_opt["combined_opt"]).to(self.device)
+        if self.cri_pix is None and self.cri_perceptual is None and self.cri_ssim is None and self.cri_lpips is None and not hasattr(self, "cri_combined"):
+            raise ValueError(_ALL_NONE)
         self._ssim_metrics()                                           # a val.metrics entry validation would refuse is refused now
         self.init_optimizer_and_ema()
 
@@ -98,19 +103,19 @@ class ImageEnhancer(BaseModel):
             if dec is not None:
                 dec.attn_drop = None                                  # the record is this forward's alone
         loss_dict = OrderedDict()
-        # :183-191: l_total = l_pix + l_percep (+ l_ssim, my_loss.py:37-38, + l_lpips) over the configured terms; preds feeds each of them,
+        # :183-191: l_total = l_pix + l_percep (+ l_ssim, my_loss.py:37-38, + l_lpips, + l_comb, my_loss.py:51-74) over the configured terms; preds feeds each of them,
         # its gradients are summed by bem_add_f32 (ag.fork_n; one term alone takes preds itself)
-        crits = (self.cri_pix, self.cri_perceptual, self.cri_ssim, self.cri_lpips)
+        crits = (self.cri_pix, self.cri_perceptual, self.cri_ssim, self.cri_lpips, getattr(self, "cri_combined", None))
         heads = iter(ag.fork_n(preds, sum(c is not None for c in crits)))
-        l_pix, l_percep, l_ssim, l_lpips = ((None if c is None else c(next(heads), self.gt)) for c in crits)
+        l_pix, l_percep, l_ssim, l_lpips, l_comb = ((None if c is None else c(next(heads), self.gt)) for c in crits)
         if l_percep is not None:
             l_percep, _ = l_percep                                       # None with perceptual_weight <= 0 (:186): the term is off
         l_total = None
-        for l in (l_pix, l_percep, l_ssim, l_lpips):
+        for l in (l_pix, l_percep, l_ssim, l_lpips, l_comb):
             if l is not None:
                 l_total = l if l_total is None else ag.AddFn.apply(l_total, l)
         if l_total is None:
-            raise ValueError("Pixel, perceptual, SSIM and LPIPS losses are all None.")
+            raise ValueError(_ALL_NONE)
         if l_pix is not None:
             loss_dict["l_pix"] = self.unweighted(l_pix, self.opt["train"]["pixel_opt"].get("loss_weight", 1))
         if l_percep is not None:
@@ -119,6 +124,10 @@ class ImageEnhancer(BaseModel):
             loss_dict["l_ssim"] = self.unweighted(l_ssim, self.cri_ssim.loss_weight)                    # 1 - SSIM
         if l_lpips is not None:
             loss_dict["l_lpips"] = self.unweighted(l_lpips, self.cri_lpips.loss_weight)                 # the mean distance
+        if l_comb is not None:
+            loss_dict["l_comb"] = self.unweighted(l_comb, self.cri_combined.loss_weight)                # the recipe's own sum
+            for name, v in self.cri_combined.parts.items():                                            # its active parts, unweighted
+                loss_dict["l_comb_" + name] = v
         l_total.backward()
         total_norm = self.finish_step()
         self.log_dict = self.reduce_loss_dict(loss_dict)

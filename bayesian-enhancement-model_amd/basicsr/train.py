@@ -73,6 +73,10 @@ def train_pipeline(root_path, argv=None):
         # the weight files of the LPIPS term are looked for now: a missing one stops the run before directories, data or a model exist
         from bem.lpips import find_weight_files
         find_weight_files(opt["train"]["lpips_opt"].get("weights_dir"))
+    if (opt.get("train") or {}).get("combined_opt") and opt.get("model_type") != "ConditionGenerator":     # Stage I refuses the block itself
+        # likewise the VGG19 state dict of the recipe's alpha2 part (--vgg_weights / BEM_VGG19_WEIGHTS, as for perceptual_opt); alpha2 = 0 needs none
+        from basicsr.losses import CombinedLoss
+        CombinedLoss.find_weights(opt["train"]["combined_opt"])
 
     resume_state = load_resume_state(opt, experiments_root=osp.dirname(opt["path"]["experiments_root"]))
     if resume_state is None and opt["rank"] == 0:

@@ -172,6 +172,41 @@ def ssim_loss(pred, gt, weight=1.0):
     return SSIMLossFn.apply(pred, gt, float(weight))
 
 
+class PixStatLossFn(Function):
+    """The per-pixel statistics of basicsr/losses/my_loss.py:51-74 (csrc/pixstat_loss.hip): a1 smooth_l1 + a3 hist + a5 psnr + a6 color
+    as a 0-d loss; the (6,) device tensor ops.PIXSTAT_VALUES (the loss and the five unweighted values) is appended to ``values`` for the log.  The
+    forward's second launch writes the backward's record when pred wants a gradient; gt takes none, and neither does the histogram term:
+    with a1 = a5 = a6 = 0 the gradient is zero and no kernel is launched for it."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, alphas, values):
+        pred, gt = pred.contiguous(), gt.contiguous()
+        ctx.has_grad = any(alphas[i] != 0 for i in (0, 2, 3))
+        if ctx.needs_input_grad[0] and ctx.has_grad:
+            vals, rec = ops.pixstat_loss(pred, gt, alphas, want_grad=True)
+            ctx.save_for_backward(pred, gt, rec)
+        else:
+            vals = ops.pixstat_loss(pred, gt, alphas)
+            if ctx.needs_input_grad[0]:
+                ctx.save_for_backward(pred)                    # its shape, for the zero gradient
+        values.append(vals)
+        return vals[:1].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.has_grad:
+            return torch.zeros_like(ctx.saved_tensors[0]), None, None, None
+        pred, gt, rec = ctx.saved_tensors
+        return ops.pixstat_loss_bwd(pred, gt, rec, g.reshape(1).contiguous().float()), None, None, None
+
+
+def pixstat_loss(pred, gt, alphas):
+    """(loss, values) of PixStatLossFn; ``alphas`` = (a1, a3, a5, a6), values = the (6,) tensor of ops.PIXSTAT_VALUES."""
+    values = []
+    loss = PixStatLossFn.apply(pred, gt, tuple(float(a) for a in alphas), values)
+    return loss, values[0]
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # VGG19 perceptual loss (basic_loss.py:198-222 over vgg_arch.py:141-161)
 # ------------------------------------------------------------------------------------------------------------------
@@ -209,8 +244,8 @@ def vgg_features(vgg, x):
 
 
 class PerceptualFn(Function):
-    """percep_loss of PerceptualLoss.forward(pred, gt), criterion l1.  Forward: both images as one 2B-row batch through the walk, one
-    bem_l1_loss_f32 per requested layer between the two halves, the values summed on the device.  Backward: the pred half only, against
+    """percep_loss of PerceptualLoss.forward(pred, gt), criterion l1 or l2.  Forward: both images as one 2B-row batch through the walk, one
+    bem_l1_loss_f32 (l2: bem_mse_loss_f32) per requested layer between the two halves, the values summed on the device.  Backward: the pred half only, against
     the frozen weights: no weight gradient, none for gt.  Saved: the post-ReLU activations of the pred rows (ReLU masks, pool argmax)
     and the requested features."""
 
@@ -223,8 +258,9 @@ class PerceptualFn(Function):
         keep = {} if need_bwd else None
         feats = _vgg_walk(vgg, ops.vgg_prep(pred, gt, vgg.use_input_norm, vgg.range_norm), keep, B)
         total = None
+        crit = ops.mse_loss if mod.criterion_type == "l2" else ops.l1_loss
         for n, f in feats.items():
-            l = ops.l1_loss(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight))
+            l = crit(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight))
             total = l if total is None else ops.add(total, l)
         if need_bwd:
             ctx.mod, ctx.B = mod, B
@@ -242,9 +278,11 @@ class PerceptualFn(Function):
         acts = dict(zip(ctx.act_names, ctx.saved_tensors[nf:]))
         gmul = g.reshape(1).contiguous().float()
 
+        crit_bwd = ops.mse_loss_bwd if mod.criterion_type == "l2" else ops.l1_loss_bwd
+
         def dfeat(n):
             f = feats[n]
-            return ops.l1_loss_bwd(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight), gmul)
+            return crit_bwd(f[:B], f[B:], float(mod.layer_weights[n]) * float(mod.perceptual_weight), gmul)
 
         d, masked = None, False          # d: gradient at the output of layer i; masked: the mask of the ReLU it leaves is already in it
         for i in range(len(names) - 1, -1, -1):

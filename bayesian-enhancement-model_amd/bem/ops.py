@@ -1725,6 +1725,28 @@ def l1_loss_bwd(pred, gt, weight=1.0, gmul=None):
     return dp
 
 
+def mse_loss(pred, gt, weight=1.0):
+    """loss (1,) = weight * mean (pred - gt)^2."""
+    _chk(pred, "pred"); _chk(gt, "gt")
+    if pred.shape != gt.shape:
+        raise ValueError("mse_loss: shapes differ")
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    ws = torch.empty(1, device=pred.device, dtype=torch.float64)
+    check(lib().bem_mse_loss_f32(_p(pred), _p(gt), _p(None), _p(loss), _p(ws), pred.numel(), float(weight), _p(None), _stream()), "mse_loss")
+    return loss
+
+
+def mse_loss_bwd(pred, gt, weight=1.0, gmul=None):
+    """dpred = gmul * weight * 2 (pred - gt) / numel  (gmul: device scalar dL/dloss, None = 1)."""
+    _chk(pred, "pred"); _chk(gt, "gt"); _chk(gmul, "gmul", optional=True)
+    if pred.shape != gt.shape:
+        raise ValueError("mse_loss_bwd: shapes differ")
+    dp = torch.empty_like(pred)
+    ws = torch.empty(1, device=pred.device, dtype=torch.float64)
+    check(lib().bem_mse_loss_f32(_p(pred), _p(gt), _p(dp), _p(None), _p(ws), pred.numel(), float(weight), _p(gmul), _stream()), "mse_loss_bwd")
+    return dp
+
+
 SSIM_WINDOW = 11          # the Gaussian window of the SSIM loss (sigma 1.5): the valid region of an H x W plane is (H - 10) x (W - 10)
 
 
@@ -1785,6 +1807,77 @@ def ssim_loss_bwd(pred, gt, coef, weight=1.0, gmul=None):
         raise ValueError(f"ssim_loss_bwd: coef {tuple(coef.shape)} is not the three valid-region maps of pred {tuple(pred.shape)}")
     dp = torch.empty_like(pred)
     check(lib().bem_ssim_loss_bwd_f32(_p(pred), _p(gt), _p(coef), _p(dp), P, H, W, float(weight), _p(gmul), _stream()), "ssim_loss_bwd")
+    return dp
+
+
+PIXSTAT_VALUES = ("loss", "smooth_l1", "mse", "psnr", "color", "hist")     # what pixstat_loss returns, in this order
+PIXSTAT_BINS = 256
+
+
+def pixstat_loss_chunk():
+    """Elements one workgroup of the pixstat kernels takes of a sample (csrc/pixstat_loss.hip); samples of at most a quarter of it go to
+    workgroups whole."""
+    return int(lib().bem_pixstat_loss_chunk())
+
+
+def _pixstat_samples(op, pred, gt):
+    """Operand check shared by the pixstat loss and its backward -> (B, C*H*W)."""
+    _chk(pred, "pred"); _chk(gt, "gt")
+    if pred.dim() != 4 or pred.shape != gt.shape:
+        raise ValueError(f"{op}: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be one (B,C,H,W) shape")
+    if pred.device != gt.device:
+        raise ValueError(f"{op}: pred is on {pred.device}, gt on {gt.device}")
+    if pred.numel() == 0:
+        raise ValueError(f"{op}: empty tensor")
+    return pred.shape[0], _prod(pred.shape[1:])
+
+
+def _pixstat_alphas(op, alphas):
+    a = tuple(float(v) for v in alphas)
+    if len(a) != 4 or not all(v >= 0 for v in a):
+        raise ValueError(f"{op}: alphas = (smooth_l1, hist, psnr, color) weights, each >= 0, got {alphas}")
+    return a
+
+
+def pixstat_loss_cost(pred, **_):
+    """Algorithmic (bytes, flops) of the forward: pred and gt read once; ~12 flops and two bin indices per element."""
+    return 8.0 * pred.numel(), 12.0 * pred.numel()
+
+
+def pixstat_loss_bwd_cost(pred, **_):
+    """Algorithmic (bytes, flops) of the backward: pred and gt read once, dpred written; 7 flops per element."""
+    return 12.0 * pred.numel(), 7.0 * pred.numel()
+
+
+@_bracket(pixstat_loss_cost)
+def pixstat_loss(pred, gt, alphas, want_grad=False, return_hist=False):
+    """The per-pixel statistics of CombinedLoss (my_loss.py:51-74) on (B,C,H,W) tensors, one pass: values (6,) f32 = PIXSTAT_VALUES, i.e.
+    a1 smooth_l1 + a3 hist + a5 psnr + a6 color for ``alphas`` = (a1, a3, a5, a6) followed by the unweighted smooth_l1, mse, psnr =
+    40 - 20 log10(1 / sqrt(mse)), color and hist.  ``want_grad``: also the backward's record (2 + B,) f64.  ``return_hist``: also the
+    counts (2, 256) int64 of torch.histc(pred, 256, 0, 1) and of gt.  Returns the values, or a tuple values[, rec][, hist]."""
+    B, n1 = _pixstat_samples("pixstat_loss", pred, gt)
+    a = _pixstat_alphas("pixstat_loss", alphas)
+    dev = pred.device
+    vals = torch.empty(len(PIXSTAT_VALUES), device=dev, dtype=torch.float32)
+    rec = torch.empty(2 + B, device=dev, dtype=torch.float64) if want_grad else None
+    nb = int(lib().bem_pixstat_loss_ws_bytes(B, n1))               # 0: a size the call below refuses by name
+    ws = _scratch("pixstat_loss", dev, max(nb, 8) // 8, torch.float64)
+    check(lib().bem_pixstat_loss_f32(_p(pred), _p(gt), _p(vals), _p(rec), _p(ws), B, n1, *a, _stream()), "pixstat_loss")
+    out = (vals,) + ((rec,) if want_grad else ())
+    if return_hist:
+        out += (ws[:PIXSTAT_BINS].view(torch.int32).reshape(2, PIXSTAT_BINS).to(torch.int64) & 0xFFFFFFFF,)
+    return out if len(out) > 1 else vals
+
+
+@_bracket(pixstat_loss_bwd_cost)
+def pixstat_loss_bwd(pred, gt, rec, gmul=None):
+    """dpred of pixstat_loss from the record its forward wrote (gmul: device scalar dL/dloss, None = 1)."""
+    B, n1 = _pixstat_samples("pixstat_loss_bwd", pred, gt)
+    _chk(rec, "rec", dtype=torch.float64); _chk(gmul, "gmul", optional=True)
+    if tuple(rec.shape) != (2 + B,):
+        raise ValueError(f"pixstat_loss_bwd: rec {tuple(rec.shape)} is not the record (2 + B,) of pred {tuple(pred.shape)}")
+    dp = torch.empty_like(pred)
+    check(lib().bem_pixstat_loss_bwd_f32(_p(pred), _p(gt), _p(rec), _p(dp), B, n1, _p(gmul), _stream()), "pixstat_loss_bwd")
     return dp
 
 

@@ -1,7 +1,7 @@
 """VGG19 perceptual loss of the Stage-II training step (basicsr/losses/basic_loss.py:146-238 over basicsr/archs/vgg_arch.py:54-161).
 
 ``VGGFeatureExtractor`` owns the frozen convolution weights and the operand forms the kernels read; ``PerceptualLoss`` is the
-reference's module around it.  The feature pass, the per-layer L1 terms and the whole backward are one autograd node of HIP
+reference's module around it.  The feature pass, the per-layer L1 (criterion l2: MSE) terms and the whole backward are one autograd node of HIP
 kernels (bem.autograd.PerceptualFn).  Weights come from a torchvision ``vgg19`` state dict on disk; nothing is ever downloaded."""
 from __future__ import annotations
 
@@ -34,12 +34,17 @@ def weights_path():
     return os.environ.get(WEIGHTS_ENV) or VGG_PRETRAIN_PATH
 
 
-def load_vgg19_state_dict(path=None):
+def find_vgg19_weights(path=None):
+    """The state dict's path (``path`` or weights_path()) if the file is there, FileNotFoundError naming where it is looked for otherwise."""
     path = path or weights_path()
     if not os.path.isfile(path):
         raise FileNotFoundError(f"VGG19 weights not found at '{path}': put torchvision's vgg19-dcbb9e9d.pth at {VGG_PRETRAIN_PATH} (relative to "
                                 f"the working directory) or point the environment variable {WEIGHTS_ENV} at it; nothing is downloaded")
-    return torch.load(path, map_location="cpu", weights_only=True)
+    return path
+
+
+def load_vgg19_state_dict(path=None):
+    return torch.load(find_vgg19_weights(path), map_location="cpu", weights_only=True)
 
 
 class VGGFeatureExtractor(nn.Module):
@@ -116,8 +121,9 @@ class PerceptualLoss(nn.Module):
         super().__init__()
         if style_weight > 0:
             raise NotImplementedError(f"PerceptualLoss: style_weight={style_weight}: the style (Gram) term is not on the HIP path (every shipped option file has 0)")
-        if criterion != "l1":
-            raise NotImplementedError(f"PerceptualLoss: criterion '{criterion}' is not on the HIP path (l1 only, as in every shipped option file)")
+        if criterion not in ("l1", "l2"):
+            raise NotImplementedError(f"PerceptualLoss: criterion '{criterion}' is not on the HIP path (l1, as in every shipped option file, "
+                                      "and l2, basic_loss.py:191-192)")
         self.perceptual_weight, self.style_weight, self.criterion_type = perceptual_weight, style_weight, criterion
         self.layer_weights = dict(layer_weights)
         self.vgg = VGGFeatureExtractor(list(self.layer_weights.keys()), vgg_type=vgg_type, use_input_norm=use_input_norm,

@@ -15,6 +15,8 @@ namespace {
 
 // ---------------------------------------------------------------- L1 loss -------------------------------------------
 // sum |pred - gt| in f64 (one atomic per workgroup); dpred = sign(pred - gt) * scale (scale = loss_weight / numel).
+// SQ (the MSE loss): sum (pred - gt)^2, dpred = 2 (pred - gt) * scale.
+template <bool SQ>
 __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ dpred,
                                                  double* __restrict__ acc, int64_t n, float scale, const float* __restrict__ gmul) {
     __shared__ double sh[4];
@@ -22,8 +24,8 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred,
     if (gmul) scale *= gmul[0];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float d = pred[i] - gt[i];
-        s += fabsf(d);
-        if (dpred) dpred[i] = d > 0.f ? scale : (d < 0.f ? -scale : 0.f);
+        s += SQ ? (double)d * (double)d : (double)fabsf(d);
+        if (dpred) dpred[i] = SQ ? 2.f * d * scale : (d > 0.f ? scale : (d < 0.f ? -scale : 0.f));
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
@@ -591,9 +593,20 @@ extern "C" int bem_l1_loss_f32(const float* pred, const float* gt, float* dpred,
     hipStream_t s = (hipStream_t)stream;
     BEM_ZERO(ws, sizeof(double), s, "l1_loss");
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, 256), 2048);
-    l1_kernel<<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, weight / (float)n, gmul);
+    l1_kernel<false><<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, weight / (float)n, gmul);
     l1_final_kernel<<<1, 1, 0, s>>>(ws, loss, (double)weight / (double)n);
     return bem_check_launch("l1_loss");
+}
+
+extern "C" int bem_mse_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
+                                const float* gmul, void* stream) {
+    BEM_REQUIRE(pred && gt && (loss || dpred) && ws && n > 0, "mse_loss: null pointer / empty tensor");
+    hipStream_t s = (hipStream_t)stream;
+    BEM_ZERO(ws, sizeof(double), s, "mse_loss");
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, 256), 2048);
+    l1_kernel<true><<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, weight / (float)n, gmul);
+    l1_final_kernel<<<1, 1, 0, s>>>(ws, loss, (double)weight / (double)n);
+    return bem_check_launch("mse_loss");
 }
 
 namespace {

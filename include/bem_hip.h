@@ -509,6 +509,35 @@ int bem_ssim_loss_f32(const float* pred, const float* gt, float* loss, float* co
 int bem_ssim_loss_bwd_f32(const float* pred, const float* gt, const float* coef, float* dpred, int64_t planes, int H, int W,
                           float weight, const float* gmul, void* stream);
 
+/* MSELoss(reduction='mean') under a weight (F.mse_loss: basicsr/losses/my_loss.py:19, the criterion 'l2' of basic_loss.py:191-192), the
+ * contract of bem_l1_loss_f32: loss[0] (or NULL) = weight * mean (pred - gt)^2; dpred (or NULL) = gmul[0] * weight * 2 (pred - gt) / n.
+ * ws: one double of scratch (zeroed by the call). */
+int bem_mse_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
+                     const float* gmul, void* stream);
+
+/* The per-pixel statistics of CombinedLoss (basicsr/losses/my_loss.py:51-74) in one pass over pred and gt, contiguous (B, n1) f32 with
+ * n1 = C*H*W elements per sample, d = pred - gt, n = B * n1 < 2^32 (the histogram counters are 32 bits wide; refused above):
+ *   out[1] smooth_l1 = mean(|d| < 1 ? d^2 / 2 : |d| - 1/2)                         (my_loss.py:30-31)
+ *   out[2] mse = mean d^2,   out[3] psnr = 40 - 20 log10(1 / sqrt(mse))            (my_loss.py:25-28; -inf for mse == 0)
+ *   out[4] color = mean_b |mean gt_b - mean pred_b|                                (my_loss.py:22-23)
+ *   out[5] hist = mean_k |h_gt[k] / sum h_gt - h_pred[k] / sum h_pred|, h = torch.histc(x, 256, 0, 1): bin floor(256 x), 1.0 in bin 255,
+ *          x < 0, x > 1 and NaN not counted; NaN when pred or gt has no value in [0,1]   (my_loss.py:40-49)
+ *   out[0] loss = a1 smooth_l1 + a3 hist + a5 psnr + a6 color, alphas >= 0, a term with a zero alpha left out   (my_loss.py:70-72)
+ * Bit-reproducible from call to call: f64 partials per workgroup (no workgroup crosses a sample) added in a fixed order by a second
+ * launch, integer histogram counts.  rec (or NULL): the backward's record, 2 + B doubles c1 | c2 | cc_b.  ws: bem_pixstat_loss_ws_bytes
+ * bytes of scratch, 16-byte aligned; its first 512 uint32 hold the counts of pred | gt after the call.  bem_pixstat_loss_chunk: the
+ * elements one workgroup takes of a sample larger than a quarter of it (smaller samples go to workgroups whole, a wave each). */
+int bem_pixstat_loss_chunk(void);
+int64_t bem_pixstat_loss_ws_bytes(int64_t B, int64_t n1);
+int bem_pixstat_loss_f32(const float* pred, const float* gt, float* out, double* rec, void* ws, int64_t B, int64_t n1, double a1,
+                         double a3, double a5, double a6, void* stream);
+/* Backward of bem_pixstat_loss_f32 (my_loss.py:62-74 under autograd; pred alone takes a gradient, the histogram term has none):
+ * dpred = gmul[0] * (c1 clamp(d, -1, 1) + c2 d + cc_b),  c1 = a1 / n,  c2 = a5 * 20 / (ln 10 * n * mse) (0 where mse == 0: torch gives
+ * NaN there),  cc_b = -a6 sign(mean gt_b - mean pred_b) / n with sign(0) = 0; rec as the forward wrote it, gmul = device scalar
+ * dL/dloss (NULL = 1). */
+int bem_pixstat_loss_bwd_f32(const float* pred, const float* gt, const double* rec, float* dpred, int64_t B, int64_t n1,
+                             const float* gmul, void* stream);
+
 /* Backward of bem_iwt_hamilton_f32: dout (B,3,2h,2w) -> dq1w, dq2w (B,16,h,w) (written). */
 int bem_iwt_hamilton_bwd_f32(const float* q1w, const float* q2w, const float* dout, float* dq1w, float* dq2w, int B, int h, int w,
                              void* stream);
