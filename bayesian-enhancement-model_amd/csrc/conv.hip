@@ -382,6 +382,12 @@ __global__ __launch_bounds__(256, MTW == 1 ? 4 : MTW == 2 ? 3 : MTW == 3 ? 2 : 1
             for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.f;
     const float* wl = Wp + lane;
     const int64_t mts = (int64_t)KS * 64;
+    // The packed weight holds cdiv(Cout, 32) M-tiles, which is fewer than MTW where Cout in 97 .. 128 runs on the MTW = 5 instantiation: the tiles
+    // past them are read at tile 0 and masked to zero (wave-uniform, as conv_taps_x6_kernel does), so no load leaves the weight.
+    const int MT = (Cout + 31) >> 5;
+    int64_t moff[MTW];
+#pragma unroll
+    for (int m = 0; m < MTW; ++m) moff[m] = (m < MT ? m : 0) * mts;
     const int rowoff0 = (2 * wave) * S * PWP + j * S, rowoff1 = rowoff0 + S * PWP;
 
     for (int ci0 = 0; ci0 < Cin; ci0 += CIB) {
@@ -421,7 +427,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 4 : MTW == 2 ? 3 : MTW == 3 ? 2 : 1
         for (int m = 0; m < MTW; ++m)
 #pragma unroll
             for (int u = 0; u < PB; ++u)      // clamped address, masked by multiplication (a uniform select becomes a branch + vmcnt(0))
-                an[m][u] = wl[m * mts + (int64_t)min(sg0 + u, KS - 1) * 64] * ((sg0 + u < KS) ? 1.f : 0.f);
+                an[m][u] = wl[moff[m] + (int64_t)min(sg0 + u, KS - 1) * 64] * ((sg0 + u < KS && m < MT) ? 1.f : 0.f);
         for (int s0 = 0; s0 < NS; s0 += PB) {
             float ac[MTW][PB];
 #pragma unroll
@@ -430,7 +436,7 @@ __global__ __launch_bounds__(256, MTW == 1 ? 4 : MTW == 2 ? 3 : MTW == 3 ? 2 : 1
                 for (int u = 0; u < PB; ++u) {
                     ac[m][u] = an[m][u];
                     const int sn = sg0 + s0 + PB + u;
-                    an[m][u] = wl[m * mts + (int64_t)min(sn, KS - 1) * 64] * ((s0 + PB + u < NS && sn < KS) ? 1.f : 0.f);
+                    an[m][u] = wl[moff[m] + (int64_t)min(sn, KS - 1) * 64] * ((s0 + PB + u < NS && sn < KS && m < MT) ? 1.f : 0.f);
                 }
 #pragma unroll
             for (int u = 0; u < PB; ++u) {

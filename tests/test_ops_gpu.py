@@ -311,6 +311,11 @@ def test_dwconv_modes(ops, cfg):
                                  (1, 3, 40, 5, 7, 3, 1), (1, 80, 160, 6, 10, 4, 2), (1, 40, 3, 70, 40, 3, 1),
                                  (1, 40, 80, 32, 64, 4, 2), (2, 80, 160, 16, 16, 4, 2), (1, 8, 24, 6, 4, 4, 2), (1, 40, 80, 12, 20, 4, 2)])   # 4x4-s2: row form / f32-MFMA (Wo = 10)
 def test_conv2d(ops, cfg, monkeypatch):
+    """Dense conv at pad 1 against torch's f32 convolution, whatever form the route gives.  Of the f32-MFMA instantiations these cases reach
+    conv2d_mfma_pipe_kernel<3,3,1,2> (11 -> 40 and 3 -> 40) and conv2d_mfma_kernel<4,4,2,3> / <4,4,2,5> (40 -> 80 at 16x12 and 12x20, 80 -> 160 at
+    6x10); the other cases run the x6 row and tap forms.  The three-channel slice calls (Cin 3, no bias, no residuals) also pass through
+    pipe<3,3,1,1>, pipe<3,3,1,2> and <4,4,2,1|3|5>.  Every instantiation with its epilogue, the other paddings and the direct kernels, against
+    float64: tests/test_conv_forms_gpu.py."""
     B, Ci, Co, H, W, k, s = cfg
     g = torch.Generator().manual_seed(Ci * Co)
     x, w, b = torch.randn(B, Ci, H, W, generator=g), torch.randn(Co, Ci, k, k, generator=g) * (Ci * k * k) ** -0.5, torch.randn(Co, generator=g)
