@@ -1,6 +1,7 @@
 """build_loss (basicsr/losses/__init__.py) for the losses of the hot path's training step.
 
-``L1Loss`` runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn).  ``PerceptualLoss``
+``L1Loss`` runs as one HIP reduction kernel forward and one elementwise kernel backward (bem.autograd.L1LossFn); ``MSELoss`` and
+``CharbonnierLoss``, the other two pixel losses of basic_loss.py, have the same shape (MSELossFn, CharbonnierLossFn).  ``PerceptualLoss``
 (VGG19 features, criterion l1 or l2) is bem.percep's module: one autograd node of HIP kernels (bem.autograd.PerceptualFn); its weights are
 read from a torchvision state dict on disk (bem.percep.weights_path), never fetched.  ``SSIMLoss`` is one tiled HIP kernel forward (plus
 the fixed-order sum of its partials) and one backward (bem.autograd.SSIMLossFn).  ``LPIPSLoss`` is the metric of bem.lpips (v0.1, AlexNet)
@@ -18,7 +19,7 @@ from bem.lpips import LPIPS
 from bem.ops import PIXSTAT_VALUES
 from bem.percep import PerceptualLoss, VGGFeatureExtractor
 
-__all__ = ["build_loss", "L1Loss", "SSIMLoss", "LPIPSLoss", "CombinedLoss", "PerceptualLoss", "VGGFeatureExtractor"]
+__all__ = ["build_loss", "L1Loss", "MSELoss", "CharbonnierLoss", "SSIMLoss", "LPIPSLoss", "CombinedLoss", "PerceptualLoss", "VGGFeatureExtractor"]
 _PIXSTAT_AT = {name: i for i, name in enumerate(PIXSTAT_VALUES)}
 
 LOSS_REGISTRY.register(PerceptualLoss)
@@ -40,6 +41,45 @@ class L1Loss(nn.Module):
         if weight is not None:
             raise NotImplementedError("L1Loss: element-wise weights are not used on the BEM path")
         return _ag.l1_loss(pred, target, self.loss_weight)
+
+
+def _mean_or_sum(name, reduction):
+    """'mean' and 'sum' are one kernel: a sum is the mean under the weight times the element count (``_weight``)."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"Unsupported reduction mode: {reduction}. {name} on the HIP path implements 'mean' and 'sum' (a scalar loss).")
+    return reduction
+
+
+def _weight(mod, pred):
+    return mod.loss_weight * pred.numel() if mod.reduction == "sum" else mod.loss_weight
+
+
+@LOSS_REGISTRY.register()
+class MSELoss(nn.Module):
+    """basicsr/losses/basic_loss.py:55-80: loss_weight * mean (or sum) of (pred - target)^2; per-element weights unsupported."""
+
+    def __init__(self, loss_weight=1.0, reduction="mean"):
+        super().__init__()
+        self.loss_weight, self.reduction = loss_weight, _mean_or_sum("MSELoss", reduction)
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        if weight is not None:
+            raise NotImplementedError("MSELoss: element-wise weights are not used on the BEM path")
+        return _ag.mse_loss(pred, target, _weight(self, pred))
+
+
+@LOSS_REGISTRY.register()
+class CharbonnierLoss(nn.Module):
+    """basicsr/losses/basic_loss.py:83-114: loss_weight * mean (or sum) of sqrt((pred - target)^2 + eps); per-element weights unsupported."""
+
+    def __init__(self, loss_weight=1.0, reduction="mean", eps=1e-12):
+        super().__init__()
+        self.loss_weight, self.reduction, self.eps = loss_weight, _mean_or_sum("CharbonnierLoss", reduction), eps
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        if weight is not None:
+            raise NotImplementedError("CharbonnierLoss: element-wise weights are not used on the BEM path")
+        return _ag.charbonnier_loss(pred, target, _weight(self, pred), self.eps)
 
 
 @LOSS_REGISTRY.register()

@@ -17,7 +17,7 @@ from collections import OrderedDict
 import torch
 
 from basicsr.models import lr_scheduler
-from bem.train import BemAdamW, WeightEma
+from bem.train import BemAdam, BemAdamW, WeightEma
 
 
 class _LazyLog(OrderedDict):
@@ -189,9 +189,9 @@ class BaseModel:
                   {"params": custom, "lr_mult": 1, "decay_mult": 0, "name": "custom_params"}]
         cfg = dict(self.opt["train"]["optim_g"])
         kind = cfg.pop("type")
-        if kind != "AdamW":
-            raise NotImplementedError(f"optimizer {kind} is not supperted yet.")      # the shipped option files use AdamW
-        self.optimizer_g = BemAdamW(groups, **cfg)
+        if kind not in ("Adam", "AdamW"):                                             # image_enhancer_model.py:124-130
+            raise NotImplementedError(f"optimizer {kind} is not supperted yet.")
+        self.optimizer_g = (BemAdamW if kind == "AdamW" else BemAdam)(groups, **cfg)
         self.optimizers.append(self.optimizer_g)
 
     def init_optimizer_and_ema(self):
@@ -251,14 +251,18 @@ class BaseModel:
     def setup_schedulers(self):
         sch = dict(self.opt["train"]["scheduler"])
         kind = sch.pop("type")
-        if kind == "CosineAnnealingRestartCyclicLR":
-            for o in self.optimizers:
-                self.schedulers.append(lr_scheduler.CosineAnnealingRestartCyclicLR(o, **sch))
-        elif kind == "TrueCosineAnnealingLR":
-            for o in self.optimizers:
-                self.schedulers.append(torch.optim.lr_scheduler.CosineAnnealingLR(o, **sch))
-        else:
+        total = self.opt["train"].get("total_iter")                 # LinearLR / VibrateLR take it alone, not the block's keys (:151-158)
+        build = {"MultiStepLR": lambda o: lr_scheduler.MultiStepRestartLR(o, **sch),
+                 "MultiStepRestartLR": lambda o: lr_scheduler.MultiStepRestartLR(o, **sch),
+                 "CosineAnnealingRestartLR": lambda o: lr_scheduler.CosineAnnealingRestartLR(o, **sch),
+                 "CosineAnnealingRestartCyclicLR": lambda o: lr_scheduler.CosineAnnealingRestartCyclicLR(o, **sch),
+                 "TrueCosineAnnealingLR": lambda o: torch.optim.lr_scheduler.CosineAnnealingLR(o, **sch),
+                 "LinearLR": lambda o: lr_scheduler.LinearLR(o, total),
+                 "VibrateLR": lambda o: lr_scheduler.VibrateLR(o, total)}.get(kind)
+        if build is None:           # CosineAnnealingWarmupRestarts / CosineAnnealingLRWithRestart included: the reference's file lacks them too
             raise NotImplementedError(f"Scheduler {kind} is not implemented yet.")
+        for o in self.optimizers:
+            self.schedulers.append(build(o))
 
     def _get_init_lr(self):
         return [[g["initial_lr"] for g in o.param_groups] for o in self.optimizers]

@@ -78,7 +78,8 @@ class ConditionGenerator(BaseModel):
         The step is ~2000 launches on 8x8 .. 2x2 planes, i.e. launch-bound: after one ordinary run per input geometry it is captured into a
         HIP graph and replayed, with everything that differs between iterations read from device memory
         (bem.train.StepState).  BEM_STAGE1_GRAPH=0, injected eps, a distributed run or an active launch profile keep the ordinary form."""
-        if current_iter > self.opt["train"]["scheduler"]["periods"][0]:
+        periods = self.opt["train"]["scheduler"].get("periods")       # a scheduler without periods has no first period: the mask stays
+        if periods and current_iter > periods[0]:
             self.mask = None
         skip = [self.net_g.mask_token] if self.mask is None else []
         if (os.environ.get("BEM_STAGE1_GRAPH", "1") != "0" and bayes.scope.ctx is None and not self.opt.get("dist") and ops._PROF is None

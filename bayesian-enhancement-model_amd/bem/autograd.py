@@ -148,6 +148,46 @@ def l1_loss(pred, gt, weight=1.0):
     return L1LossFn.apply(pred, gt, float(weight))
 
 
+class MSELossFn(Function):
+    """basicsr/losses/basic_loss.py MSELoss(loss_weight, reduction='mean'); only pred takes a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, weight):
+        pred, gt = pred.contiguous(), gt.contiguous()
+        ctx.save_for_backward(pred, gt)
+        ctx.weight = weight
+        return ops.mse_loss(pred, gt, weight).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, gt = ctx.saved_tensors
+        return ops.mse_loss_bwd(pred, gt, ctx.weight, g.reshape(1).contiguous().float()), None, None
+
+
+def mse_loss(pred, gt, weight=1.0):
+    return MSELossFn.apply(pred, gt, float(weight))
+
+
+class CharbonnierLossFn(Function):
+    """basicsr/losses/basic_loss.py CharbonnierLoss(loss_weight, reduction='mean', eps); only pred takes a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, weight, eps):
+        pred, gt = pred.contiguous(), gt.contiguous()
+        ctx.save_for_backward(pred, gt)
+        ctx.weight, ctx.eps = weight, eps
+        return ops.charbonnier_loss(pred, gt, weight, eps).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, gt = ctx.saved_tensors
+        return ops.charbonnier_loss_bwd(pred, gt, ctx.weight, ctx.eps, g.reshape(1).contiguous().float()), None, None, None
+
+
+def charbonnier_loss(pred, gt, weight=1.0, eps=1e-12):
+    return CharbonnierLossFn.apply(pred, gt, float(weight), float(eps))
+
+
 class SSIMLossFn(Function):
     """basicsr/losses/my_loss.py:37-38: weight * (1 - ssim(pred, gt)), 11x11 Gaussian window, data range 1.  The forward launch writes the
     three coefficient maps of the backward when pred wants a gradient; gt takes none."""

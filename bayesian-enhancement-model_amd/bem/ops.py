@@ -1747,6 +1747,32 @@ def mse_loss_bwd(pred, gt, weight=1.0, gmul=None):
     return dp
 
 
+def _charbonnier(what, pred, gt, dp, loss, weight, eps, gmul):
+    if pred.shape != gt.shape:
+        raise ValueError(f"{what}: shapes differ")
+    if not eps >= 0:
+        raise ValueError(f"{what}: eps {eps} must be >= 0")
+    n = pred.numel()
+    ws = torch.empty(int(lib().bem_charbonnier_loss_ws_elems(n)), device=pred.device, dtype=torch.float64)
+    check(lib().bem_charbonnier_loss_f32(_p(pred), _p(gt), _p(dp), _p(loss), _p(ws), n, float(weight), float(eps), _p(gmul), _stream()), what)
+
+
+def charbonnier_loss(pred, gt, weight=1.0, eps=1e-12):
+    """loss (1,) = weight * mean sqrt((pred - gt)^2 + eps), the same bits from call to call."""
+    _chk(pred, "pred"); _chk(gt, "gt")
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    _charbonnier("charbonnier_loss", pred, gt, None, loss, weight, eps, None)
+    return loss
+
+
+def charbonnier_loss_bwd(pred, gt, weight=1.0, eps=1e-12, gmul=None):
+    """dpred = gmul * weight * (pred - gt) / sqrt((pred - gt)^2 + eps) / numel  (gmul: device scalar dL/dloss, None = 1)."""
+    _chk(pred, "pred"); _chk(gt, "gt"); _chk(gmul, "gmul", optional=True)
+    dp = torch.empty_like(pred)
+    _charbonnier("charbonnier_loss_bwd", pred, gt, dp, None, weight, eps, gmul)
+    return dp
+
+
 SSIM_WINDOW = 11          # the Gaussian window of the SSIM loss (sigma 1.5): the valid region of an H x W plane is (H - 10) x (W - 10)
 
 
@@ -2353,17 +2379,26 @@ def grad_sumsq(g, acc):
     return acc
 
 
-def adamw_step_(p, g, m, v, lr, betas, eps, weight_decay, step, max_norm=0.0, sumsq=None, norm_out=None, hyper=None):
-    """hyper: optional device tensor [lr, 1 - beta1^t, sqrt(1 - beta2^t)] read by the kernel in place of ``lr`` / ``step``."""
+def _adam_step(entry, what, p, g, m, v, lr, betas, eps, weight_decay, step, max_norm, sumsq, norm_out, hyper):
     _chk(hyper, "hyper", optional=True)
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n)
     _chk(sumsq, "sumsq", dtype=torch.float64, optional=True); _chk(norm_out, "norm_out", optional=True)
     n = p.numel()
     if g.numel() != n or m.numel() != n or v.numel() != n:
-        raise ValueError("adamw_step: buffer sizes differ")
-    check(lib().bem_adamw_step_f32(_p(p), _p(g), _p(m), _p(v), n, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                   int(step), float(max_norm), _p(sumsq), _p(norm_out), _p(hyper), _stream()), "adamw_step")
+        raise ValueError(f"{what}: buffer sizes differ")
+    check(entry(_p(p), _p(g), _p(m), _p(v), n, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                float(max_norm), _p(sumsq), _p(norm_out), _p(hyper), _stream()), what)
+
+
+def adamw_step_(p, g, m, v, lr, betas, eps, weight_decay, step, max_norm=0.0, sumsq=None, norm_out=None, hyper=None):
+    """hyper: optional device tensor [lr, 1 - beta1^t, sqrt(1 - beta2^t)] read by the kernel in place of ``lr`` / ``step``."""
+    _adam_step(lib().bem_adamw_step_f32, "adamw_step", p, g, m, v, lr, betas, eps, weight_decay, step, max_norm, sumsq, norm_out, hyper)
+
+
+def adam_step_(p, g, m, v, lr, betas, eps, weight_decay, step, max_norm=0.0, sumsq=None, norm_out=None, hyper=None):
+    """torch.optim.Adam's update (weight decay added to the gradient) with adamw_step_'s arguments."""
+    _adam_step(lib().bem_adam_step_f32, "adam_step", p, g, m, v, lr, betas, eps, weight_decay, step, max_norm, sumsq, norm_out, hyper)
 
 
 @_bracket(lambda ema, **_: (12.0 * ema.numel(), 3.0 * ema.numel()))

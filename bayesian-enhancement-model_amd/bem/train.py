@@ -7,7 +7,8 @@ one (``p.grad`` are views; the backward kernels of bem.autograd accumulate strai
   clip       = one sum-of-squares reduction (f64) whose result stays on the device,
   step       = one elementwise kernel that reads the clip coefficient from the device -- no host synchronisation in the step.
 Hyper-parameters, update rule and state layout follow torch.optim.AdamW (decoupled weight decay, bias correction), so a
-``state_dict()`` from here loads into torch.optim.AdamW and back.
+``state_dict()`` from here loads into torch.optim.AdamW and back.  ``BemAdam`` is the same optimizer with torch.optim.Adam's update
+(``optim_g.type: Adam``): the weight decay enters the gradient instead of scaling the parameter, one compile-time flag of the kernel.
 """
 from __future__ import annotations
 
@@ -113,6 +114,8 @@ class WeightEma:
 
 
 class BemAdamW(torch.optim.Optimizer):
+    _step_op = staticmethod(ops.adamw_step_)         # the one launch a subclass replaces (BemAdam)
+
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **ignored):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
@@ -234,9 +237,9 @@ class BemAdamW(torch.optim.Optimizer):
             def hyper(group=group, b1=b1, b2=b2):
                 t = self._steps + 1
                 return [float(group["lr"]), float(1.0 - b1 ** t), float((1.0 - b2 ** t) ** 0.5)]
-            ops.adamw_step_(f["p"], f["g"], f["m"], f["v"], group["lr"], group["betas"], group["eps"], group["weight_decay"], 0,
-                            max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm,
-                            hyper=state.slot(hyper, 3))
+            self._step_op(f["p"], f["g"], f["m"], f["v"], group["lr"], group["betas"], group["eps"], group["weight_decay"], 0,
+                          max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm,
+                          hyper=state.slot(hyper, 3))
         for p, val, m, v in keep:
             p.copy_(val); self.state[p]["exp_avg"].copy_(m); self.state[p]["exp_avg_sq"].copy_(v)
         self._max_norm = 0.0
@@ -257,8 +260,8 @@ class BemAdamW(torch.optim.Optimizer):
         for group, f in zip(self.param_groups, self._flat):
             if f is None:
                 continue
-            ops.adamw_step_(f["p"], f["g"], f["m"], f["v"], group["lr"], group["betas"], group["eps"], group["weight_decay"], self._steps,
-                            max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm)
+            self._step_op(f["p"], f["g"], f["m"], f["v"], group["lr"], group["betas"], group["eps"], group["weight_decay"], self._steps,
+                          max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm)
             for p in f["params"]:
                 self.state[p]["step"] += 1
         for p, val, m, v in keep:
@@ -268,8 +271,8 @@ class BemAdamW(torch.optim.Optimizer):
             self._lag[p] = self._lag.get(p, 0) + 1
         for p in behind:
             (fp, fg, fm, fv), group = self._slices(p)
-            ops.adamw_step_(fp, fg, fm, fv, group["lr"], group["betas"], group["eps"], group["weight_decay"], self._steps - self._lag[p],
-                            max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm)
+            self._step_op(fp, fg, fm, fv, group["lr"], group["betas"], group["eps"], group["weight_decay"], self._steps - self._lag[p],
+                          max_norm=self._max_norm, sumsq=self._sumsq if self._max_norm > 0 else None, norm_out=self._norm)
         self._max_norm = 0.0
         ops.bump_weight_epoch()        # parameters changed behind torch's version counters: derived-weight caches are stale
 
@@ -309,3 +312,16 @@ class BemAdamW(torch.optim.Optimizer):
         self._steps = max((k for _, k in own), default=0)
         self._lag = {p: self._steps - k for p, k in own if k != self._steps}
         ops.bump_weight_epoch()
+
+
+class BemAdam(BemAdamW):
+    """torch.optim.Adam (amsgrad=False, maximize=False) over the flat buffers: everything of BemAdamW but the kernel the step launches
+    (bem_adam_step_f32: g' = g + weight_decay * p feeds the moments, the parameter is not scaled), with torch's defaults
+    (weight_decay = 0).  ``state_dict()`` loads into torch.optim.Adam and back."""
+    _step_op = staticmethod(ops.adam_step_)
+
+    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **ignored):
+        if amsgrad:
+            raise NotImplementedError("BemAdam: amsgrad is not implemented on the HIP path (the fused step keeps no running maximum of the "
+                                      "second moment); remove `amsgrad` from optim_g")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **ignored)

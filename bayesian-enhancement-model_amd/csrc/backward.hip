@@ -5,7 +5,8 @@
 //   - LayerNorm2d backward                        (vmamba.py:58-63)
 //   - depthwise 3x3 + SiLU / GELU-gate backward   (vmamba.py:124,130-131,507-515,708-710)
 //   - PixelUnshuffle(2), channel sums, axpy       (layout / reduction helpers of the chain)
-//   - fused AdamW + global-norm clip on one flat parameter buffer (torch.optim.AdamW, clip_grad_norm_)
+//   - Charbonnier loss + its gradient             (basicsr/losses/basic_loss.py CharbonnierLoss; f64 partials, fixed order)
+//   - fused AdamW / Adam + global-norm clip on one flat parameter buffer (torch.optim.AdamW, torch.optim.Adam, clip_grad_norm_)
 // All f32, NCHW planar; reductions over pixels go wave (DPP / shuffles) -> LDS -> one float atomic per workgroup.
 #include "bem_common.h"
 #include "wavelet.h"
@@ -33,6 +34,64 @@ __global__ __launch_bounds__(256) void l1_kernel(const float* __restrict__ pred,
     if (threadIdx.x == 0) atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
 }
 __global__ void l1_final_kernel(const double* __restrict__ acc, float* __restrict__ loss, double inv_n) { if (loss) loss[0] = (float)(acc[0] * inv_n); }
+
+// ---------------------------------------------------------------- Charbonnier loss ----------------------------------
+// basicsr/losses/basic_loss.py:23-25, CharbonnierLoss: the term sqrt((pred - gt)^2 + eps) in f32, one rounding per operation as torch
+// evaluates it (no fused multiply-add: with eps = 1e-12 the sum decides the value below |d| ~ 1e-6), its gradient d / term (exactly 0
+// at d = 0 for eps > 0).
+__device__ __forceinline__ float charb_term(float d, float eps) { return __fsqrt_rn(__fadd_rn(__fmul_rn(d, d), eps)); }
+
+constexpr int CHARB_MAX_WG = 1024;          // workgroups of the first launch = f64 partials the second one adds
+
+// Grid-stride over 64-bit indices; workgroup b leaves the f64 sum of its terms in part[b] (no atomics: the second launch adds the
+// partials in a fixed order).  VEC (every pointer 16-byte aligned): float4 for the first n / 4 * 4 elements, the last n % 4 go to the
+// first threads of workgroup 0; without VEC one float per access.  dpred (or NULL) = scale * gmul[0] * d / term.
+template <bool VEC>
+__global__ __launch_bounds__(256) void charbonnier_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ dpred,
+                                                          double* __restrict__ part, int64_t n, float eps, float scale,
+                                                          const float* __restrict__ gmul) {
+    __shared__ double sh[4];
+    double s = 0.0;
+    if (gmul) scale *= gmul[0];
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        const float4* p4 = reinterpret_cast<const float4*>(pred);
+        const float4* g4 = reinterpret_cast<const float4*>(gt);
+        for (int64_t i = t; i < n4; i += stride) {
+            const float4 a = p4[i], b = g4[i];
+            const float d[4] = {a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w};
+            float c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { c[j] = charb_term(d[j], eps); s += (double)c[j]; }
+            if (dpred) reinterpret_cast<float4*>(dpred)[i] = make_float4(d[0] / c[0] * scale, d[1] / c[1] * scale, d[2] / c[2] * scale, d[3] / c[3] * scale);
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+            const int64_t i = (n4 << 2) + threadIdx.x;
+            const float d = pred[i] - gt[i], c = charb_term(d, eps);
+            s += (double)c;
+            if (dpred) dpred[i] = d / c * scale;
+        }
+    } else {
+        for (int64_t i = t; i < n; i += stride) {
+            const float d = pred[i] - gt[i], c = charb_term(d, eps);
+            s += (double)c;
+            if (dpred) dpred[i] = d / c * scale;
+        }
+    }
+    s = block_sum<4>(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// loss[0] = (sum of the nparts partials) * weight / n: thread t adds part[t], part[t + 256], ... in that order, the workgroup adds its
+// 256 values by block_sum's fixed tree -- the same bits from call to call.
+__global__ __launch_bounds__(256) void charbonnier_final_kernel(const double* __restrict__ part, int nparts, float* __restrict__ loss, double w_over_n) {
+    __shared__ double sh[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+    s = block_sum<4>(s, sh);
+    if (threadIdx.x == 0) loss[0] = (float)(s * w_over_n);
+}
 
 // ---------------------------------------------------------------- IWT + Hamilton backward ---------------------------
 __global__ void iwt_hamilton_bwd_kernel(const float* __restrict__ q1w, const float* __restrict__ q2w, const float* __restrict__ dout,
@@ -533,9 +592,12 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 // torch.optim.AdamW (decoupled weight decay, bias-corrected) on a flat buffer, with clip_grad_norm_(max_norm) folded in:
 // the clip coefficient min(1, max_norm / (sqrt(sumsq) + 1e-6)) is read from the device (no host round trip) and the clipped
 // gradient is written back, as clip_grad_norm_ does in place.  max_norm <= 0: no clipping.
-__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                             float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, float max_norm,
-                             const double* __restrict__ sumsq, float* __restrict__ norm_out, const float* __restrict__ hyper) {
+// DECOUPLED = false is torch.optim.Adam (amsgrad=False, maximize=False): the weight decay enters the gradient of the moments,
+// g' = g + wd p, instead of scaling the parameter; g' is not written back (torch adds out of place), the clipped g is.
+template <bool DECOUPLED>
+__global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                            float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, float max_norm,
+                            const double* __restrict__ sumsq, float* __restrict__ norm_out, const float* __restrict__ hyper) {
     if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; }     // per-iteration values of a captured step, kept in HBM
     float coef = 1.f;
     if (max_norm > 0.f) {
@@ -545,9 +607,11 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
     }
     const int64_t i = bem_gid1d();
     if (i >= n) return;
-    const float gi = g[i] * coef;
+    float gi = g[i] * coef;
     g[i] = gi;
-    float pi = p[i] * (1.f - lr * wd);
+    float pi = p[i];
+    if (DECOUPLED) pi *= 1.f - lr * wd;
+    else gi += wd * pi;
     const float mi = beta1 * m[i] + (1.f - beta1) * gi;
     const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
     m[i] = mi; v[i] = vi;
@@ -607,6 +671,22 @@ extern "C" int bem_mse_loss_f32(const float* pred, const float* gt, float* dpred
     l1_kernel<true><<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, weight / (float)n, gmul);
     l1_final_kernel<<<1, 1, 0, s>>>(ws, loss, (double)weight / (double)n);
     return bem_check_launch("mse_loss");
+}
+
+extern "C" int64_t bem_charbonnier_loss_ws_elems(int64_t n) { return n > 0 ? std::min<int64_t>(cdiv64(n, 256), CHARB_MAX_WG) : 0; }
+
+extern "C" int bem_charbonnier_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
+                                        float eps, const float* gmul, void* stream) {
+    BEM_REQUIRE(pred && gt && (loss || dpred) && ws && n > 0, "charbonnier_loss: null pointer / empty tensor");
+    BEM_REQUIRE(eps >= 0.f, "charbonnier_loss: eps must be >= 0");
+    hipStream_t s = (hipStream_t)stream;
+    // a NULL dpred adds nothing to the alignment test
+    const bool vec = (((uintptr_t)pred | (uintptr_t)gt | (uintptr_t)dpred) & 15) == 0;
+    const unsigned grid = (unsigned)bem_charbonnier_loss_ws_elems(n);           // one partial per workgroup, whichever form runs
+    if (vec) charbonnier_kernel<true><<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, eps, weight / (float)n, gmul);
+    else charbonnier_kernel<false><<<grid, 256, 0, s>>>(pred, gt, dpred, ws, n, eps, weight / (float)n, gmul);
+    if (loss) charbonnier_final_kernel<<<1, 256, 0, s>>>(ws, (int)grid, loss, (double)weight / (double)n);
+    return bem_check_launch("charbonnier_loss");
 }
 
 namespace {
@@ -750,14 +830,27 @@ extern "C" int bem_grad_sumsq_f32(const float* g, int64_t n, double* acc, void* 
     return bem_check_launch("grad_sumsq");
 }
 
+namespace {
+template <bool DECOUPLED>
+int adam_step(const char* what, float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+              int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper, void* stream) {
+    BEM_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || hyper), "%s: bad arguments", what);
+    BEM_REQUIRE(max_norm <= 0.f || sumsq, "%s: clipping needs the sum of squares from bem_grad_sumsq_f32", what);
+    const double bc1 = 1.0 - pow((double)beta1, step > 0 ? step : 1), bc2 = 1.0 - pow((double)beta2, step > 0 ? step : 1);
+    adam_kernel<DECOUPLED><<<GRID1D(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
+                                                                    (float)sqrt(bc2), max_norm, sumsq, norm_out, hyper);
+    return bem_check_launch(what);
+}
+}  // namespace
+
 extern "C" int bem_adamw_step_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                                   float weight_decay, int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper, void* stream) {
-    BEM_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || hyper), "adamw_step: bad arguments");
-    BEM_REQUIRE(max_norm <= 0.f || sumsq, "adamw_step: clipping needs the sum of squares from bem_grad_sumsq_f32");
-    const double bc1 = 1.0 - pow((double)beta1, step > 0 ? step : 1), bc2 = 1.0 - pow((double)beta2, step > 0 ? step : 1);
-    adamw_kernel<<<GRID1D(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
-                                                          max_norm, sumsq, norm_out, hyper);
-    return bem_check_launch("adamw_step");
+    return adam_step<true>("adamw_step", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, max_norm, sumsq, norm_out, hyper, stream);
+}
+
+extern "C" int bem_adam_step_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper, void* stream) {
+    return adam_step<false>("adam_step", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, max_norm, sumsq, norm_out, hyper, stream);
 }
 
 extern "C" int bem_ema_update_f32(float* ema, const float* p, int64_t n, float decay, float one_minus_decay, void* stream) {

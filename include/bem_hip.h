@@ -515,6 +515,16 @@ int bem_ssim_loss_bwd_f32(const float* pred, const float* gt, const float* coef,
 int bem_mse_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
                      const float* gmul, void* stream);
 
+/* CharbonnierLoss(reduction='mean') under a weight (basicsr/losses/basic_loss.py:23-25, 96-115), the contract of bem_l1_loss_f32 with
+ * c = sqrt((pred - gt)^2 + eps) evaluated in f32 one operation at a time (eps >= 0 is not folded away: 1e-12 decides c below
+ * |pred - gt| ~ 1e-6): loss[0] (or NULL) = weight * mean c; dpred (or NULL) = gmul[0] * weight * (pred - gt) / c / n, exactly 0 where
+ * pred == gt (eps > 0).  Bit-reproducible from call to call: one f64 partial per workgroup in ws, added in a fixed order by a second
+ * launch; no atomics.  16-byte vector accesses when pred, gt and dpred are all 16-byte aligned (the last n % 4 elements one by one),
+ * single floats otherwise.  ws: bem_charbonnier_loss_ws_elems(n) doubles of scratch (every one written by the call). */
+int64_t bem_charbonnier_loss_ws_elems(int64_t n);
+int bem_charbonnier_loss_f32(const float* pred, const float* gt, float* dpred, float* loss, double* ws, int64_t n, float weight,
+                             float eps, const float* gmul, void* stream);
+
 /* The per-pixel statistics of CombinedLoss (basicsr/losses/my_loss.py:51-74) in one pass over pred and gt, contiguous (B, n1) f32 with
  * n1 = C*H*W elements per sample, d = pred - gt, n = B * n1 < 2^32 (the histogram counters are 32 bits wide; refused above):
  *   out[1] smooth_l1 = mean(|d| < 1 ? d^2 / 2 : |d| - 1/2)                         (my_loss.py:30-31)
@@ -638,6 +648,13 @@ int bem_grad_sumsq_f32(const float* g, int64_t n, double* acc, void* stream);
 int bem_adamw_step_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                        float weight_decay, int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper,
                        void* stream);
+/* torch.optim.Adam (amsgrad=False, maximize=False) in place of AdamW, everything else as bem_adamw_step_f32 (the clip, norm_out,
+ * hyper): the weight decay enters the gradient the moments see, g' = g + weight_decay * p, and the parameter is not scaled:
+ *   m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).
+ * g receives the clipped gradient, not g'.  One kernel body with AdamW, chosen by a compile-time flag. */
+int bem_adam_step_f32(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int step, float max_norm, const double* sumsq, float* norm_out, const float* hyper,
+                      void* stream);
 
 /* base_model.py:77-84: ema = decay * ema + (1 - decay) * p over n floats.
  * The averaged copy of the weights (train.ema_decay), one launch per flat parameter buffer, after the optimizer step.  The host passes
